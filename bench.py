@@ -44,6 +44,9 @@ whole job), plus
   cpu_baseline the CPU restatement (oracle/, single thread like the reference's
                extractor) timed on this box on the 512^3 metric volume, N = 1 only;
                cpu_baseline_ncores: its OpenMP build on all host cores of the box
+
+`--dump-outputs DIR` (N = 1) also writes the records of the last timed step to DIR
+as .npy files (dump_outputs), so that two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -81,6 +84,29 @@ def resolve_volume(args):
         desc = 0
     label = "%d^3" % nx if nx == ny == nz else "%d x %d x %d" % (nx, ny, nz)
     return nx, ny, nz, desc, label
+
+
+DUMP_BUDGET = 64 * 10 ** 6   # bytes --dump-outputs may write in all
+
+
+def dump_outputs(recs, out_dir, budget=DUMP_BUDGET):
+    """--dump-outputs: the records of one extraction as out_dir/<field>.npy, what a caller of Context.extract receives -- the
+    float fields as float32, `info` (uint32 flags) as float64, which holds them exactly -- and out_dir/index.npy, the record
+    numbers written.  When all records would exceed `budget` bytes, a sample of them drawn with a fixed seed, in record order."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(recs)
+    names = recs.dtype.names
+    per_rec = 8 + sum(8 if f == "info" else recs.dtype[f].itemsize for f in names)   # 8: the index entry
+    headers = 128 * (len(names) + 1)   # .npy header of each file
+    index = np.arange(n)
+    if n * per_rec + headers > budget:
+        index = np.sort(np.random.default_rng(12345).choice(n, (budget - headers) // per_rec, replace=False))
+    arrays = {f: recs[f][index].astype(np.float64 if f == "info" else np.float32) for f in names}
+    arrays["index"] = index.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "records": n, "written": len(index), "sampled": bool(len(index) < n),
+            "bytes": sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in arrays)}
 
 
 def blur_source_hash():
@@ -556,7 +582,15 @@ def main():
     ap.add_argument("--launch-check", default=None, choices=["ok", "fail"],
                     help="only bring the ranks up (process group over gloo, no GPU call), print a line with the world size "
                          "seen and leave -- 'fail': rank 1 exits with code 7 instead (tests of the self-launch path)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="--gpus 1: after the timed steps, write the records of the last timed step as DIR/<field>.npy (float32; "
+                         "info as float64) and their record numbers as DIR/index.npy, at most 64 MB in all (beyond that a sample "
+                         "drawn with a fixed seed); the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus != 1 or args.mode == "zslab_c"):
+        ap.error("--dump-outputs writes the single-GPU path's records: --gpus 1 only")
 
     if args.mode == "zslab_c":   # one process over all devices: no launcher, no torch
         pkg = importlib.import_module("3d_sift_cuda_amd")
@@ -972,6 +1006,8 @@ def main():
     if rank != 0:
         return
     if world == 1 or args.mode == "volumes":
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(gpu_recs, args.dump_outputs)
         print(json.dumps(out), flush=True)
         return
     # ---- N > 1: the line's value is the Z-slab split of ONE volume over the N GPUs (strong scaling) ----

@@ -82,3 +82,45 @@ def test_volume_presets_and_the_one_gpu_refusal():
     assert bench.resolve_volume(ns(size=256)) == (256, 256, 256, 0, "256^3")
     r = subprocess.run([sys.executable, BENCH, "--config", "c4"], capture_output=True, text=True, env=_env(), timeout=120)
     assert r.returncode != 0 and "multi-GPU configuration" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_steps_and_dump_outputs_are_checked_before_any_gpu_call(tmp_path):
+    """--steps 0 would time nothing; --dump-outputs writes the single-GPU path's records.  Both refused at parse time."""
+    for args, msg in ((["--steps", "0"], "--steps must be at least 1"),
+                      (["--gpus", "2", "--dump-outputs", str(tmp_path / "d")], "--gpus 1 only")):
+        r = subprocess.run([sys.executable, BENCH] + args, capture_output=True, text=True, env=_env(), timeout=120)
+        assert r.returncode != 0 and msg in r.stderr, r.stderr[-2000:]
+    assert not os.path.exists(tmp_path / "d")
+
+
+def test_dump_outputs_writes_the_records_within_the_budget(tmp_path):
+    """bench.dump_outputs: every record field as float32 (info as float64, exact for uint32) and the record numbers; above the
+    byte budget a sample drawn with a fixed seed, the same on every call, in record order."""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    pkg = importlib.import_module("3d_sift_cuda_amd")
+    rng = np.random.default_rng(7)
+    recs = np.zeros(1000, pkg.FEATURE_DTYPE)
+    for f in recs.dtype.names:
+        recs[f] = rng.integers(0, 2 ** 32, recs[f].shape, dtype=np.uint64) if f == "info" else rng.standard_normal(recs[f].shape)
+
+    def load(d):
+        return {f: np.load(os.path.join(d, f + ".npy")) for f in recs.dtype.names + ("index",)}
+
+    full = bench.dump_outputs(recs, str(tmp_path / "full"))
+    assert full["records"] == full["written"] == 1000 and not full["sampled"] and full["bytes"] <= bench.DUMP_BUDGET
+    a = load(tmp_path / "full")
+    assert (a["index"] == np.arange(1000)).all() and a["info"].dtype == np.float64 and a["desc"].dtype == np.float32
+    for f in recs.dtype.names:
+        assert (a[f] == recs[f]).all(), f
+    budget = 100000
+    s1 = bench.dump_outputs(recs, str(tmp_path / "s1"), budget)
+    s2 = bench.dump_outputs(recs, str(tmp_path / "s2"), budget)
+    assert s1["sampled"] and 0 < s1["written"] < 1000 and s1["bytes"] <= budget
+    b, c = load(tmp_path / "s1"), load(tmp_path / "s2")
+    idx = b["index"].astype(np.int64)
+    assert (np.diff(idx) > 0).all() and (b["index"] == c["index"]).all()
+    for f in recs.dtype.names:
+        assert (b[f] == recs[f][idx]).all() and (c[f] == b[f]).all(), f

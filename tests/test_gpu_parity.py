@@ -1712,3 +1712,25 @@ def test_roofline_ceiling_probe_runs(built):
     assert 0.0 < one < two < 1.0, list(ms)                      # 256^3: 16.8 M voxels, 8 and 12 B each: tens of microseconds
     assert 8.0 * 256 ** 3 / (one * 1e-3) / 1e9 < 8000.0          # below the HBM peak
     assert L.roof_march(100, 5, ms) != 0                         # a volume its tiles do not divide is refused, not marched out of bounds
+
+
+def test_bench_dump_outputs_are_the_timed_steps_records(built, oracle, tmp_path):
+    """bench.py --dump-outputs: the files hold the records of the timed path's last step, and with --steps 2 two steps are
+    timed.  Checked against the oracle on the seeded volume bench.py extracts (same bar as smoke())."""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--size", "256", "--steps", "2", "--warmup", "1",
+                        "--cpu-sample", "0", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    d = line["dump_outputs"]
+    assert line["steps"] == 2 and d["records"] == d["written"] == line["config"]["records_per_volume"] and not d["sampled"]
+    got = {f: np.load(out / (f + ".npy")) for f in built.FEATURE_DTYPE.names + ("index",)}
+    assert all(a.dtype == (np.float64 if f in ("info", "index") else np.float32) for f, a in got.items())
+    want, _ = oracle.extract(built.synth_blobs(256, 256, 256, seed=12345))
+    assert len(want) == d["records"] and (got["index"] == np.arange(len(want))).all()
+    assert (got["info"] == want["info"]).all() and (got["desc"] == want["desc"]).all()
+    for f in ("x", "y", "z", "scale", "ori", "eigs"):
+        assert np.abs(got[f] - want[f]).max() <= TOL, f

@@ -1,8 +1,10 @@
 """CPU suite: the oracle against everything that pins it.
 
 1. bit-exact against the partial reference build oracle/_ref (taps, SVD, 3x3
-   inverse, stable high-low sort) when that library is present, and against the
-   committed reference-generated tap fixture always;
+   inverse, stable high-low sort, .key / image.pgm I/O, matcher distance, world
+   frame): against that library when it is built, else against the digests of
+   its outputs stored in tests/golden/ref_source_digests.json; and against the
+   committed reference-generated tap fixture;
 2. end-to-end against the .key files written by the CPU featExtract binary
    shipped in the reference repository (tests/golden/refbin_*.key): identical
    record count, info flags and near-identical geometry / ranks (that binary is
@@ -11,6 +13,7 @@
 4. its own committed outputs (regression).
 """
 import gzip
+import hashlib
 import json
 import os
 
@@ -21,10 +24,34 @@ import _oracle
 from keyio import read_key
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF_DIGESTS = os.path.join(GOLD, "ref_source_digests.json")
+WRITER_THRESHOLDS = [140.0, -1.0, 27.0, 1e9]
+recorded = None   # tests/golden/make_golden.py sets a dict here: ref_digest() then collects the live digests instead of checking them
 
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def sha(b):
+    return hashlib.sha256(b).hexdigest()
+
+
+def ref_digest(key, run):
+    """SHA-256 of the bytes run(ref) gets from the partial reference build oracle/_ref for the test's fixed, seeded inputs.
+    oracle/_ref can only be built where the reference sources are; where it is, the reference runs and must still give the
+    digest stored in tests/golden/ref_source_digests.json, and everywhere else the stored digest stands in for it."""
+    ref = _oracle.load_ref()
+    if ref is not None:
+        live = sha(run(ref))
+        if recorded is not None:
+            recorded[key] = live
+            return live
+    stored = json.load(open(REF_DIGESTS))["digests"]
+    assert key in stored, "%s: no digest in %s (tests/golden/make_golden.py writes them)" % (key, REF_DIGESTS)
+    if ref is not None:
+        assert live == stored[key], "%s: oracle/_ref no longer gives the stored digest" % key
+    return stored[key]
 
 
 def test_taps_match_reference_fixture(oracle):
@@ -43,45 +70,76 @@ def test_taps_match_reference_fixture(oracle):
         assert (bits(oracle.taps(sigma, 0.01)) == bits(want / s)).all(), name
 
 
+def _taps_bytes(taps, sigmas):
+    return b"".join(np.int32(len(t)).tobytes() + bits(t).tobytes() for t in (taps(sg) for sg in sigmas))
+
+
+def _ref_taps(ref, sg):
+    n = ref.ref_gauss_filter_size(float(sg), 0.01)
+    t = np.zeros(n, np.float32)
+    ref.ref_gauss_taps_raw(float(sg), n, t.ctypes.data)
+    return t
+
+
+def _svd_bytes(svd3, sort_eig, mats):
+    out = []
+    for m in mats:
+        m, w, v = m.copy(), np.zeros(3, np.float32), np.zeros(9, np.float32)
+        svd3(m.ctypes.data, w.ctypes.data, v.ctypes.data)
+        sort_eig(w.ctypes.data, v.ctypes.data)
+        out += [w, v, m.ravel()]
+    return np.concatenate(out).tobytes()
+
+
+def _invert_bytes(invert3, vecs):
+    out = []
+    for a in vecs:
+        b = np.zeros(9, np.float32)
+        invert3(a.ctypes.data, b.ctypes.data)
+        out.append(b)
+    return np.concatenate(out).tobytes()
+
+
+def _sort_bytes(sort_high_low, lists):
+    out = []
+    for a in lists:
+        a = a.copy()
+        sort_high_low(a.ctypes.data, len(a))
+        out.append(a.tobytes())
+    return b"".join(out)
+
+
 def test_partial_reference_build(oracle):
-    ref = _oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
+    """Taps (120 sigmas), the 3x3 SVD with its eigen sort (4000 matrices), the 3x3 inverse (4000) and the stable high-low
+    sort (500 lists): the oracle's output bytes are the partial reference build's."""
     rng = np.random.default_rng(1)
-    for sg in list(np.linspace(0.3, 8.0, 120)):
-        n = ref.ref_gauss_filter_size(float(sg), 0.01)
-        t = np.zeros(n, np.float32)
-        ref.ref_gauss_taps_raw(float(sg), n, t.ctypes.data)
-        assert (bits(oracle.taps(sg, 0.01, normalise=False)) == bits(t)).all()
+    sigmas = list(np.linspace(0.3, 8.0, 120))
+    mats, vecs, lists = [], [], []
     for t in range(4000):
         g = rng.standard_normal((515, 3)).astype(np.float32) * np.float32(rng.uniform(0.01, 10))
         if t % 3 == 0:
             g[:, 2] *= np.float32(1e-3)
-        m = (g.T @ g).astype(np.float32)
+        # g^T g from exact float64 products summed in a fixed order, then rounded: the same bits on every host (a float32 BLAS
+        # product sums in an order that depends on the library and the CPU, and the stored digests need identical inputs)
+        g64 = g.astype(np.float64)
+        m = (g64[:, :, None] * g64[:, None, :]).sum(0).astype(np.float32)
         if t % 50 == 0:
             m = np.diag(rng.uniform(0, 3, 3)).astype(np.float32)
-        m1, m2 = m.copy(), m.copy()
-        w1, w2 = np.zeros(3, np.float32), np.zeros(3, np.float32)
-        v1, v2 = np.zeros(9, np.float32), np.zeros(9, np.float32)
-        oracle.L.o3_svd3(m1.ctypes.data, w1.ctypes.data, v1.ctypes.data)
-        ref.ref_svd3(m2.ctypes.data, w2.ctypes.data, v2.ctypes.data)
-        oracle.L.o3_sort_eig(w1.ctypes.data, v1.ctypes.data)
-        ref.ref_sort_eig(w2.ctypes.data, v2.ctypes.data)
-        assert (bits(w1) == bits(w2)).all() and (bits(v1) == bits(v2)).all() and (bits(m1) == bits(m2)).all()
-        a = rng.standard_normal(9).astype(np.float32)
-        b1, b2 = np.zeros(9, np.float32), np.zeros(9, np.float32)
-        oracle.L.o3_invert3(a.ctypes.data, b1.ctypes.data)
-        ref.ref_invert3(a.ctypes.data, b2.ctypes.data)
-        assert (bits(b1) == bits(b2)).all()
+        mats.append(m)
+        vecs.append(rng.standard_normal(9).astype(np.float32))
     for t in range(500):
         n = int(rng.integers(0, 125))
         a = np.zeros(n, _oracle.EXT)
         a["x"] = np.arange(n)
         a["value"] = rng.integers(0, 8, n).astype(np.float32) if t % 2 else rng.standard_normal(n).astype(np.float32)
-        b = a.copy()
-        oracle.L.o3_sort_high_low(a.ctypes.data, n)
-        ref.ref_sort_high_low(b.ctypes.data, n)
-        assert (a == b).all()
+        lists.append(a)
+    assert sha(_taps_bytes(lambda sg: oracle.taps(sg, 0.01, normalise=False), sigmas)) == \
+        ref_digest("taps", lambda ref: _taps_bytes(lambda sg: _ref_taps(ref, sg), sigmas))
+    assert sha(_svd_bytes(oracle.L.o3_svd3, oracle.L.o3_sort_eig, mats)) == \
+        ref_digest("svd3_sort_eig", lambda ref: _svd_bytes(ref.ref_svd3, ref.ref_sort_eig, mats))
+    assert sha(_invert_bytes(oracle.L.o3_invert3, vecs)) == ref_digest("invert3", lambda ref: _invert_bytes(ref.ref_invert3, vecs))
+    assert sha(_sort_bytes(oracle.L.o3_sort_high_low, lists)) == \
+        ref_digest("sort_high_low", lambda ref: _sort_bytes(ref.ref_sort_high_low, lists))
 
 
 def _oracle_key(oracle, built, tmp_path, n, mode=0, seed=12345, dims=None):
@@ -286,14 +344,7 @@ def test_openmp_build_is_byte_identical(oracle, built, dims, mode, scale):
 
 
 # ---- round 4: the reference's own .key reader / writers, image.pgm writer, matcher distance and world-frame rotation,
-# ---- compiled from /root/reference as they lie (oracle/ref_driver.cpp), against the product's host code and the oracle's
-
-
-def _need_ref():
-    ref = _oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    return ref
+# ---- compiled from the reference sources as they lie (oracle/ref_driver.cpp), against the product's host code and the oracle's
 
 
 def _adversarial_records(built, rng):
@@ -331,64 +382,77 @@ def _adversarial_records(built, rng):
     return np.concatenate([recs, extra, edge, fuzz])
 
 
-@pytest.mark.parametrize("thres", [140.0, -1.0, 27.0, 1e9])
+@pytest.mark.parametrize("thres", WRITER_THRESHOLDS)
 def test_key_writers_against_reference_source(oracle, built, tmp_path, thres):
     """Row O1 of SURVEY.md 8a and the writer half of 8f-3: csrc/keyfile.c and the oracle's writer produce the bytes of
     msFeature3DVectorOutputText / msFeature3DVectorOutputBin (R/src_common/MultiScale.h:386-474, :228-303) instantiated
     from the reference's header, for golden, adversarial and random records, with and without the eigenvalue filter."""
-    ref = _need_ref()
     import ctypes as C
     recs = _adversarial_records(built, np.random.default_rng(4))
     comments = ["Extraction Voxel Resolution (ijk) : 64 64 64", "Extraction Voxel Size (mm)  (ijk) : 1.000000 1.000000 1.000000",
                 "Feature Coordinate Space: voxels: 1.0 0.0 0.0 0.0 0.0 1.0 0.0 0.0 0.0 0.0 1.0 0.0 0.0 0.0 0.0 1.0"]
-    for cm in (comments, []):
-        pr, pp, po = str(tmp_path / "ref.key"), str(tmp_path / "prod.key"), str(tmp_path / "orc.key")
+    pr = str(tmp_path / "ref.key")
+
+    def ref_text(ref, cm):
         arr = (C.c_char_p * max(1, len(cm)))(*[c.encode() for c in cm])
         assert ref.ref_write_key_text(recs.ctypes.data, len(recs), pr.encode(), thres, len(cm), C.cast(arr, C.c_void_p)) == 0
+        return open(pr, "rb").read()
+
+    def ref_bin(ref):
+        assert ref.ref_write_key_bin(recs.ctypes.data, len(recs), pr.encode(), thres) == 0
+        return open(pr, "rb").read()
+
+    for cm in (comments, []):
+        pp, po = str(tmp_path / "prod.key"), str(tmp_path / "orc.key")
         built.write_key(pp, recs, eig_thres=thres, comments=cm)
         oracle.write_key(po, recs, eig_thres=thres, comments=cm)
-        want = open(pr, "rb").read()
-        assert len(want) > 1000
-        assert open(pp, "rb").read() == want
-        assert open(po, "rb").read() == want
-    pr, pp = str(tmp_path / "ref.bin"), str(tmp_path / "prod.bin")
-    assert ref.ref_write_key_bin(recs.ctypes.data, len(recs), pr.encode(), thres) == 0
+        want = ref_digest("key_text thres=%r comments=%d" % (thres, len(cm)), lambda ref: ref_text(ref, cm))
+        mine = open(pp, "rb").read()
+        assert len(mine) > 1000
+        assert sha(mine) == want
+        assert sha(open(po, "rb").read()) == want
+    pp = str(tmp_path / "prod.bin")
     built.write_key_bin(pp, recs, eig_thres=thres)
-    assert open(pp, "rb").read() == open(pr, "rb").read()
+    assert sha(open(pp, "rb").read()) == ref_digest("key_bin thres=%r" % thres, ref_bin)
 
 
 def test_key_reader_against_reference_source(built, tmp_path):
     """The reader half of SURVEY.md 8f-3: sift3d_read_key returns the records msFeature3DVectorInputText
     (R/src_common/MultiScale.h:305-384) reads, bit for bit -- on every committed .key file and on a file of adversarial
     values -- and refuses what the reference's reader refuses (no Features line, zero features, wrong column line)."""
-    ref = _need_ref()
     import ctypes as C
+
+    def ref_read(ref, path, cap):
+        buf = np.zeros(cap, built.FEATURE_DTYPE)
+        n = C.c_int(0)
+        rc = ref.ref_read_key_text(path.encode(), buf.ctypes.data, cap, C.byref(n))
+        return b"rc %d " % rc + buf[:n.value].tobytes()
+
     files = [os.path.join(GOLD, f) for f in sorted(os.listdir(GOLD)) if f.endswith(".key")]
     p = str(tmp_path / "adv.key")
     built.write_key(p, _adversarial_records(built, np.random.default_rng(9)), eig_thres=-1.0, comments=["a", "b", "c"])
     files.append(p)
     assert len(files) >= 8
     for f in files:
+        want = None
         for mode in (0, 1):   # round 5: 0 = the parallel in-memory reader (with its fall-backs), 1 = the fscanf loop
             built.host_lib().sift3d_read_key_mode(mode)
             try:
                 mine = built.read_key(f)
             finally:
                 built.host_lib().sift3d_read_key_mode(0)
-            buf = np.zeros(len(mine) + 8, mine.dtype)
-            n = C.c_int(0)
-            assert ref.ref_read_key_text(f.encode(), buf.ctypes.data, len(buf), C.byref(n)) == 0
-            assert n.value == len(mine) > 0
-            assert buf[:n.value].tobytes() == mine.tobytes(), (f, mode)
+            assert len(mine) > 0
+            if want is None:
+                name = "adversarial" if f == p else os.path.basename(f)
+                want = ref_digest("read_key %s" % name, lambda ref: ref_read(ref, f, len(mine) + 8))
+            assert sha(b"rc 0 " + mine.tobytes()) == want, (f, mode)
     bad = {"nofeat.key": "# featExtract 1.1\nScale-space location[x y z scale]\n",
            "zero.key": "# featExtract 1.1\nFeatures: 0\nScale-space location[x y z scale]\n",
            "cols.key": "# featExtract 1.1\nFeatures: 1\nsomething else\n1 2 3\n"}
     for name, text in bad.items():
         q = str(tmp_path / name)
         open(q, "w").write(text)
-        n = C.c_int(0)
-        buf = np.zeros(4, built.FEATURE_DTYPE)
-        assert ref.ref_read_key_text(q.encode(), buf.ctypes.data, 4, C.byref(n)) == -1
+        assert ref_digest("read_key refuses %s" % name, lambda ref: ref_read(ref, q, 4)[:6]) == sha(b"rc -1 ")
         with pytest.raises(built.Sift3DError):
             built.read_key(q)
 
@@ -396,7 +460,12 @@ def test_key_reader_against_reference_source(built, tmp_path):
 def test_image_pgm_against_reference_source(built, tmp_path):
     """./image.pgm (SURVEY.md 8b, optional side effect): sift3d_write_pgm against output_float + GenericImage::WriteToFile
     compiled from the reference (PpImageFloatOutput.cpp:131-180, GenericImage.cpp:135-180)."""
-    ref = _need_ref()
+    pr, pp = str(tmp_path / "r.pgm"), str(tmp_path / "p.pgm")
+
+    def ref_pgm(ref, a):
+        assert ref.ref_output_float_pgm(a.ctypes.data, a.shape[0], a.shape[1], pr.encode()) == 0
+        return open(pr, "rb").read()
+
     rng = np.random.default_rng(2)
     for (rows, cols) in [(64, 64), (37, 53), (1, 9), (7, 1), (128, 96)]:
         for kind in range(3):
@@ -405,35 +474,34 @@ def test_image_pgm_against_reference_source(built, tmp_path):
                 a += np.float32(100.0)
             if a.max() == a.min():
                 continue
-            pr, pp = str(tmp_path / "r.pgm"), str(tmp_path / "p.pgm")
-            assert ref.ref_output_float_pgm(a.ctypes.data, rows, cols, pr.encode()) == 0
             built.write_pgm(pp, a)
-            assert open(pp, "rb").read() == open(pr, "rb").read()
-    vol = built.synth_blobs(64, 64, 64)[32]
-    pr, pp = str(tmp_path / "r.pgm"), str(tmp_path / "p.pgm")
-    ref.ref_output_float_pgm(np.ascontiguousarray(vol).ctypes.data, 64, 64, pr.encode())
+            assert sha(open(pp, "rb").read()) == ref_digest("pgm %dx%d kind %d" % (rows, cols, kind), lambda ref: ref_pgm(ref, a))
+    vol = np.ascontiguousarray(built.synth_blobs(64, 64, 64)[32])
     built.write_pgm(pp, vol)
-    assert open(pp, "rb").read() == open(pr, "rb").read()
+    assert sha(open(pp, "rb").read()) == ref_digest("pgm blob64 plane 32", lambda ref: ref_pgm(ref, vol))
 
 
 def test_matcher_distance_against_reference_source(oracle, built):
     """The distance under which the matcher's search is exact: Feature3DInfo::DistSqrPCs (R/src_common/MultiScale.h:61-73)
     compiled from the reference's header equals the integer distance of the oracle's brute-force search (and of
     sift3d_knn64, which the GPU suite holds to that oracle) for rank descriptors and for any bytes 0..127."""
-    ref = _need_ref()
     rng = np.random.default_rng(3)
+    pairs = []
     for t in range(400):
         if t % 2:
             a, b = rng.permutation(64), rng.permutation(64)
         else:
             a, b = rng.integers(0, 128, 64), rng.integers(0, 128, 64)
         fa, fb = a.astype(np.float32), b.astype(np.float32)
-        d_ref = ref.ref_dist_sqr_pcs(fa.ctypes.data, fb.ctypes.data, 64)
+        pairs.append((fa, fb))
         idx, d2 = oracle.knn64(b.astype(np.int8)[None, :], a.astype(np.int8)[None, :], 1)
-        assert idx[0, 0] == 0 and float(d2[0, 0]) == d_ref == float(((a - b) ** 2).sum())
+        assert idx[0, 0] == 0 and float(d2[0, 0]) == float(((a - b) ** 2).sum())
         f = np.zeros(1, built.FEATURE_DTYPE)
         f["desc"] = fa
         assert (built.match_descriptors(f)[0] == a).all()
+    exact = np.array([((fa - fb) ** 2).sum(dtype=np.float64) for fa, fb in pairs], np.float32)   # integers < 2^24: exact
+    assert sha(exact.tobytes()) == ref_digest(
+        "dist_sqr_pcs", lambda ref: np.array([ref.ref_dist_sqr_pcs(fa.ctypes.data, fb.ctypes.data, 64) for fa, fb in pairs], np.float32).tobytes())
 
 
 def test_match_descriptors_refuses_what_is_not_a_byte(built):
@@ -451,9 +519,9 @@ def test_world_orientation_against_reference_source(built):
     invert_3x3<float,float>, mult_3x3_matrix<float,float>, invert_3x3<float,float> of the reference's header applied as
     featExtract.cpp:535-537 does, bit for bit; the row normalisation in front (vec3D_norm_3d, in a file that does not
     compile here) is restated in numpy the way csrc/world.c cites it."""
-    ref = _need_ref()
     rng = np.random.default_rng(6)
     recs = built.read_key(os.path.join(GOLD, "oracle_blob64_sift.key"))
+    rots, mine = [], []
     for t in range(40):
         q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
         m = np.eye(4, dtype=np.float32)
@@ -464,8 +532,16 @@ def test_world_orientation_against_reference_source(built):
             ss = np.float32(np.float32(np.float32(m[i, 0] * m[i, 0]) + np.float32(m[i, 1] * m[i, 1])) + np.float32(m[i, 2] * m[i, 2]))
             div = np.float32(1.0 / float(np.sqrt(ss, dtype=np.float32)))
             rot[i] = m[i, :3] * div
-        out = built.world_transform(recs, m)
-        for r_in, r_out in zip(recs[:60], out[:60]):
-            ori = r_in["ori"].copy()
-            ref.ref_world_orientation(rot.ctypes.data, ori.ctypes.data)
-            assert (bits(ori) == bits(r_out["ori"])).all()
+        rots.append(rot)
+        mine.append(bits(built.world_transform(recs, m)[:60]["ori"]).tobytes())
+
+    def ref_frames(ref):
+        out = []
+        for rot in rots:
+            for r_in in recs[:60]:
+                ori = r_in["ori"].copy()
+                ref.ref_world_orientation(rot.ctypes.data, ori.ctypes.data)
+                out.append(bits(ori).tobytes())
+        return b"".join(out)
+
+    assert sha(b"".join(mine)) == ref_digest("world_orientation", ref_frames)
