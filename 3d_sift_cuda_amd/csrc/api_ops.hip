@@ -386,7 +386,7 @@ int cand_append(sift3d_ctx *c, const level_job &j, bool record)
     const cand_target tg = cand_target_of(c);
     HIPCHK(c, sift3d_launch_extrema(st, j.dp, j.dc, j.dn, j.X, j.Xl ? j.Xl : j.X, j.Y, j.Z, j.z_lo, j.z_hi, j.lvl_id, tg.keys,
                                     tg.vals, tg.count, tg.cap, surv, counters, c->d_count + 2, cover, !fresh,
-                                    lazy ? &lz : nullptr));
+                                    lazy ? &lz : nullptr, c->strict_extrema));
     return SIFT3D_OK;
 }
 
@@ -478,6 +478,8 @@ extern "C" int sift3d_extrema(sift3d_ctx *c, const float *d_prev, const float *d
     if (d_next) HIPCHK(c, hipMemcpyAsync(c->D[2], d_next, b, hipMemcpyHostToDevice, c->stream));
     c->has_volume = false;
     c->pad_nx = 0; /* the level buffers were used as dense scratch: their pad columns must be cleared again */
+    /* the own level decides the first pass's form; d_prev / d_next are compared element by element in every form */
+    c->strict_extrema = sift3d_volume_needs_strict(d_cur, nx * ny * nz);
     int64_t cnt = 0;
     rc = cand_reset(c);
     if (!rc) rc = cand_append(c, {c->D[0], c->D[1], d_next ? c->D[2] : nullptr, nx, ny, nz, 0, (int)nz, 0}, true);

@@ -86,6 +86,20 @@ static int load_volume(sift3d_ctx *c, const float *src, bool from_host, int64_t 
     return SIFT3D_OK;
 }
 
+/* Once per volume, where it is set: does it hold a value that sends the first extrema pass to its element-wise form
+ * (sift3d_volume_needs_strict)?  c->vol with its pitched rows (the pad columns are zeros).  d_count[7] is free outside an
+ * extraction; the read-back waits for the stream, which every caller of this does anyway. */
+static int scan_volume(sift3d_ctx *c, int64_t nx, int64_t ny, int64_t nz)
+{
+    unsigned long long flag = 0;
+    HIPCHK(c, hipMemsetAsync(c->d_count + 7, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, sift3d_launch_scan_strict(c->stream, c->vol, pitch_of(nx) * ny * nz, (unsigned *)(c->d_count + 7)));
+    HIPCHK(c, hipMemcpyAsync(&flag, c->d_count + 7, sizeof flag, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->strict_extrema = flag != 0;
+    return SIFT3D_OK;
+}
+
 extern "C" int sift3d_set_volume(sift3d_ctx *c, const float *vol, int64_t nx, int64_t ny, int64_t nz)
 {
     NEED_LEVELS(c);
@@ -96,7 +110,8 @@ extern "C" int sift3d_set_volume(sift3d_ctx *c, const float *vol, int64_t nx, in
     HIPCHK(c, hipSetDevice(c->device));
     rc = load_volume(c, vol, true, nx, ny, nz);
     if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rc = scan_volume(c, nx, ny, nz); /* waits for the copy */
+    if (rc) return rc;
     c->nx = nx; c->ny = ny; c->nz = nz;
     c->has_volume = true;
     return SIFT3D_OK;
@@ -113,6 +128,8 @@ extern "C" int sift3d_set_volume_dev(sift3d_ctx *c, const float *d_vol, int64_t 
     rc = fence_in(c); /* the caller's volume may still be in the making on the default stream */
     if (rc) return rc;
     rc = load_volume(c, d_vol, false, nx, ny, nz);
+    if (rc) return rc;
+    rc = scan_volume(c, nx, ny, nz);
     if (rc) return rc;
     c->nx = nx; c->ny = ny; c->nz = nz;
     c->has_volume = true;
@@ -138,7 +155,8 @@ extern "C" int sift3d_set_volume_resized(sift3d_ctx *c, const float *vol, int64_
     else HIPCHK(c, sift3d_launch_halve_size(c->stream, c->T[0], nx, ny, nz, c->T[1]));
     rc = load_volume(c, c->T[1], false, ox, oy, oz);
     if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream)); /* the caller may free vol */
+    rc = scan_volume(c, ox, oy, oz); /* of the resized volume; waits for the stream: the caller may free vol */
+    if (rc) return rc;
     c->nx = ox; c->ny = oy; c->nz = oz;
     c->has_volume = true;
     return SIFT3D_OK;
@@ -218,7 +236,8 @@ extern "C" int sift3d_set_volume_end(sift3d_ctx *c)
         if (rc) return rc;
         nx = ox; ny = oy; nz = oz;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream)); /* the caller may free its planes */
+    const int rs = scan_volume(c, nx, ny, nz); /* waits for the stream: the caller may free its planes */
+    if (rs) return rs;
     c->nx = nx; c->ny = ny; c->nz = nz;
     c->has_volume = true;
     return SIFT3D_OK;

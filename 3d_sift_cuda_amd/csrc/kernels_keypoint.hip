@@ -1291,10 +1291,26 @@ __global__ __launch_bounds__(DESC_NT) void descriptor_kernel(sift3d_kp_params p,
     if (!w0) return;
     /* NormalizeDataRankedPCs, MultiScale.cpp:207-233, order of :3148-3176 */
     int rank = 0;
+    const unsigned long long nans = __ballot(myval != myval);
+    if (nans == 0) {
 #pragma unroll
-    for (int j = 0; j < 64; j++) {
-        float vj = lane_value(myval, j);
-        rank += (vj < myval || (vj == myval && j < lane)) ? 1 : 0;
+        for (int j = 0; j < 64; j++) {
+            float vj = lane_value(myval, j);
+            rank += (vj < myval || (vj == myval && j < lane)) ? 1 : 0;
+        }
+    } else {
+        /* NaN values (a patch that reached a NaN region of the volume): the reference's stable insertion sort moves a value
+         * left only past values that compare greater, and nothing compares greater than or less than a NaN -- so every NaN
+         * keeps its own index and the values between two NaNs are sorted among themselves (o3_rank) */
+        const unsigned long long below = nans & ((1ull << lane) - 1ull), above = lane == 63 ? 0ull : nans & ~((2ull << lane) - 1ull);
+        const int lo = below ? 64 - __clzll((long long)below) : 0; /* first index of this lane's run of non-NaN values */
+        const int hi = above ? __ffsll((long long)above) - 1 : 64;  /* one past its last */
+        rank = lo;
+        for (int j = 0; j < 64; j++) {
+            float vj = lane_value(myval, j);
+            rank += (j >= lo && j < hi && (vj < myval || (vj == myval && j < lane))) ? 1 : 0;
+        }
+        if (myval != myval) rank = lane;
     }
     /* where the record goes: slot r of this launch's records -- or, when several contexts write ONE merged list (the slab
      * driver), shifted by a per-group offset: a rank's records are sorted by group already, so the merged position of its

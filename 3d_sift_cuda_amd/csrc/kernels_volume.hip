@@ -370,8 +370,9 @@ __global__ void halve_size_kernel(const float *__restrict__ in, long long X, lon
 /* + peak/valleyFunction4D (R/src_common/MultiScale.cpp:2260-2524) followed  */
 /* by validateDifferencePeak/Valley3D (:1135-1318).                          */
 /*                                                                          */
-/* "c > every one of 26 neighbours" == "c > max of the 26", and max/min are  */
-/* exact, so the own-level test is done separably: a workgroup owns 64 x by  */
+/* "c > every one of 26 neighbours" == "c > max of the 26" when none is NaN  */
+/* (volumes that may hold one take extrema_strict_kernel: sift3d_volume_needs_strict), */
+/* and max/min are exact, so the own-level test is done separably: a workgroup owns 64 x by  */
 /* EX_ROWS y and marches along z; each wavefront owns one row (two extra     */
 /* wavefronts carry the halo rows), gets its x-neighbours with wave-wide DPP */
 /* shifts, publishes the row's 3-max / 3-min through LDS, and keeps the 3x3  */
@@ -566,7 +567,8 @@ __global__ __launch_bounds__(256) void extrema_kernel(const float *__restrict__ 
  * A step on plane p computes the 3x3 max m / min n and the 8-neighbour max / min of p, FINISHES plane p-1 (cmx > m: a
  * maximum; cmn < n: a minimum -- a comparison with -inf / +inf is false, so non-candidates need no flag), and restarts the
  * candidates from p.  The decisions are the max / min / compare operations of extrema_kernel on the same values --
- * "c > every one of 26" == "c > max of 8" and "c > max of 9 below" and "c > max of 9 above" -- so the lists are the same.
+ * "c > every one of 26" == "c > max of 8" and "c > max of 9 below" and "c > max of 9 above" (NaN-free levels; see
+ * extrema_strict_kernel) -- so the lists are the same.
  * The round-2 form kept the five reduced arrays of three planes (195 registers for two rows); this one keeps four arrays of
  * one plane, which pays for four rows per wavefront (six rows loaded for four instead of four for two: 1.5 instead of 2
  * requests per voxel to L1/L2), two planes of prefetch in registers, and buffer loads (row offset in a VGPR, plane offset in
@@ -1318,6 +1320,71 @@ hipError_t sift3d_launch_tiny_octave(hipStream_t s, const float *L0, const sift3
     return hipGetLastError();
 }
 
+/* First phase for the volumes that sift3d_volume_needs_strict flags: the 26 own-level comparisons one by one, as the
+ * reference makes them (a NaN neighbour fails both "v < c" and "v > c"; MultiScale.cpp:2408-2524), appended to the same
+ * segmented own-level list as the march -- one thread per voxel, 64 x 4 voxels of one plane per workgroup, blockIdx.y =
+ * the plane -- so that the second phase, which already compares element by element, is the same launch.  Never taken for
+ * finite volumes of ordinary magnitude: those keep the march and its instruction stream. */
+__global__ __launch_bounds__(256) void extrema_strict_kernel(const float *__restrict__ dcur, int X, int Xl, int Y, int z_first, int xblocks,
+                                                             sift3d_survivor *__restrict__ surv, unsigned long long *surv_count,
+                                                             long long surv_cap)
+{
+    const int x = (int)(blockIdx.x % (unsigned)xblocks) * 64 + (threadIdx.x & 63);
+    const int y = (int)(blockIdx.x / (unsigned)xblocks) * 4 + (threadIdx.x >> 6);
+    const int z = z_first + (int)blockIdx.y;
+    if (x < 1 || x >= Xl - 1 || y < 1 || y >= Y - 1) return;
+    const long long XY = (long long)X * Y;
+    const long long idx = (long long)z * XY + (long long)y * X + x;
+    const float c = dcur[idx];
+    bool mx = true, mn = true;
+#pragma unroll
+    for (int dz = -1; dz <= 1; dz++)
+#pragma unroll
+        for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                if (dz == 0 && dy == 0 && dx == 0) continue;
+                const float v = dcur[idx + dz * XY + dy * X + dx];
+                mx = mx && (v < c);
+                mn = mn && (v > c);
+            }
+    if (!(mx || mn)) return;
+    const int seg = ex_segment_of_z_block();
+    const unsigned long long slot = atomicAdd(surv_count + seg * EX_SEG_STRIDE, 1ull);
+    if ((long long)slot < surv_cap) {
+        sift3d_survivor sv;
+        sv.idx = idx;
+        sv.value = c;
+        sv.is_max = mx ? 1 : 0;
+        surv[(long long)seg * surv_cap + (long long)slot] = sv;
+    }
+}
+
+/* !(|v| <= FLT_MAX / 4) is true for NaN, for +-inf and for magnitudes the pyramid's arithmetic could overflow */
+__host__ __device__ __forceinline__ bool strict_value(float v) { return !(fabsf(v) <= 3.4028234663852886e38f / 4.0f); }
+
+__global__ __launch_bounds__(256) void scan_strict_kernel(const float *__restrict__ v, long long n, unsigned *flag)
+{
+    bool bad = false;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) bad = bad || strict_value(v[i]);
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+
+hipError_t sift3d_launch_scan_strict(hipStream_t s, const float *v, int64_t n, unsigned *flag)
+{
+    if (n <= 0) return hipSuccess;
+    const long long blocks = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
+    hipLaunchKernelGGL(scan_strict_kernel, dim3((unsigned)blocks), dim3(256), 0, s, v, (long long)n, flag);
+    return hipGetLastError();
+}
+
+bool sift3d_volume_needs_strict(const float *v, int64_t n)
+{
+    for (int64_t i = 0; i < n; i++)
+        if (strict_value(v[i])) return true;
+    return false;
+}
+
 hipError_t sift3d_launch_zero_pad(hipStream_t s, float *a, float *b, int64_t X, int64_t Xl, int64_t rows)
 {
     const long long n = rows * (X - Xl);
@@ -1380,7 +1447,7 @@ hipError_t sift3d_launch_extrema(hipStream_t s, const float *dprev, const float 
                                  int64_t Xl, int64_t Y, int64_t Z, int z_lo, int z_hi, int lvl_id, unsigned long long *keys,
                                  sift3d_cval *vals, unsigned long long *count, int64_t cap, sift3d_survivor *surv,
                                  unsigned long long *surv_count, unsigned long long *surv_overflow, int64_t surv_cap,
-                                 bool zero_counters, const sift3d_extrema_lazy *lazy)
+                                 bool zero_counters, const sift3d_extrema_lazy *lazy, bool strict)
 {
     if (Xl < 3 || Y < 3 || Z < 3) return hipSuccess;
     const bool pair = lazy && lazy->prev_b, defer = lazy && lazy->next_g;
@@ -1406,7 +1473,7 @@ hipError_t sift3d_launch_extrema(hipStream_t s, const float *dprev, const float 
         /* the longest chunk that still gives the chip 2 048 wavefronts (two per SIMD: what the kernel's registers allow) --
          * 512^3: 64 planes, 256^3: 8 --, else the longest that gives 512 (128^3: 8); below that the plane-per-block form */
         int zchunk = 1;
-        for (int need = 2048; need >= 512 && zchunk == 1; need /= 4)
+        for (int need = 2048; need >= 512 && zchunk == 1 && !strict; need /= 4) /* the strict form takes one plane per block */
             for (int zc = 64; zc >= 8; zc /= 2)
                 if (waves_m * ((z1 - z0 + zc - 1) / zc) >= need && (zc + 2) * plane_bytes < (1ll << 32)) {
                     zchunk = zc;
@@ -1415,7 +1482,11 @@ hipError_t sift3d_launch_extrema(hipStream_t s, const float *dprev, const float 
         const unsigned nz = (unsigned)((z1 - z0 + zchunk - 1) / zchunk);
         const int nseg = ex_segments_in_use(nz);
         const long long segcap = surv_cap / nseg; /* entries per segment of the own-level list */
-        if (zchunk >= 2) {
+        if (strict) {
+            const int xblocks = (int)((X + 63) / 64);
+            dim3 grid((unsigned)(xblocks * ((Y + 3) / 4)), nz);
+            hipLaunchKernelGGL(extrema_strict_kernel, grid, dim3(256), 0, s, dcur, (int)X, (int)Xl, (int)Y, z0, xblocks, surv, surv_count, segcap);
+        } else if (zchunk >= 2) {
             dim3 grid((unsigned)(xtiles_m * ygroups), nz);
             hipLaunchKernelGGL(extrema_march_kernel, grid, dim3(256), 0, s, dcur, (int)X, (int)Xl, (int)Y, (int)Z, z0, z1, zchunk, xtiles_m,
                                ygroups, surv, surv_count, segcap);

@@ -132,6 +132,9 @@ struct sift3d_ctx {
     int64_t nx, ny, nz;
     int64_t pad_nx, pad_ny, pad_nz; /* geometry the pad columns of the level buffers were last cleared for */
     bool has_volume;
+    bool strict_extrema; /* the first extrema pass compares element by element (extrema_strict_kernel) instead of against a
+                          * max / min reduction: set where a volume is set, when it holds a value the reductions would get wrong
+                          * (sift3d_volume_needs_strict) */
     struct {                /* sift3d_set_volume_begin / _planes / _end: a volume arriving in runs of planes */
         bool open;
         int64_t nx, ny, nz, got; /* dims of what arrives; planes received so far */

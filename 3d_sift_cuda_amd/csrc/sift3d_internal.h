@@ -117,7 +117,13 @@ hipError_t sift3d_launch_extrema(hipStream_t s, const float *dprev, const float 
                                  sift3d_cval *vals, unsigned long long *count, int64_t cap, sift3d_survivor *surv,
                                  unsigned long long *surv_count /* SIFT3D_SURV_COUNTERS words */,
                                  unsigned long long *surv_overflow, int64_t surv_cap, bool zero_counters,
-                                 const sift3d_extrema_lazy *lazy = nullptr);
+                                 const sift3d_extrema_lazy *lazy = nullptr, bool strict = false);
+/* Volumes the max / min form of the first extrema pass would get wrong: a NaN anywhere (v_max_f32 / v_min_f32 return the
+ * other operand, so "c > max of 26" would hold beside a NaN neighbour where the reference's element-wise "every neighbour < c"
+ * fails), an infinity, or a magnitude above FLT_MAX / 4 (the blur, DoG and subsample can overflow it to an infinity, and
+ * inf - inf is NaN).  sift3d_launch_scan_strict ORs 1 into *flag when any of the n floats at v is such a value. */
+hipError_t sift3d_launch_scan_strict(hipStream_t s, const float *v, int64_t n, unsigned *flag);
+bool sift3d_volume_needs_strict(const float *v, int64_t n); /* the same test on host memory */
 /* the three detection levels of an octave of at most SIFT3D_TINY_VOX voxels (d[0..4]: its five stored DoG levels) in one launch */
 hipError_t sift3d_launch_extrema_octave_small(hipStream_t s, const float *const d[5], int64_t X, int64_t Xl, int64_t Y, int64_t Z,
                                               int lvl_id0, unsigned long long *keys, sift3d_cval *vals, unsigned long long *count,

@@ -188,6 +188,7 @@ struct sift3d_zslab {
     int poison_halo = 0;                    /* SIFT3D_ZSLAB_POISON_HALO (tests): the halo slices of L1..L3 that are not fetched hold NaN */
     zs_transport *tr = nullptr;             /* created by the first extraction after the choice (zslab_transport.hip) */
     bool has_volume = false;                /* sift3d_zslab_set_volume has put every rank's input slices on its device */
+    bool strict_extrema = false;            /* ... and that volume sends the first extrema pass to its element-wise form */
     /* The merged records (round 5): ONE pinned host buffer every rank's device can store into (hipHostMallocPortable).  A rank's
      * records are sorted by group already, so their merged positions are the rank's own positions shifted group by group: once
      * every rank's records per group are known (a 193-word read-back beside the record total each rank waits for anyway) the
@@ -444,6 +445,11 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
         return false;
     };
     const auto wall0 = std::chrono::steady_clock::now();
+    /* once per extraction, for every rank alike: a rank whose own slices are finite still reads its neighbours' halo planes
+     * and the gathered octaves of all of them (sift3d_volume_needs_strict) */
+    const bool strict = vol ? sift3d_volume_needs_strict(vol, nx * ny * nz) : h->strict_extrema;
+    for (int i = 0; i < T; i++)
+        if (R[(size_t)i].c) R[(size_t)i].c->strict_extrema = strict;
 
     /* sigma schedule, MultiScale.cpp:288-294,369,526-527 (float arithmetic as there) */
     float sigma_init = 0.5f;
@@ -1051,6 +1057,7 @@ extern "C" int sift3d_zslab_set_volume(sift3d_zslab *h, const float *vol, char *
             if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", errs[(size_t)r].b);
             return rcs[(size_t)r];
         }
+    h->strict_extrema = sift3d_volume_needs_strict(vol, XY * plan.nz);
     h->has_volume = true;
     return SIFT3D_OK;
 }

@@ -205,6 +205,10 @@ int sift3d_halve_size(sift3d_ctx *ctx, const float *in, int64_t nx, int64_t ny, 
  * (R/src_common/MultiScale.cpp:236-570, R/featExtract/featExtract.cpp:409,474-505).
  * Everything stays on the device between the upload of the volume and the
  * download of the records. */
+/* Input semantics: any float32 values.  NaN compares false as in the reference (a NaN neighbour refutes an extremum), and
+ * +-inf and magnitudes near FLT_MAX follow IEEE arithmetic through the pyramid.  Every sift3d_set_volume* scans the volume once:
+ * one that holds a NaN, an infinity or |v| > FLT_MAX / 4 takes the element-wise first extrema pass; the
+ * records of volumes with infinities or overflowing values are not defined by the reference past the candidates. */
 int sift3d_set_volume(sift3d_ctx *ctx, const float *vol, int64_t nx, int64_t ny, int64_t nz);
 int sift3d_set_volume_dev(sift3d_ctx *ctx, const float *d_vol, int64_t nx, int64_t ny, int64_t nz);
 /* The -2+ / -2- options without a round trip through the host (R/featExtract/featExtract.cpp:409-421 calls
