@@ -758,15 +758,9 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
     std::vector<octave_dims> oct = octave_list(c->nx, c->ny, c->nz);
     if (c->max_octaves > 0 && oct.size() > (size_t)c->max_octaves) oct.resize((size_t)c->max_octaves);
 
-    /* sigma schedule, MultiScale.cpp:288-294,369,526-527 (float arithmetic as there) */
-    float sigma_init = 0.5f;
-    if (init_scale > 0) sigma_init /= init_scale;
-    float sigma = 1.6f;
-    const float factor = (float)pow(2.0, 1.0 / (double)3);
-    const float extra0 = sqrtf(sigma * sigma - sigma_init * sigma_init);
-
+    const octave_sigmas s = sigma_schedule(init_scale);
     const int64_t xp0 = pitch_of(c->nx);
-    int rc = blur_dev(c, c->vol, c->L[0], nullptr, xp0, c->ny, c->nz, extra0, 0.01f);
+    int rc = blur_dev(c, c->vol, c->L[0], nullptr, xp0, c->ny, c->nz, s.extra0, 0.01f);
     if (rc) return rc;
     if (xp0 != c->nx) HIPCHK(c, sift3d_launch_zero_pad(c->stream, c->L[0], nullptr, xp0, c->nx, c->ny * c->nz));
     /* the counters of the extrema passes are cleared on the first extrema stream, idle until octave 1's levels are done,
@@ -793,50 +787,40 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
     int64_t tiny_base = -1; /* float offset of the first octave of at most SIFT3D_TINY_VOX voxels */
     for (const octave_dims &d : oct)
         if (tiny_base < 0 && d.X * d.Y * d.Z <= SIFT3D_TINY_VOX) tiny_base = d.off;
-    std::vector<sift3d_level> levels(oct.size() * 3);
-    float fscale = 1;
-    float sig[7];
-    struct ex_plan {
-        bool tiny_done, lazy, lazy_next;
-        float *d4tiny;
-        int next_ntaps;
-        float next_taps[2 * SIFT3D_FAST_MAX_R + 1];
-        float sig[7];
-        float fscale;
+    /* octave d's part of the level buffers (D[4] NULL while that buffer is not allocated) */
+    auto octave_buffers = [&](const octave_dims &d, const float *L[5], const float *D[5]) {
+        for (int j = 0; j < 5; j++) {
+            L[j] = c->L[j] + d.off;
+            D[j] = c->D[j] ? c->D[j] + d.off : nullptr;
+        }
     };
-    std::vector<ex_plan> plans(oct.size());
-    bool used_second = false;
-    /* split tail: the level table does not depend on anything the loop below finds out, so it goes to the device now, on the
-     * stream the first part's keypoint kernel will run on, instead of between that part's count and its sort */
-    std::vector<sift3d_level> levels_sent;
-    bool levels_early_split = false;
-    if (split_tail && levels.size() <= 96) {
-        float sg[7] = {0, 0, 0, 0, 0, 0, 0}, s_ = 1.6f, fs = 1;
-        sg[0] = s_;
-        for (int j = 1; j < 6; j++) {
-            s_ *= factor;
-            sg[j] = s_;
-        }
+    /* the level table holds nothing the loop below finds out: it is made before it */
+    std::vector<sift3d_level> levels(oct.size() * 3);
+    {
+        float fscale = 1;
         for (size_t o = 0; o < oct.size(); o++) {
-            for (int l = 0; l < 3; l++) {
-                sift3d_level &lv = levels[o * 3 + (size_t)l];
-                memset(&lv, 0, sizeof lv);
-                lv.img = c->L[l + 1] + oct[o].off;
-                lv.dogc = c->D[l + 1] + oct[o].off;
-                lv.X = (int)oct[o].X; lv.Y = (int)oct[o].Y; lv.Z = (int)oct[o].Z;
-                lv.XP = (int)oct[o].XP;
-                lv.sigma_h = sg[l]; lv.sigma_c = sg[l + 1]; lv.sigma_l = sg[l + 2];
-                lv.octave_factor = fs;
-                lv.Zl = (int)oct[o].Z;
-                lv.z_off = 0;
-                lv.pad = 0;
-            }
-            fs *= 2.0f;
+            const octave_dims &d = oct[o];
+            const float *L[5], *D[5];
+            octave_buffers(d, L, D);
+            octave_level_rows(&levels[o * 3], L, D, d.X, d.XP, d.Y, d.Z, d.Z, 0, s, fscale);
+            fscale *= 2.0f;
         }
-        levels_sent = levels;
-        HIPCHK(c, hipMemcpyAsync(c->d_levels, levels_sent.data(), sizeof(sift3d_level) * levels_sent.size(), hipMemcpyHostToDevice, c->kp_stream));
-        levels_early_split = true;
     }
+    /* split tail: the table goes to the device now, on the stream the first part's keypoint kernel will run on, instead of
+     * between that part's count and its sort */
+    if (split_tail && levels.size() <= 96)
+        HIPCHK(c, hipMemcpyAsync(c->d_levels, levels.data(), sizeof(sift3d_level) * levels.size(), hipMemcpyHostToDevice, c->kp_stream));
+    /* the filter that makes L_5 from L_4: the lazy form of D_4 applies it around the candidates of D_3 only */
+    float next_taps[SIFT3D_MAX_TAPS];
+    const int next_ntaps = sift3d_gauss_taps(s.extras[4], 0.01f, next_taps);
+    /* what differs from octave to octave in how its levels were made */
+    struct octave_run {
+        bool tiny_done; /* one workgroup built all its levels, every DoG level stored */
+        bool lazy;      /* D_0 and D_4 not stored (see the loop) */
+        float *d4tiny;  /* where its D_4 went then (or NULL) */
+    };
+    std::vector<octave_run> runs(oct.size());
+    bool used_second = false;
     /* One chain of levels on the main stream.  (Round 3 tried two: the octaves after the first -- some sixty small launches
      * bound by launch latency, 0.5 ms of kernel time -- on a stream of their own from the moment the second octave's level 0
      * exists, beside the first octave's last level and its extrema passes.  It cannot overlap: the fused blur runs one
@@ -847,7 +831,7 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
      * queued on the main stream so far */
     auto enqueue_extrema = [&](size_t o, int which) -> int {
         const octave_dims &d = oct[o];
-        const ex_plan &pl = plans[o];
+        const octave_run &ru = runs[o];
         /* timing mode 3 (measurement only): the extrema stay on the main stream, so that every launch's event pair times
          * that launch alone instead of the launch plus whatever shares the chip with it */
         hipStream_t exs = c->timing == 3 ? c->stream : (which == 0 ? c->ex_stream : c->ex_stream2);
@@ -861,43 +845,23 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
         c->cand_stream = exs;
         c->cand_group = o >= 2 ? 1 : 0; /* only looked at while the list is split */
         c->surv_sel = (exs != c->stream && which == 1) ? 1 : 0;
+        const float *L[5], *D[5];
+        octave_buffers(d, L, D);
+        if (ru.lazy) D[0] = D[4] = nullptr;
+        if (ru.tiny_done) D[4] = ru.d4tiny;
+        level_job jobs[3];
+        octave_jobs(jobs, L, D, d.XP, d.X, d.Y, d.Z, 0, (int)d.Z, (int)o * 3, next_taps, next_ntaps);
         int rc_ = SIFT3D_OK;
         /* an octave one workgroup built whole (at most 4 096 voxels, every DoG level stored): its three detection levels in one
          * launch; the per-level jobs are recorded all the same, for a replay after a list overflow */
-        const bool small_octave = pl.tiny_done && pl.d4tiny;
-        if (small_octave) {
-            const float *dl[5] = {c->D[0] + d.off, c->D[1] + d.off, c->D[2] + d.off, c->D[3] + d.off, pl.d4tiny};
+        if (ru.tiny_done) {
             stage_scope sc(c, SIFT3D_STAGE_EXTREMA, 12.0 * (double)d.XP * d.Y * d.Z, 0, d.XP * d.Y * d.Z, exs);
             const cand_target tg = cand_target_of(c);
-            HIPCHK(c, sift3d_launch_extrema_octave_small(exs, dl, d.XP, d.X, d.Y, d.Z, (int)o * 3, tg.keys, tg.vals, tg.count, tg.cap));
+            HIPCHK(c, sift3d_launch_extrema_octave_small(exs, D, d.XP, d.X, d.Y, d.Z, (int)o * 3, tg.keys, tg.vals, tg.count, tg.cap));
             c->count_queued = false;
-        }
-        for (int l = 0; l < 3 && !rc_; l++) {
-            const int id = (int)o * 3 + l;
-            const float *dnext = l < 2 ? c->D[l + 2] + d.off : (pl.tiny_done ? pl.d4tiny : (pl.lazy_next ? nullptr : c->D[4] + d.off));
-            level_job job = {c->D[l] + d.off, c->D[l + 1] + d.off, dnext, d.XP, d.Y, d.Z, 0, (int)d.Z, id, d.X};
-            if (pl.lazy && l == 0) { /* the level below D_1 is L_0 - L_1 */
-                job.dp = c->L[0] + d.off;
-                job.prev_b = c->L[1] + d.off;
-            }
-            if (pl.lazy_next && l == 2) { /* the level above D_3 is L_4 - blur(L_4) */
-                job.dn = nullptr;
-                job.next_g = c->L[4] + d.off;
-                job.next_ntaps = pl.next_ntaps;
-                for (int q = 0; q < pl.next_ntaps; q++) job.next_taps[q] = pl.next_taps[q];
-            }
-            if (small_octave) c->jobs.push_back(job);
-            else rc_ = cand_append(c, job, true);
-            sift3d_level &lv = levels[(size_t)id];
-            lv.img = c->L[l + 1] + d.off;
-            lv.dogc = c->D[l + 1] + d.off;
-            lv.X = (int)d.X; lv.Y = (int)d.Y; lv.Z = (int)d.Z;
-            lv.XP = (int)d.XP;
-            lv.sigma_h = pl.sig[l]; lv.sigma_c = pl.sig[l + 1]; lv.sigma_l = pl.sig[l + 2];
-            lv.octave_factor = pl.fscale;
-            lv.Zl = (int)d.Z;
-            lv.z_off = 0;
-            lv.pad = 0;
+            for (const level_job &jb : jobs) c->jobs.push_back(jb);
+        } else {
+            for (int l = 0; l < 3 && !rc_; l++) rc_ = cand_append(c, jobs[l], true);
         }
         c->cand_stream = nullptr;
         c->cand_group = 0;
@@ -908,32 +872,29 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
         const octave_dims &d = oct[o];
         const double N = (double)d.X * d.Y * d.Z;
         hipStream_t ws = c->stream;
-        sigma = 1.6f;
-        sig[0] = sigma;
+        octave_run &ru = runs[o];
         /* an octave of at most 4096 voxels: all five levels in one single-workgroup launch instead of fifteen */
-        bool tiny_done = false;
+        ru.tiny_done = false;
         /* the last DoG level of such an octave lives in a small buffer of its own, at the octave's offset from the first of them */
-        float *const d4tiny = (tiny_base >= 0 && d.off >= tiny_base && d.off - tiny_base + d.XP * d.Y * d.Z <= SIFT3D_D4TINY_FLOATS)
-                                  ? c->D4tiny + (d.off - tiny_base) : nullptr;
-        if (d.X * d.Y * d.Z <= SIFT3D_TINY_VOX && d4tiny && c->tune[SIFT3D_TUNE_TINY_OCTAVE]) {
+        ru.d4tiny = (tiny_base >= 0 && d.off >= tiny_base && d.off - tiny_base + d.XP * d.Y * d.Z <= SIFT3D_D4TINY_FLOATS)
+                        ? c->D4tiny + (d.off - tiny_base) : nullptr;
+        if (d.X * d.Y * d.Z <= SIFT3D_TINY_VOX && ru.d4tiny && c->tune[SIFT3D_TUNE_TINY_OCTAVE]) {
             sift3d_octave_taps ot;
             sift3d_octave_out oo;
-            float sg = sigma;
             bool ok = true;
             for (int j = 1; j < 6 && ok; j++) {
                 float taps[SIFT3D_MAX_TAPS];
-                const int n = sift3d_gauss_taps(sg * sqrtf(factor * factor - 1.0f), 0.01f, taps);
+                const int n = sift3d_gauss_taps(s.extras[j - 1], 0.01f, taps);
                 ok = n >= 3 && n <= 2 * SIFT3D_FAST_MAX_R + 1;
                 for (int q = 0; ok && q < n; q++) ot.f[j - 1][q] = taps[q];
                 ot.n[j - 1] = n;
                 oo.L[j - 1] = j < 5 ? c->L[j] + d.off : nullptr;
-                oo.D[j - 1] = j < 5 ? c->D[j - 1] + d.off : d4tiny;
-                sg *= factor;
+                oo.D[j - 1] = j < 5 ? c->D[j - 1] + d.off : ru.d4tiny;
             }
             if (ok) {
                 stage_scope sc(c, SIFT3D_STAGE_OCTAVE_TINY, 40.0 * N, 0, (int64_t)N, ws);
                 hipError_t e = sift3d_launch_tiny_octave(ws, c->L[0] + d.off, oo, d.X, d.XP, d.Y, d.Z, ot);
-                if (e == hipSuccess) tiny_done = true;
+                if (e == hipSuccess) ru.tiny_done = true;
                 else if (e != hipErrorNotSupported) HIPCHK(c, e);
                 else sc.cancel();
             }
@@ -945,73 +906,40 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
          * L_5.  Here D_0 is taken as L_0 - L_1 at those positions and L_5 is filtered only in the 27-voxel neighbourhood
          * of what passed every other test (extrema_validate_lazy_kernel: same operations, same order, same bits).  Per
          * octave that is one 17-tap blur of the whole volume and two DoG stores less.  SIFT3D_TUNE_LAZY_LEVELS = 0 (A/B,
-         * tests): every level stored, as before. */
-        float next_taps[SIFT3D_MAX_TAPS];
-        int next_ntaps = 0;
-        bool lazy = !tiny_done && d.XP >= 8 && d.Y >= 3 && d.Z >= 3 && d.XP * d.Y < (1ll << 29) && c->tune[SIFT3D_TUNE_LAZY_LEVELS];
-        if (lazy) {
-            float sg = 1.6f; /* sigma entering j = 5, accumulated as the loop below does */
-            for (int j = 1; j < 5; j++) sg *= factor;
-            next_ntaps = sift3d_gauss_taps(sg * sqrtf(factor * factor - 1.0f), 0.01f, next_taps);
-            if (next_ntaps != 2 * SIFT3D_FAST_MAX_R + 1) lazy = false; /* the one filter length the third phase is built for */
-        }
-        const bool lazy_next = lazy;
+         * tests): every level stored, as before.  17 taps is the one filter length the third phase is built for. */
+        ru.lazy = !ru.tiny_done && lazy_shape_ok(d.XP, d.Y, d.Z) && c->tune[SIFT3D_TUNE_LAZY_LEVELS] && next_ntaps == 2 * SIFT3D_FAST_MAX_R + 1;
+        const bool more = o + 1 < oct.size();
         for (int j = 1; j < 6; j++) {
-            if (tiny_done) {
-                if (j == 3 && o + 1 < oct.size()) {
-                    stage_scope sc(c, SIFT3D_STAGE_SUBSAMPLE, 4.5 * N, 0, (int64_t)N, ws);
-                    HIPCHK(c, sift3d_launch_subsample(ws, c->L[3] + d.off, d.XP, d.X, d.Y, d.Z, c->L[0] + oct[o + 1].off, oct[o + 1].XP));
-                    /* the subsample writes the logical columns only: a pitched coarser octave (100 -> 50 -> pitch 52) needs its pad
-                     * columns zeroed here -- the blur reads them as the zero border, and the buffer may hold an earlier volume */
-                    if (oct[o + 1].XP != oct[o + 1].X)
-                        HIPCHK(c, sift3d_launch_zero_pad(ws, c->L[0] + oct[o + 1].off, nullptr, oct[o + 1].XP, oct[o + 1].X, oct[o + 1].Y * oct[o + 1].Z));
-                }
-                sigma *= factor;
-                sig[j] = sigma;
-                continue;
-            }
-            const float ex = sigma * sqrtf(factor * factor - 1.0f);
             bool sub_done = false;
             /* L_j = blur(L_{j-1}); D_{j-1} = L_{j-1} - L_j fused into the z pass */
             /* nothing reads L_5: only D_4 = L_4 - L_5 is needed, so the last level is not stored */
-            if (!(lazy_next && j == 5)) {
+            if (!ru.tiny_done && !(ru.lazy && j == 5)) {
                 if (j == 5) {
                     rc = ensure_level_buffer(c, &c->D[4]);
                     if (rc) return rc;
                 }
-                float *dst_dog = (lazy && j == 1) ? nullptr : c->D[j - 1] + d.off;
+                float *dst_dog = (ru.lazy && j == 1) ? nullptr : c->D[j - 1] + d.off;
                 /* level 3 is what the next octave starts from: the launch that makes it writes the half-size volume too where it can */
                 float *sub = nullptr;
-                if (j == 3 && o + 1 < oct.size() && d.XP % 8 == 0 && oct[o + 1].XP == d.XP / 2) sub = c->L[0] + oct[o + 1].off;
-                rc = blur_dev(c, c->L[j - 1] + d.off, j < 5 ? c->L[j] + d.off : nullptr, dst_dog, d.XP, d.Y, d.Z, ex, 0.01f, sub, &sub_done);
+                if (j == 3 && more && d.XP % 8 == 0 && oct[o + 1].XP == d.XP / 2) sub = c->L[0] + oct[o + 1].off;
+                rc = blur_dev(c, c->L[j - 1] + d.off, j < 5 ? c->L[j] + d.off : nullptr, dst_dog, d.XP, d.Y, d.Z, s.extras[j - 1], 0.01f, sub, &sub_done);
                 if (rc) return rc;
                 if (d.XP != d.X) /* the blur ran over the pitched width: its pad columns go back to zero */
                     HIPCHK(c, sift3d_launch_zero_pad(ws, j < 5 ? c->L[j] + d.off : nullptr, dst_dog, d.XP, d.X, d.Y * d.Z));
             }
-            if (j == 3 && o + 1 < oct.size()) {
+            if (j == 3 && more) {
+                const octave_dims &dn = oct[o + 1];
                 if (!sub_done) {
                     stage_scope sc(c, SIFT3D_STAGE_SUBSAMPLE, 4.5 * N, 0, (int64_t)N, ws);
-                    HIPCHK(c, sift3d_launch_subsample(ws, c->L[3] + d.off, d.XP, d.X, d.Y, d.Z, c->L[0] + oct[o + 1].off, oct[o + 1].XP));
+                    HIPCHK(c, sift3d_launch_subsample(ws, c->L[3] + d.off, d.XP, d.X, d.Y, d.Z, c->L[0] + dn.off, dn.XP));
                 }
                 /* the subsample writes the logical columns only: a pitched coarser octave (100 -> 50 -> pitch 52) needs its pad
                  * columns zeroed here -- the blur reads them as the zero border, and the buffer may hold an earlier volume */
-                if (oct[o + 1].XP != oct[o + 1].X)
-                    HIPCHK(c, sift3d_launch_zero_pad(ws, c->L[0] + oct[o + 1].off, nullptr, oct[o + 1].XP, oct[o + 1].X, oct[o + 1].Y * oct[o + 1].Z));
+                if (dn.XP != dn.X) HIPCHK(c, sift3d_launch_zero_pad(ws, c->L[0] + dn.off, nullptr, dn.XP, dn.X, dn.Y * dn.Z));
             }
-            sigma *= factor;
-            sig[j] = sigma;
         }
-        /* the extrema of this octave go to another stream: see enqueue_extrema above */
-        ex_plan &pl = plans[o];
-        pl.tiny_done = tiny_done;
-        pl.d4tiny = d4tiny;
-        pl.lazy = lazy;
-        pl.lazy_next = lazy_next;
-        pl.next_ntaps = next_ntaps;
-        for (int q = 0; q < next_ntaps && q < 2 * SIFT3D_FAST_MAX_R + 1; q++) pl.next_taps[q] = next_taps[q];
-        for (int q = 0; q < 7; q++) pl.sig[q] = sig[q];
-        pl.fscale = fscale;
-        /* Octave 0's extrema fill the chip for a millisecond, and so do octave 1's blurs for a third of one, while everything
+        /* the extrema of this octave go to another stream: see enqueue_extrema above.
+         * Octave 0's extrema fill the chip for a millisecond, and so do octave 1's blurs for a third of one, while everything
          * coarser is a chain of small launches that leaves it idle: octave 0's extrema therefore wait until octave 1's levels
          * are done and then run beside that chain; the extrema of the coarser octaves go to a stream of their own so that
          * they do not queue up behind octave 0's.  (Started right after octave 0's own levels they shared the chip with
@@ -1039,7 +967,6 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
                 HIPCHK(c, hipEventRecord(c->ev_split[2], c->kp_stream));
             }
         }
-        fscale *= 2.0f;
         c->last.n_octaves++;
     }
     HIPCHK(c, hipEventRecord(c->ev_oct[1], c->ex_stream)); /* the candidate counts are read on the main stream */
@@ -1050,10 +977,7 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
     }
     if (split_tail) {
         bool done = false;
-        /* the table the loop above filled in is the one that was uploaded before it (same expressions); checked, not assumed */
-        const bool table_ok = levels_early_split && levels.size() == levels_sent.size() &&
-                              memcmp(levels.data(), levels_sent.data(), sizeof(sift3d_level) * levels.size()) == 0;
-        rc = finish_split_tail(c, levels, table_ok, desc_mode, eig_thres, size_factor, n_out, &done);
+        rc = finish_split_tail(c, levels, levels.size() <= 96, desc_mode, eig_thres, size_factor, n_out, &done);
         if (rc) return rc;
         if (done) {
             *feats_out = c->h_recs; /* pinned, owned by the context */

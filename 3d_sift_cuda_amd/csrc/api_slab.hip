@@ -45,12 +45,6 @@ extern "C" int sift3d_extrema_append_dev(sift3d_ctx *c, const float *d_prev, con
     return fence_out(c); /* the caller may reuse the buffers once the pass has read them */
 }
 
-/* shapes the second and third extrema phase take neighbour levels in unstored form for */
-static bool lazy_shape_ok(int64_t nx, int64_t ny, int64_t nz_local)
-{
-    return nx % 4 == 0 && nx >= 8 && ny >= 3 && nz_local >= 3 && nx * ny < (1ll << 29);
-}
-
 extern "C" int sift3d_lazy_levels_supported(int64_t nx, int64_t ny, int64_t nz_local, float next_sigma)
 {
     float taps[SIFT3D_MAX_TAPS];

@@ -5,7 +5,9 @@
  */
 #ifndef SIFT3D_PIPELINE_H
 #define SIFT3D_PIPELINE_H
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "sift3d_internal.h"
@@ -45,6 +47,75 @@ struct octave_dims {
     int64_t X, Y, Z, off; /* dims and float offset of this octave inside every level buffer */
     int64_t XP;           /* row pitch: X rounded up to whole 16-byte vectors (the pad columns stay zero) */
 };
+
+/* The sigma schedule, the same for every octave: MultiScale.cpp:288-294,369,526-527, float arithmetic as there.  extra0 is
+ * the initial blur (input -> L_0), extras[j] the blur L_j -> L_{j+1}, sig[j] the sigma of L_j. */
+struct octave_sigmas {
+    float extra0;
+    float extras[5];
+    float sig[6];
+};
+static inline octave_sigmas sigma_schedule(float initial_image_scale)
+{
+    octave_sigmas s;
+    float sigma_init = 0.5f;
+    if (initial_image_scale > 0) sigma_init /= initial_image_scale;
+    const float factor = (float)pow(2.0, 1.0 / (double)3);
+    s.extra0 = sqrtf(1.6f * 1.6f - sigma_init * sigma_init);
+    float sg = 1.6f;
+    s.sig[0] = sg;
+    for (int j = 0; j < 5; j++) {
+        s.extras[j] = sg * sqrtf(factor * factor - 1.0f);
+        sg *= factor;
+        s.sig[j + 1] = sg;
+    }
+    return s;
+}
+
+/* shapes (row pitch, rows, slices held) the extrema passes can take D_0 and D_4 in unstored form for (level_job's prev_b /
+ * next_g); the pitch is always a multiple of 4 on one device, a slab's rows are its logical rows */
+static inline bool lazy_shape_ok(int64_t nx, int64_t ny, int64_t nz_local)
+{
+    return nx % 4 == 0 && nx >= 8 && ny >= 3 && nz_local >= 3 && nx * ny < (1ll << 29);
+}
+
+/* The three detection levels of an octave as extrema jobs.  L and D: the octave's Gaussian levels 0..4 and DoG levels 0..4
+ * as the buffers hold them (pitch XP, logical row length Xl, 0: XP; Zl slices, of which [z_lo, z_hi) are detected; first_id:
+ * the level id of the first).  A null D[0] is not stored: the level below D_1 is L_0 - L_1.  A null D[4] is not stored either:
+ * the level above D_3 is L_4 - blur(L_4, next_taps). */
+static inline void octave_jobs(level_job jobs[3], const float *const L[5], const float *const D[5], int64_t XP, int64_t Xl, int64_t Y,
+                               int64_t Zl, int z_lo, int z_hi, int first_id, const float *next_taps, int next_ntaps)
+{
+    for (int l = 0; l < 3; l++) jobs[l] = {D[l], D[l + 1], D[l + 2], XP, Y, Zl, z_lo, z_hi, first_id + l, Xl};
+    if (!D[0]) {
+        jobs[0].dp = L[0];
+        jobs[0].prev_b = L[1];
+    }
+    if (!D[4]) {
+        jobs[2].next_g = L[4];
+        jobs[2].next_ntaps = next_ntaps;
+        for (int q = 0; q < next_ntaps; q++) jobs[2].next_taps[q] = next_taps[q];
+    }
+}
+
+/* The level-table rows of those three levels (L_1..L_3, D_1..D_3): the octave is X x Y x Z with rows of pitch XP; the buffers
+ * hold Zl slices from global slice z_off on. */
+static inline void octave_level_rows(sift3d_level rows[3], const float *const L[5], const float *const D[5], int64_t X, int64_t XP, int64_t Y,
+                                     int64_t Z, int64_t Zl, int64_t z_off, const octave_sigmas &s, float octave_factor)
+{
+    for (int l = 0; l < 3; l++) {
+        sift3d_level &lv = rows[l];
+        memset(&lv, 0, sizeof lv);
+        lv.img = L[l + 1];
+        lv.dogc = D[l + 1];
+        lv.X = (int)X; lv.Y = (int)Y; lv.Z = (int)Z;
+        lv.XP = (int)XP;
+        lv.sigma_h = s.sig[l]; lv.sigma_c = s.sig[l + 1]; lv.sigma_l = s.sig[l + 2];
+        lv.octave_factor = octave_factor;
+        lv.Zl = (int)Zl;
+        lv.z_off = (int)z_off;
+    }
+}
 
 struct sift3d_ctx {
     int device;

@@ -96,6 +96,21 @@ struct zs_plan {
     }
 };
 
+/* a rank's part of an octave of zo slices whose own slices are [z0, z1) (lo / hi: it has a neighbour below / above): its
+ * level buffers hold [e0, e1), ZS_HALO slices beyond its own clipped to the volume; a blur computes [c0, c1), ZS_BLUR beyond */
+struct zs_extent {
+    int64_t e0, e1, c0, c1;
+};
+static zs_extent zs_extent_of(int64_t z0, int64_t z1, bool lo, bool hi, int64_t zo)
+{
+    zs_extent x;
+    x.e0 = lo ? std::max<int64_t>(0, z0 - ZS_HALO) : z0;
+    x.e1 = hi ? std::min<int64_t>(zo, z1 + ZS_HALO) : z1;
+    x.c0 = lo ? std::max(x.e0, z0 - ZS_BLUR) : x.e0;
+    x.c1 = hi ? std::min(x.e1, z1 + ZS_BLUR) : x.e1;
+    return x;
+}
+
 struct zs_rank {
     sift3d_ctx *c = nullptr;
     int dev = 0;
@@ -110,7 +125,7 @@ struct zs_rank {
     float *vol_dev = nullptr;          /* sift3d_zslab_set_volume: this rank's input slices [i0, i1), resident between extractions */
     int64_t arena_cap = 0, arena_used = 0, need = 0; /* floats */
     float *L[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, *D[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int64_t z0 = 0, z1 = 0, e0 = 0, e1 = 0; /* current octave: own slices [z0, z1), buffer extent [e0, e1) */
+    int64_t z0 = 0, z1 = 0, e0 = 0, e1 = 0, c0 = 0, c1 = 0; /* current octave: own slices [z0, z1), buffer extent [e0, e1), blurred [c0, c1) */
     bool lo = false, hi = false;
     std::vector<sift3d_level> levels;
     float *alloc(int64_t nfloats)
@@ -451,21 +466,9 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
     for (int i = 0; i < T; i++)
         if (R[(size_t)i].c) R[(size_t)i].c->strict_extrema = strict;
 
-    /* sigma schedule, MultiScale.cpp:288-294,369,526-527 (float arithmetic as there) */
-    float sigma_init = 0.5f;
-    if (initial_image_scale > 0) sigma_init /= initial_image_scale;
-    const float factor = (float)pow(2.0, 1.0 / (double)3);
-    const float extra0 = sqrtf(1.6f * 1.6f - sigma_init * sigma_init);
-    float extras[5], sig[6];
-    {
-        float sg = 1.6f;
-        sig[0] = sg;
-        for (int j = 0; j < 5; j++) {
-            extras[j] = sg * sqrtf(factor * factor - 1.0f);
-            sg *= factor;
-            sig[j + 1] = sg;
-        }
-    }
+    const octave_sigmas sigmas = sigma_schedule(initial_image_scale);
+    float taps5[SIFT3D_MAX_TAPS]; /* L_4 -> L_5: the lazy form of D_4 applies it around the candidates of D_3 only */
+    const int ntaps5 = sift3d_gauss_taps(sigmas.extras[4], 0.01f, taps5);
     std::vector<float *> next0((size_t)T, nullptr); /* level 0 of the next octave per rank */
     float fscale = 1.0f;
 
@@ -489,8 +492,8 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
         int64_t z0 = 0, z1 = nz;
         if (S > 1) plan.slab(r, 0, z0, z1);
         const bool lo = S > 1 && r > 0, hi = S > 1 && r < S - 1;
-        const int64_t e0 = lo ? std::max<int64_t>(0, z0 - ZS_HALO) : z0, e1 = hi ? std::min<int64_t>(nz, z1 + ZS_HALO) : z1;
-        const int64_t c0 = lo ? std::max(e0, z0 - ZS_BLUR) : e0, c1 = hi ? std::min(e1, z1 + ZS_BLUR) : e1;
+        const zs_extent x = zs_extent_of(z0, z1, lo, hi, nz);
+        const int64_t e0 = x.e0, e1 = x.e1, c0 = x.c0, c1 = x.c1;
         float *l0 = q.alloc((e1 - e0) * XY);
         if (!l0) ZR_FAIL(SIFT3D_ERR_MEMORY, "rank %d: out of device memory", r);
         /* Level 0 = the initial blur of the input, wanted on slab +- 8 (planes [c0, c1)) from input slab +- 16 (planes [i0, i1)).
@@ -498,12 +501,12 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
          * input's plane numbering the buffer starts i0 - e0 planes before its own first plane (i0 >= e0: the input reaches 16
          * slices beyond the slab, the buffer 32), and only the window is written.  Otherwise: the whole input slab into a
          * scratch volume, then a copy of the planes that are exact (rounds 2 - 4). */
-        if (i0 >= e0 && blur_window_supported(nx, ny, extra0, 0.01f)) {
-            ZR_RC(blur_window_dev(q.c, din, l0 + (i0 - e0) * XY, nullptr, nx, ny, i1 - i0, c0 - i0, c1 - i0, extra0, 0.01f));
+        if (i0 >= e0 && blur_window_supported(nx, ny, sigmas.extra0, 0.01f)) {
+            ZR_RC(blur_window_dev(q.c, din, l0 + (i0 - e0) * XY, nullptr, nx, ny, i1 - i0, c0 - i0, c1 - i0, sigmas.extra0, 0.01f));
         } else {
             float *tmp = q.alloc((i1 - i0) * XY);
             if (!tmp) ZR_FAIL(SIFT3D_ERR_MEMORY, "rank %d: out of device memory", r);
-            ZR_RC(blur_dev(q.c, din, tmp, nullptr, nx, ny, i1 - i0, extra0, 0.01f));
+            ZR_RC(blur_dev(q.c, din, tmp, nullptr, nx, ny, i1 - i0, sigmas.extra0, 0.01f));
             ZR_HIP(hipMemcpyAsync(l0 + (c0 - e0) * XY, tmp + (c0 - i0) * XY, sizeof(float) * (size_t)((c1 - c0) * XY), hipMemcpyDeviceToDevice, q.c->stream));
         }
         next0[r] = l0;
@@ -532,17 +535,15 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
          * four halos per octave instead of five; the third extrema phase reads L_4 nine slices beyond a candidate, so L_4's
          * halo is refreshed nine slices deep instead of eight.  Rows that are not whole 16-byte vectors keep every level
          * stored (the extrema kernels of such rows take stored levels only), as does sift3d_zslab_set_tuning(SIFT3D_TUNE_LAZY_LEVELS, 0). */
-        float taps5[SIFT3D_MAX_TAPS];
-        const int ntaps5 = sift3d_gauss_taps(extras[4], 0.01f, taps5);
-        const bool lazy = ntaps5 == 2 * SIFT3D_FAST_MAX_R + 1 && X % 4 == 0 && X >= 8 && XY < (1ll << 29) && Y >= 3 && zo >= 3 && h->lazy_levels;
+        const bool lazy = ntaps5 == 2 * SIFT3D_FAST_MAX_R + 1 && lazy_shape_ok(X, Y, zo) && h->lazy_levels;
         const int nlev = lazy ? 4 : 5;
         for (r = r0; r < r1; r++) { /* (bump allocations from the rank's arena: nothing to share out) */
             zs_rank &q = R[(size_t)r];
             if (sharded) plan.slab(r, o, q.z0, q.z1); else { q.z0 = 0; q.z1 = zo; }
             q.lo = sharded && r > 0;
             q.hi = sharded && r < S - 1;
-            q.e0 = q.lo ? std::max<int64_t>(0, q.z0 - ZS_HALO) : q.z0;
-            q.e1 = q.hi ? std::min<int64_t>(zo, q.z1 + ZS_HALO) : q.z1;
+            const zs_extent x = zs_extent_of(q.z0, q.z1, q.lo, q.hi, zo);
+            q.e0 = x.e0; q.e1 = x.e1; q.c0 = x.c0; q.c1 = x.c1;
             ZR_HIP(hipSetDevice(q.dev));
             q.L[0] = next0[(size_t)r];
             for (int j = 1; j < 6; j++) q.L[j] = j <= nlev ? q.alloc((q.e1 - q.e0) * XY) : nullptr;
@@ -561,25 +562,24 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
              * launch to complete: no halo byte is waited for with an idle device unless the link is slower than the
              * interior.  Without the windowed form (other row lengths): the level on slab +- 8 in one piece, then the
              * exchange, as in round 2. */
-            const bool banded = sharded && blur_window_supported(X, Y, extras[j - 1], 0.01f) && h->bands_first;
+            const bool banded = sharded && blur_window_supported(X, Y, sigmas.extras[j - 1], 0.01f) && h->bands_first;
             /* -- the level's launches: every rank by its own thread (bands, event, interior).  The transfers of the bands are
              *    queued in the step after this one -- in host time behind the interior launch, on the device behind the event only -- */
             step([&](int r) {
                 zs_rank &q = R[(size_t)r];
-                const int64_t c0 = q.lo ? std::max(q.e0, q.z0 - ZS_BLUR) : q.e0, c1 = q.hi ? std::min(q.e1, q.z1 + ZS_BLUR) : q.e1;
-                const int64_t a = c0 - q.e0, b = c1 - q.e0, nzl = q.e1 - q.e0;
+                const int64_t a = q.c0 - q.e0, b = q.c1 - q.e0, nzl = q.e1 - q.e0;
                 ZR_HIP(hipSetDevice(q.dev));
                 if (banded && (q.lo || q.hi)) {
-                    if (q.lo) ZR_RC(blur_window_dev(q.c, q.L[j - 1], q.L[j], q.D[j - 1], X, Y, nzl, q.z0 - q.e0, q.z0 - q.e0 + hb, extras[j - 1], 0.01f));
-                    if (q.hi) ZR_RC(blur_window_dev(q.c, q.L[j - 1], q.L[j], q.D[j - 1], X, Y, nzl, q.z1 - q.e0 - hb, q.z1 - q.e0, extras[j - 1], 0.01f));
+                    if (q.lo) ZR_RC(blur_window_dev(q.c, q.L[j - 1], q.L[j], q.D[j - 1], X, Y, nzl, q.z0 - q.e0, q.z0 - q.e0 + hb, sigmas.extras[j - 1], 0.01f));
+                    if (q.hi) ZR_RC(blur_window_dev(q.c, q.L[j - 1], q.L[j], q.D[j - 1], X, Y, nzl, q.z1 - q.e0 - hb, q.z1 - q.e0, sigmas.extras[j - 1], 0.01f));
                     ZR_HIP(hipEventRecord(q.ev_level, q.c->stream)); /* the bands are final: the neighbours may fetch them */
                     const int64_t w0 = q.lo ? q.z0 - q.e0 + hb : 0, w1 = q.hi ? q.z1 - q.e0 - hb : q.e1 - q.e0;
-                    ZR_RC(blur_window_dev(q.c, q.L[j - 1], q.L[j], q.D[j - 1], X, Y, nzl, w0, w1, extras[j - 1], 0.01f)); /* the interior, while the bands travel */
+                    ZR_RC(blur_window_dev(q.c, q.L[j - 1], q.L[j], q.D[j - 1], X, Y, nzl, w0, w1, sigmas.extras[j - 1], 0.01f)); /* the interior, while the bands travel */
                     if (j == 3) ZR_HIP(hipEventRecord(q.ev_l3, q.c->stream));
                 } else {
                     /* level j on slab +- 8 (clipped to the buffer: at a face of the whole volume the buffer ends at the face,
                      * which is what makes the zero border exact), D_{j-1} fused */
-                    ZR_RC(blur_dev(q.c, q.L[j - 1] + a * XY, q.L[j] + a * XY, q.D[j - 1] ? q.D[j - 1] + a * XY : nullptr, X, Y, b - a, extras[j - 1], 0.01f));
+                    ZR_RC(blur_dev(q.c, q.L[j - 1] + a * XY, q.L[j] + a * XY, q.D[j - 1] ? q.D[j - 1] + a * XY : nullptr, X, Y, b - a, sigmas.extras[j - 1], 0.01f));
                     ZR_HIP(hipEventRecord(q.ev_level, q.c->stream));
                     if (j == 3) ZR_HIP(hipEventRecord(q.ev_l3, q.c->stream));
                 }
@@ -656,7 +656,7 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
                     ZR_COMM(hipEventRecord(q.ev_halo, q.halo_stream));
                     ZR_COMM(hipStreamWaitEvent(q.c->stream, q.ev_halo, 0));
                 }
-                const int64_t a = (q.lo ? std::max(q.e0, q.z0 - ZS_BLUR) : q.e0) - q.e0, b = (q.hi ? std::min(q.e1, q.z1 + ZS_BLUR) : q.e1) - q.e0;
+                const int64_t a = q.c0 - q.e0, b = q.c1 - q.e0;
                 if (q.D[j - 1] && q.lo && q.z0 - q.e0 > a)
                     ZR_HIP(sift3d_launch_dog(q.c->stream, q.L[j - 1] + a * XY, q.L[j] + a * XY, q.D[j - 1] + a * XY, (q.z0 - q.e0 - a) * XY));
                 if (q.D[j - 1] && q.hi && b > q.z1 - q.e0)
@@ -718,38 +718,24 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
             ZR_HIP(hipEventRecord(q.c->ev_oct[0], q.c->stream));
             ZR_HIP(hipStreamWaitEvent(q.c->ex_stream, q.c->ev_oct[0], 0));
             q.c->cand_stream = q.c->ex_stream;
+            /* (lazy: D_0 and D_4 are NULL, the jobs take L_0 - L_1 and L_4 - blur(L_4) for them) */
+            level_job jobs[3];
+            octave_jobs(jobs, q.L, q.D, X, 0, Y, q.e1 - q.e0, (int)(q.z0 - q.e0), (int)(q.z1 - q.e0), o * 3, taps5, ntaps5);
             for (int l = 0; l < 3; l++) {
-                const int id = o * 3 + l;
-                level_job jb = {q.D[l], q.D[l + 1], q.D[l + 2], X, Y, q.e1 - q.e0, (int)(q.z0 - q.e0), (int)(q.z1 - q.e0), id, 0};
-                if (lazy && l == 0) { /* the level below D_1 is L_0 - L_1 */
-                    jb.dp = q.L[0];
-                    jb.prev_b = q.L[1];
-                }
-                if (lazy && l == 2) { /* the level above D_3 is L_4 - blur(L_4) */
-                    jb.dn = nullptr;
-                    jb.next_g = q.L[4];
-                    jb.next_ntaps = ntaps5;
-                    for (int t = 0; t < ntaps5; t++) jb.next_taps[t] = taps5[t];
-                }
-                const int rc_ = cand_append(q.c, jb, true);
+                const int rc_ = cand_append(q.c, jobs[l], true);
                 if (rc_ != SIFT3D_OK) {
                     q.c->cand_stream = nullptr;
                     ZR_FAIL(rc_, "rank %d: %s", r, sift3d_last_error(q.c));
                 }
-                sift3d_level &lv = q.levels[(size_t)id];
-                lv.img = q.L[l + 1]; lv.dogc = q.D[l + 1];
-                lv.X = (int)X; lv.Y = (int)Y; lv.Z = (int)zo; lv.XP = (int)X;
-                lv.sigma_h = sig[l]; lv.sigma_c = sig[l + 1]; lv.sigma_l = sig[l + 2];
-                lv.octave_factor = fscale;
-                lv.Zl = (int)(q.e1 - q.e0); lv.z_off = (int)q.e0; lv.pad = 0;
             }
+            octave_level_rows(&q.levels[(size_t)o * 3], q.L, q.D, X, X, Y, zo, q.e1 - q.e0, q.e0, sigmas, fscale);
             q.c->cand_stream = nullptr;
             if (q.lo || q.hi) ZR_HIP(hipStreamWaitEvent(q.c->stream, q.ev_patch, 0)); /* before the subsample reads L3 beyond +- 8: the first deferred step only */
             if (more && sharded && o + 1 < K) {
                 int64_t n0, n1;
                 plan.slab(r, o + 1, n0, n1);
-                const int64_t ne0 = q.lo ? std::max<int64_t>(0, n0 - ZS_HALO) : n0, ne1 = q.hi ? std::min<int64_t>(zn, n1 + ZS_HALO) : n1;
-                const int64_t s0 = q.lo ? std::max(ne0, n0 - ZS_BLUR) : ne0, s1 = q.hi ? std::min(ne1, n1 + ZS_BLUR) : ne1;
+                const zs_extent nxt = zs_extent_of(n0, n1, q.lo, q.hi, zn);
+                const int64_t ne0 = nxt.e0, ne1 = nxt.e1, s0 = nxt.c0, s1 = nxt.c1;
                 float *nx0 = q.alloc((ne1 - ne0) * XYn);
                 if (!nx0) ZR_FAIL(SIFT3D_ERR_MEMORY, "rank %d: out of device memory", r);
                 ZR_HIP(sift3d_launch_subsample(q.c->stream, q.L[3] + (2 * s0 - q.e0) * XY, X, X, Y, 2 * (s1 - s0), nx0 + (s0 - ne0) * XYn, Xn));
