@@ -161,6 +161,9 @@ def hip_lib():
     _sig(L.sift3d_zslab_set_volume, I, P, P, C.c_char_p, I64)
     _sig(L.sift3d_zslab_extract_resident, I, P, F, I, F, F, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_knn64, I, I, P, I64, P, I64, I, P, P, I, P, C.c_char_p, I64)
+    _sig(L.sift3d_match_ratio, I, I, P, I64, P, I64, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_hough_similarity, I, I, P, P, P, P, P, P, C.c_int32, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_match_keys, I, I, P, I64, P, I64, C.c_int32, P, C.c_char_p, I64)
     _sig(L.sift3d_get_level_slice, I, P, I, I, I64, P, P, P)
     _hip = L
     return L
@@ -192,6 +195,10 @@ def host_lib():
     _sig(L.sift3d_match_descriptors, I, P, I64, P)
     _sig(L.sift3d_match_votes, I, P, P, I, P, I, P, P, I, P, P)
     _sig(L.sift3d_match_write_votes, I, C.c_char_p, C.c_char_p, C.c_char_p, P, P, I, I, I)
+    _sig(L.sift3d_log_ratio_interval, I, C.c_double, P, P)
+    _sig(L.sift3d_similarity_invert, None, P, P)
+    _sig(L.sift3d_write_similarity, I, C.c_char_p, P)
+    _sig(L.sift3d_write_alignment_matches, I, C.c_char_p, C.c_char_p, C.c_char_p, P, I64, P, I64, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -368,6 +375,131 @@ def match_descriptors(feats):
     if host_lib().sift3d_match_descriptors(f.ctypes.data, len(f), out.ctypes.data) != 0:
         raise Sift3DError("a descriptor value is outside 0..127")
     return out
+
+
+# ---- matcher, alignment path (featMatchMultiple -a): ratio matching and Hough similarity, DESIGN.md section 7b -------------
+class Similarity(C.Structure):
+    """sift3d_similarity"""
+    _fields_ = [("scale", C.c_float), ("rot", C.c_float * 9), ("trans", C.c_float * 3), ("center0", C.c_float * 3),
+                ("center1", C.c_float * 3), ("n_matches", C.c_int32), ("inliers", C.c_int32), ("winner", C.c_int32),
+                ("capacity", C.c_int32), ("moving_idx", C.c_void_p), ("fixed_idx", C.c_void_p), ("inlier", C.c_void_p),
+                ("dist2", C.c_void_p)]
+
+
+def _raise(name, rc, err):
+    e = Sift3DError("%s -> %d: %s" % (name, rc, err.value.decode(errors="replace")))
+    e.code = rc
+    raise e
+
+
+def match_ratio(db_feats, q_feats, device=0):
+    """sift3d_match_ratio: the reference's ratio search of every query record over all database records (>= 2), in index
+    order.  Returns (i1, d1, i2, d2, kernel_ms); the reference's ratio is float32(d1) / float32(d2)."""
+    db = np.ascontiguousarray(db_feats, FEATURE_DTYPE)
+    q = np.ascontiguousarray(q_feats, FEATURE_DTYPE)
+    out = [np.empty(len(q), np.int32) for _ in range(4)]
+    ms, err = C.c_double(0.0), C.create_string_buffer(256)
+    rc = hip_lib().sift3d_match_ratio(int(device), db.ctypes.data, len(db), q.ctypes.data, len(q), *[o.ctypes.data for o in out], C.byref(ms), err, 256)
+    if rc != 0:
+        _raise("sift3d_match_ratio", rc, err)
+    return tuple(out) + (ms.value,)
+
+
+def hough_similarity(p0, p1, s0, s1, o0, o1, device=0):
+    """sift3d_hough_similarity on M correspondences (moving side p0 / s0 / o0, fixed side p1 / s1 / o1; points M x 3,
+    scales M, frames M x 3 x 3 row-major).  Returns a dict: counts (-1: degenerate hypothesis), winner (-1: none), rot
+    (3 x 3), scale, flags."""
+    arr = [np.ascontiguousarray(a, np.float32) for a in (p0, p1, s0, s1, o0, o1)]
+    m = len(arr[2])
+    assert arr[0].size == 3 * m and arr[1].size == 3 * m and arr[3].size == m and arr[4].size == 9 * m and arr[5].size == 9 * m
+    counts, flags = np.empty(m, np.int32), np.empty(m, np.int32)
+    rot, scale, winner = np.zeros(9, np.float32), C.c_float(0.0), C.c_int32(-1)
+    err = C.create_string_buffer(256)
+    rc = hip_lib().sift3d_hough_similarity(int(device), *[a.ctypes.data for a in arr], m, counts.ctypes.data, C.byref(winner), rot.ctypes.data,
+                                           C.byref(scale), flags.ctypes.data, err, 256)
+    if rc != 0:
+        _raise("sift3d_hough_similarity", rc, err)
+    return {"counts": counts, "winner": winner.value, "rot": rot.reshape(3, 3), "scale": np.float32(scale.value), "flags": flags}
+
+
+def _similarity_dict(t, arrays):
+    n = t.n_matches
+    d = {"scale": np.float32(t.scale), "rot": np.array(t.rot, np.float32).reshape(3, 3), "trans": np.array(t.trans, np.float32),
+         "center0": np.array(t.center0, np.float32), "center1": np.array(t.center1, np.float32), "n_matches": n,
+         "inliers": t.inliers, "winner": t.winner}
+    for k, a in arrays.items():
+        d[k] = a[:n].copy()
+    return d
+
+
+def _similarity_struct(d):
+    """a sift3d_similarity from a match_keys dict (the arrays kept alive in the returned tuple)"""
+    t = Similarity()
+    t.scale = float(d["scale"])
+    t.rot[:] = [float(v) for v in np.asarray(d["rot"], np.float32).ravel()]
+    t.trans[:] = [float(v) for v in np.asarray(d["trans"], np.float32)]
+    t.center0[:] = [float(v) for v in np.asarray(d.get("center0", np.zeros(3)), np.float32)]
+    t.center1[:] = [float(v) for v in np.asarray(d.get("center1", np.zeros(3)), np.float32)]
+    t.n_matches, t.inliers, t.winner = int(d.get("n_matches", 0)), int(d.get("inliers", 0)), int(d.get("winner", -1))
+    keep = {}
+    for k in ("moving_idx", "fixed_idx", "inlier", "dist2"):
+        a = np.ascontiguousarray(d.get(k, np.zeros(0)), np.int32)
+        keep[k] = a
+        setattr(t, k, a.ctypes.data if len(a) else None)
+    t.capacity = min(len(a) for a in keep.values()) if keep else 0
+    return t, keep
+
+
+def match_keys(fixed, moving, device=0, max_matches=3000):
+    """sift3d_match_keys: MatchKeys of `moving` onto `fixed` (records as FEATURE_DTYPE).  Returns a dict: scale, rot (3 x 3),
+    trans, center0, center1, n_matches, inliers, winner and per match (sorted by ratio) moving_idx, fixed_idx, inlier,
+    dist2.  x_fixed = scale * rot @ x_moving + trans."""
+    f = np.ascontiguousarray(fixed, FEATURE_DTYPE)
+    m = np.ascontiguousarray(moving, FEATURE_DTYPE)
+    cap = max(1, min(len(m), int(max_matches)))
+    arrays = {k: np.zeros(cap, np.int32) for k in ("moving_idx", "fixed_idx", "inlier", "dist2")}
+    t = Similarity()
+    t.capacity = cap
+    for k, a in arrays.items():
+        setattr(t, k, a.ctypes.data)
+    err = C.create_string_buffer(256)
+    rc = hip_lib().sift3d_match_keys(int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), int(max_matches), C.byref(t), err, 256)
+    if rc != 0:
+        _raise("sift3d_match_keys", rc, err)
+    return _similarity_dict(t, arrays)
+
+
+def log_ratio_interval(t):
+    """sift3d_log_ratio_interval: the float interval [lo, hi] of ratios r with fabsf(logf(r)) < float32(t)."""
+    lo, hi = C.c_float(0.0), C.c_float(0.0)
+    if host_lib().sift3d_log_ratio_interval(float(t), C.byref(lo), C.byref(hi)) != 0:
+        raise Sift3DError("logf is not monotonic near the interval's ends")
+    return np.float32(lo.value), np.float32(hi.value)
+
+
+def similarity_invert(d):
+    """sift3d_similarity_invert (TransformSimilarity::Invert) of a match_keys-style dict: (scale, rot, trans)."""
+    t, _keep = _similarity_struct(d)
+    out = Similarity()
+    host_lib().sift3d_similarity_invert(C.byref(t), C.byref(out))
+    return np.float32(out.scale), np.array(out.rot, np.float32).reshape(3, 3), np.array(out.trans, np.float32)
+
+
+def write_similarity(path, d):
+    """sift3d_write_similarity: TransformSimilarity::WriteMatrix of a match_keys-style dict."""
+    t, _keep = _similarity_struct(d)
+    if host_lib().sift3d_write_similarity(os.fsencode(path), C.byref(t)) != 0:
+        raise Sift3DError("could not write %s" % path)
+
+
+def write_alignment_matches(base, fixed_name, moving_name, fixed, moving, d):
+    """sift3d_write_alignment_matches: <base>.matches.info.txt, .matches.img1.txt, .matches.img2.txt."""
+    f = np.ascontiguousarray(fixed, FEATURE_DTYPE)
+    m = np.ascontiguousarray(moving, FEATURE_DTYPE)
+    t, _keep = _similarity_struct(d)
+    if host_lib().sift3d_write_alignment_matches(os.fsencode(base), os.fsencode(fixed_name), os.fsencode(moving_name), f.ctypes.data, len(f),
+                                                 m.ctypes.data, len(m), C.byref(t)) != 0:
+        raise Sift3DError("could not write the match files of %s" % base)
 
 
 def match_votes(first, labels, n_labels, nn_idx, nn_dist2):

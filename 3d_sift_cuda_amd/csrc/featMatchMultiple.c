@@ -10,8 +10,13 @@
  *   - the search is exact (sift3d_knn64 on the GPU) where the reference asks FLANN's randomised kd-tree forest, which is
  *     neither deterministic nor part of /root/reference;
  *   - the reference's main() calls matchAllToOne (:640), whose nearest-neighbour step has its distance computation commented
- *     out (featMatchUtilities.cpp:348-362: every distance is the constant 0), so that path cannot be restated as a working
- *     program; the all-to-all path is the one that still computes what its name says.
+ *     out (featMatchUtilities.cpp:348-362: every distance is the constant 0); the all-to-all path is the one that computes
+ *     what its name says without that distance, and stays the default.
+ * -a selects matchAllToOne (:148-390) with the distance restored (DESIGN.md sections 7b and 8): image 0 is the fixed image,
+ * every other image is aligned to it by ratio matching and a Hough similarity (sift3d_match_keys), and the files of
+ * :297-358 are written beside each moving key file: .matches.info.txt, .matches.img1.txt, .matches.img2.txt, .trans.txt,
+ * .trans-inverse.txt, .update.key; stdout gets one "inliers" line per moving image.  -s2 runs three passes (all records,
+ * peaks, valleys), each overwriting the files, as :640-644 does.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,6 +33,7 @@ static void usage(void)
     printf("Usage: %s [options] <input keys 1> <input keys 2> ... \n", "featMatchMultiple");
     printf("  <input keys 1, ...>: input key files, produced from featExtract.\n");
     printf("  <output transform>: output text file with linear transform from keys 2 -> keys 1.\n");
+    printf("  -a: align keys 2, 3, ... to keys 1 (ratio matching + Hough similarity; default: all-to-all votes).\n");
 }
 
 typedef struct {
@@ -82,6 +88,47 @@ done:
     return rc;
 }
 
+/* one matchAllToOne pass (featMatchMultiple.cpp:148-390): image 0 fixed, every other image aligned to it */
+static int align_all(char **names, key_set *sets, int n_sets, int device)
+{
+    enum { MAX_MATCHES = 3000 }; /* MatchKeys' iMaxMatches */
+    int32_t mi[MAX_MATCHES], fi[MAX_MATCHES], in[MAX_MATCHES], d2[MAX_MATCHES];
+    char err[256] = "", *path = NULL;
+    for (int i = 1; i < n_sets; i++) {
+        sift3d_similarity t, inv;
+        memset(&t, 0, sizeof t);
+        t.capacity = MAX_MATCHES;
+        t.moving_idx = mi;
+        t.fixed_idx = fi;
+        t.inlier = in;
+        t.dist2 = d2;
+        if (sift3d_match_keys(device, sets[0].f, sets[0].n, sets[i].f, sets[i].n, MAX_MATCHES, &t, err, sizeof err) != SIFT3D_OK) {
+            printf("Error: alignment of %s failed: %s\n", names[i], err);
+            free(path);
+            return -1;
+        }
+        path = (char *)realloc(path, strlen(names[i]) + 32);
+        if (!path) return -1;
+        int rc = sift3d_write_alignment_matches(names[i], names[0], names[i], sets[0].f, sets[0].n, sets[i].f, sets[i].n, &t);
+        sprintf(path, "%s.trans.txt", names[i]);
+        if (rc == 0) rc = sift3d_write_similarity(path, &t);
+        sift3d_similarity_invert(&t, &inv);
+        sprintf(path, "%s.trans-inverse.txt", names[i]);
+        if (rc == 0) rc = sift3d_write_similarity(path, &inv);
+        printf("%s: inliers %d\t%d\t%d\t%f\n", names[i], t.inliers, 0, 0, t.scale);
+        sprintf(path, "%s.update.key", names[i]);
+        if (rc == 0) rc = sift3d_write_key(path, sets[i].f, sets[i].n, -1.0f, 0, NULL);
+        if (rc != 0) {
+            printf("Error: could not write the alignment files of %s\n", names[i]);
+            free(path);
+            return -1;
+        }
+    }
+    printf("\n");
+    free(path);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (sift3d_abi_version() != SIFT3D_ABI_VERSION) { /* the library writes whole structures through this program's pointers */
@@ -98,7 +145,7 @@ int main(int argc, char **argv)
         fprintf(cf, "\n");
         fclose(cf);
     }
-    int a = 1, only_reoriented = 1, peaks_mode = 4, neighbours = 5;
+    int a = 1, only_reoriented = 1, peaks_mode = 4, neighbours = 5, align = 0;
     const char *report = "report.txt", *list_file = NULL;
     while (a < argc && argv[a][0] == '-') {
         switch (argv[a][1]) {
@@ -119,6 +166,10 @@ int main(int argc, char **argv)
             a++;
             if (a >= argc) { usage(); return -1; }
             neighbours = atoi(argv[a++]);
+            break;
+        case 'a': case 'A':
+            align = 1;
+            a++;
             break;
         case 'f': case 'F':
             a++;
@@ -217,6 +268,14 @@ int main(int argc, char **argv)
     }
     /* -s2: all three passes append to matching_votes.txt / vote_count.txt (featMatchMultiple.cpp:58-65: "at" whenever
      * bOnlyPeaksFeatures == 2, the first pass included) */
+    if (align) {
+        int rc = align_all(names, sets, n_read, 0);
+        if (rc == 0 && peaks_mode == 2) {
+            rc = align_all(names, peaks, n_read, 0);
+            if (rc == 0) rc = align_all(names, valleys, n_read, 0);
+        }
+        return rc == 0 ? 0 : -1;
+    }
     int rc = match_all(names, sets, n_read, neighbours, title, peaks_mode == 2, 0);
     if (rc == 0 && peaks_mode == 2) {
         rc = match_all(names, peaks, n_read, neighbours, "Peaks", 1, 0);

@@ -1,5 +1,6 @@
 /*
- * match_votes.c -- feature filters, descriptor bytes and the soft-vote accumulation of the matcher (see match.h).
+ * match_votes.c -- feature filters and the soft-vote accumulation of the matcher (see match.h; the descriptor bytes are in
+ * match_desc.c).
  * R/ = /root/reference/3dsift_cleanup-softVote_App_Weight_SoftMax/.
  */
 #include "match.h"
@@ -29,20 +30,6 @@ int64_t sift3d_match_filter(sift3d_feature *f, int64_t n, int reoriented, int pe
         f[kept++] = r;
     }
     return kept;
-}
-
-int sift3d_match_descriptors(const sift3d_feature *f, int64_t n, int8_t *out)
-{
-    /* The reference hands the floats to FLANN as they are; the rank transform leaves whole numbers 0..63 there.  The search
-     * here works on bytes, so anything that is not a whole number in 0..127 is refused -- tested on the float, because a
-     * cast of an out-of-range float to char is undefined (advisor, round 3) and would wrap some of them into range. */
-    for (int64_t i = 0; i < n; i++)
-        for (int j = 0; j < SIFT3D_DESC_LEN; j++) {
-            const float d = f[i].desc[j];
-            if (!(d >= 0.0f && d <= 127.0f) || d != (float)(int)d) return -1;
-            out[i * SIFT3D_DESC_LEN + j] = (int8_t)(int)d;
-        }
-    return 0;
 }
 
 /* which database feature a query image's features have voted for already, and with what weight: open addressing over

@@ -478,6 +478,70 @@ int sift3d_zslab_set_tuning(sift3d_zslab *h, int knob, int value);
 int sift3d_knn64(int device, const int8_t *db, int64_t n_db, const int8_t *queries, int64_t n_q, int k, int32_t *idx,
                  int32_t *dist2, int repeats, double *kernel_ms, char *err, int64_t err_len);
 
+/* ---- matcher, alignment path: ratio matching and Hough similarity (featMatchMultiple -a) ------------------------------
+ * matchAllToOne -> MatchKeys -> determine_similarity_transform_hough (R/featMatchMultiple/featMatchMultiple.cpp:148-390,
+ * R/feat_common/featMatchUtilities.cpp:336-428, 816-1250) with the descriptor distance DistSqrPCs(.., 64) restored; the
+ * deliberate differences are listed in DESIGN.md section 8.  The fixed image's records are the database, the moving
+ * image's records the queries; the transform maps moving coordinates to fixed ones. */
+
+/* msComputeNearestNeighborDistanceRatioInfo: for every query record the reference's in-order scan of ALL database records
+ * (n_db >= 2), with compatible_features at its defaults between the candidate and the current best.  Per query: i1 / d1
+ * the best database index and its squared distance, i2 / d2 the second; the reference's ratio is (float)d1 / (float)d2.
+ * Descriptors as sift3d_match_descriptors takes them (whole numbers 0..127, else SIFT3D_ERR_ARG).  *kernel_ms (may be
+ * NULL): device time of the search kernel. */
+int sift3d_match_ratio(int device, const sift3d_feature *db, int64_t n_db, const sift3d_feature *q, int64_t n_q, int32_t *i1, int32_t *d1,
+                       int32_t *i2, int32_t *d2, double *kernel_ms, char *err, int64_t err_len);
+
+/* determine_similarity_transform_hough on M given correspondences (pfProb all ones): p0 / s0 / o0 the moving side (3, 1
+ * and 9 floats per match, frames row-major), p1 / s1 / o1 the fixed side.  counts (M entries, may be NULL): inliers of each
+ * one-match hypothesis, -1 where two of its three points coincide (skipped).  *winner: the first hypothesis with the most
+ * inliers (at least one), or -1; rot / *scale its transform and flags (M entries, may be NULL) its inlier flags (zeros
+ * when there is no winner).  The winner's transform is computed on the device and checked bit for bit against the host. */
+int sift3d_hough_similarity(int device, const float *p0, const float *p1, const float *s0, const float *s1, const float *o0, const float *o1,
+                            int32_t m, int32_t *counts, int32_t *winner, float *rot, float *scale, int32_t *flags, char *err,
+                            int64_t err_len);
+
+/* The result of MatchKeys for one moving image: x_fixed = scale * rot (x_moving - center0) + center1 = scale * rot x_moving
+ * + trans.  The identity (scale 1, rot I, trans 0, center1 = center0) when there are fewer than 2 fixed records, no moving
+ * record, at most 3 matches or no winning hypothesis.  inliers: the match count when there are at most 3 matches, else
+ * the winner's inlier count (0 without a winner). */
+typedef struct {
+    float scale;
+    float rot[9];      /* row-major */
+    float trans[3];
+    float center0[3];  /* bounding-box centre of the moving records (getMinMaxDim) */
+    float center1[3];  /* center0 mapped by the winning hypothesis */
+    int32_t n_matches; /* min(moving records, max_matches) when there are at least 2 fixed records, else 0 */
+    int32_t inliers;
+    int32_t winner;    /* index into the sorted matches, or -1 */
+    int32_t capacity;  /* entries the caller's arrays below hold (0: they are not filled) */
+    int32_t *moving_idx; /* per match, sorted by (ratio, moving index) ascending with NaN ratios last: */
+    int32_t *fixed_idx;
+    int32_t *inlier;   /* 1: inlier of the winner */
+    int32_t *dist2;    /* squared descriptor distance of the match */
+} sift3d_similarity;
+
+/* MatchKeys (featMatchUtilities.cpp:1028-1250): ratio search, the matches sorted by ratio and cut at max_matches (the
+ * reference's iMaxMatches is 3000), the Hough, the transform.  out->capacity and the four arrays are the caller's; the
+ * arrays are filled when capacity >= n_matches (else SIFT3D_ERR_CAPACITY, with everything else filled in). */
+int sift3d_match_keys(int device, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving,
+                      int32_t max_matches, sift3d_similarity *out, char *err, int64_t err_len);
+
+/* Host helpers of this path (also in libsift3d_host.so; no GPU needed).
+ * The closed float interval [lo, hi] of ratios r with fabsf(logf(r)) < (float)t, from this host's logf: compatible_features'
+ * scale test as a comparison the device can make.  Returns 0, or -1 if logf is not monotonic within 2^16 floats of an end. */
+int sift3d_log_ratio_interval(double t, float *lo, float *hi);
+/* TransformSimilarity::Invert (R/feat_common/featMatchUtilities.h:213-226): the inverse transform in scale / rot / trans. */
+void sift3d_similarity_invert(const sift3d_similarity *in, sift3d_similarity *out);
+/* TransformSimilarity::WriteMatrix: the 4 x 4 text matrix of a .trans.txt file.  Returns 0 or -1. */
+int sift3d_write_similarity(const char *path, const sift3d_similarity *t);
+/* The three match files of matchAllToOne (featMatchMultiple.cpp:297-358) for one moving image: <base>.matches.info.txt,
+ * .matches.img1.txt and .matches.img2.txt.  fixed_name / moving_name: the key file names as given (the headers name them
+ * with the extension replaced by .hdr).  Every fixed record g gets the moving record of its last inlier (in match order);
+ * t's arrays must hold its n_matches entries.  Returns 0 or -1. */
+int sift3d_write_alignment_matches(const char *base, const char *fixed_name, const char *moving_name, const sift3d_feature *fixed,
+                                   int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving, const sift3d_similarity *t);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
