@@ -31,6 +31,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_HIP = os.path.join(CSRC, "_build", "libsift3d_hip.so")
 LIB_HOST = os.path.join(CSRC, "_build", "libsift3d_host.so")
 FEATEXTRACT = os.path.join(CSRC, "_build", "featExtract")
+FEATRESAMPLE = os.path.join(CSRC, "_build", "featResample")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 6   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -165,6 +166,8 @@ def hip_lib():
     _sig(L.sift3d_hough_similarity, I, I, P, P, P, P, P, P, C.c_int32, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_match_keys, I, I, P, I64, P, I64, C.c_int32, P, C.c_char_p, I64)
     _sig(L.sift3d_get_level_slice, I, P, I, I, I64, P, P, P)
+    _sig(L.sift3d_resample_affine, I, I, P, I64, I64, I64, P, I64, I64, I64, P, I, F, P, C.c_char_p, I64)
+    _sig(L.sift3d_resample_affine_dev, I, P, P, I64, I64, I64, P, I64, I64, I64, P, I, F)
     _hip = L
     return L
 
@@ -199,6 +202,10 @@ def host_lib():
     _sig(L.sift3d_similarity_invert, None, P, P)
     _sig(L.sift3d_write_similarity, I, C.c_char_p, P)
     _sig(L.sift3d_write_alignment_matches, I, C.c_char_p, C.c_char_p, C.c_char_p, P, I64, P, I64, P)
+    _sig(L.sift3d_similarity_matrix, None, P, P)
+    _sig(L.sift3d_read_similarity, I, C.c_char_p, P)
+    _sig(L.sift3d_resample_map, I, P, P, P, P)
+    _sig(L.sift3d_key_vox2key, None, P, P, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -500,6 +507,73 @@ def write_alignment_matches(base, fixed_name, moving_name, fixed, moving, d):
     if host_lib().sift3d_write_alignment_matches(os.fsencode(base), os.fsencode(fixed_name), os.fsencode(moving_name), f.ctypes.data, len(f),
                                                  m.ctypes.data, len(m), C.byref(t)) != 0:
         raise Sift3DError("could not write the match files of %s" % base)
+
+
+# ---- resampling (featResample), DESIGN.md section 7c ----------------------------------------------------------------------
+INTERP = {"linear": 0, "nearest": 1}   # include/sift3d.h: sift3d_interp
+
+
+def _map12(m):
+    a = np.ascontiguousarray(m, np.float32)
+    if a.size != 12:
+        raise ValueError("a resampling map is 3 x 4 floats")
+    return a.reshape(12)
+
+
+def resample_affine(vol, out_shape, map, interp="linear", fill=0.0, device=0, return_ms=False):
+    """sift3d_resample_affine: vol (nz, ny, nx) float32 resampled onto an output of out_shape = (oz, oy, ox) through the
+    3 x 4 map that takes an output voxel index (i, j, k) to a source voxel position.  interp "linear" or "nearest"; output
+    voxels that map outside the source get fill.  return_ms=True returns (out, kernel_ms)."""
+    v = _f32(vol)
+    nz, ny, nx = v.shape
+    oz, oy, ox = (int(d) for d in out_shape)
+    out = np.empty((oz, oy, ox), np.float32)
+    m = _map12(map)
+    ms, err = C.c_double(0.0), C.create_string_buffer(512)
+    rc = hip_lib().sift3d_resample_affine(int(device), v.ctypes.data, nx, ny, nz, out.ctypes.data, ox, oy, oz, m.ctypes.data,
+                                          INTERP[interp], float(fill), C.byref(ms), err, 512)
+    if rc != 0:
+        _raise("sift3d_resample_affine", rc, err)
+    return (out, ms.value) if return_ms else out
+
+
+def resample_map(moving_to_fixed, fixed_vox2key=None, moving_vox2key=None):
+    """sift3d_resample_map: the 3 x 4 map that puts the moving image on the fixed grid, inv(moving_vox2key) .
+    inv(moving_to_fixed) . fixed_vox2key in double, rounded to float32 once (4 x 4 inputs; None = identity)."""
+    ms = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(16) for a in (moving_to_fixed, fixed_vox2key, moving_vox2key)]
+    if ms[0] is None:
+        raise ValueError("moving_to_fixed is required")
+    out = np.zeros(12, np.float32)
+    if host_lib().sift3d_resample_map(*[None if a is None else a.ctypes.data for a in ms], out.ctypes.data) != 0:
+        raise Sift3DError("sift3d_resample_map: a matrix is singular or its last row is not 0 0 0 1")
+    return out.reshape(3, 4)
+
+
+def key_vox2key(voxel=(1.0, 1.0, 1.0), world=None):
+    """sift3d_key_vox2key: the 4 x 4 float32 map from an image's voxel indices to the key coordinates featExtract writes
+    for it -- x + 0.5 in voxel units (world None), world . (x + 0.5 f) under -w / -ws (world: the qto_xyz / sto_xyz used,
+    f = min(voxel) / voxel)."""
+    v = np.ascontiguousarray(voxel, np.float32).reshape(3)
+    w = None if world is None else np.ascontiguousarray(world, np.float32).reshape(16)
+    m = np.zeros(16, np.float32)
+    host_lib().sift3d_key_vox2key(v.ctypes.data, None if w is None else w.ctypes.data, m.ctypes.data)
+    return m.reshape(4, 4)
+
+
+def similarity_matrix(d):
+    """sift3d_similarity_matrix: the 4 x 4 float32 matrix WriteMatrix prints for a match_keys-style dict, before %f."""
+    t, _keep = _similarity_struct(d)
+    m = np.zeros(16, np.float32)
+    host_lib().sift3d_similarity_matrix(C.byref(t), m.ctypes.data)
+    return m.reshape(4, 4)
+
+
+def read_similarity(path):
+    """sift3d_read_similarity: the 4 x 4 float32 matrix of a .trans.txt file."""
+    m = np.zeros(16, np.float32)
+    if host_lib().sift3d_read_similarity(os.fsencode(path), m.ctypes.data) != 0:
+        raise Sift3DError("could not read a 4 x 4 similarity with last row 0 0 0 1 from %s" % path)
+    return m.reshape(4, 4)
 
 
 def match_votes(first, labels, n_labels, nn_idx, nn_dist2):
@@ -827,6 +901,14 @@ class Context:
     def dog_dev(self, d_a, d_b, d_out, n):
         self._chk(self._L.sift3d_dog_dev(self._h, C.c_void_p(int(d_a)), C.c_void_p(int(d_b)), C.c_void_p(int(d_out)), n),
                   "sift3d_dog_dev")
+
+    def resample_affine_dev(self, d_src, src_shape, d_dst, out_shape, map, interp="linear", fill=0.0):
+        """sift3d_resample_affine_dev on device buffers; shapes as (nz, ny, nx)."""
+        nz, ny, nx = (int(d) for d in src_shape)
+        oz, oy, ox = (int(d) for d in out_shape)
+        m = _map12(map)
+        self._chk(self._L.sift3d_resample_affine_dev(self._h, C.c_void_p(int(d_src)), nx, ny, nz, C.c_void_p(int(d_dst)), ox, oy, oz,
+                                                     m.ctypes.data, INTERP[interp], float(fill)), "sift3d_resample_affine_dev")
 
     def subsample2_dev(self, d_in, nx, ny, nz, d_out):
         self._chk(self._L.sift3d_subsample2_dev(self._h, C.c_void_p(int(d_in)), nx, ny, nz, C.c_void_p(int(d_out))),

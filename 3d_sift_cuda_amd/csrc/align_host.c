@@ -3,7 +3,8 @@
  * the device, the inverse of a similarity transform, and the files matchAllToOne writes per moving image
  * (R/featMatchMultiple/featMatchMultiple.cpp:297-358; TransformSimilarity, R/feat_common/featMatchUtilities.h:152-290;
  * R/ = the reference tree).  Linked into libsift3d_hip.so (the interval is computed when the library first aligns, and
- * featMatchMultiple -a writes through it) and into libsift3d_host.so.
+ * featMatchMultiple -a writes through it) and into libsift3d_host.so.  At the end: the .trans.txt matrix, its reader and
+ * the voxel-to-voxel map of featResample (section 7c).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -162,4 +163,101 @@ done:
     free(model);
     free(path);
     return rc;
+}
+
+/* ---- featResample ---------------------------------------------------------------------------- */
+
+void sift3d_similarity_matrix(const sift3d_similarity *t, float m[16])
+{
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) m[4 * r + c] = t->scale * t->rot[3 * r + c]; /* as WriteMatrix forms it, before %f */
+        m[4 * r + 3] = t->trans[r];
+    }
+    m[12] = m[13] = m[14] = 0.0f;
+    m[15] = 1.0f;
+}
+
+int sift3d_read_similarity(const char *path, float m[16])
+{
+    FILE *f = fopen(path, "rt");
+    if (!f) return -1;
+    double v[16];
+    int n = 0;
+    while (n < 16 && fscanf(f, "%lf", &v[n]) == 1) n++;
+    char rest[2] = "";
+    const int extra = fscanf(f, " %1s", rest); /* anything but white space after the sixteenth number is an error */
+    fclose(f);
+    if (n != 16 || extra == 1) return -1;
+    if (v[12] != 0.0 || v[13] != 0.0 || v[14] != 0.0 || v[15] != 1.0) return -1;
+    for (int k = 0; k < 16; k++) m[k] = (float)v[k];
+    return 0;
+}
+
+/* the inverse of an affine 4 x 4 (last row 0 0 0 1) in double: the adjugate of the 3 x 3 part over its determinant, then
+ * the translation.  -1 when the last row is not 0 0 0 1 or the 3 x 3 part is singular or not finite. */
+static int affine_inverse(const double a[16], double o[16])
+{
+    if (a[12] != 0.0 || a[13] != 0.0 || a[14] != 0.0 || a[15] != 1.0) return -1;
+    const double c00 = a[5] * a[10] - a[6] * a[9], c01 = a[6] * a[8] - a[4] * a[10], c02 = a[4] * a[9] - a[5] * a[8];
+    const double det = a[0] * c00 + a[1] * c01 + a[2] * c02;
+    if (!(det != 0.0) || !isfinite(det)) return -1;
+    const double inv[9] = {c00, a[2] * a[9] - a[1] * a[10], a[1] * a[6] - a[2] * a[5],
+                           c01, a[0] * a[10] - a[2] * a[8], a[2] * a[4] - a[0] * a[6],
+                           c02, a[1] * a[8] - a[0] * a[9], a[0] * a[5] - a[1] * a[4]};
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) o[4 * r + c] = inv[3 * r + c] / det;
+        o[4 * r + 3] = -(o[4 * r] * a[3] + o[4 * r + 1] * a[7] + o[4 * r + 2] * a[11]);
+        if (!isfinite(o[4 * r]) || !isfinite(o[4 * r + 1]) || !isfinite(o[4 * r + 2]) || !isfinite(o[4 * r + 3])) return -1;
+    }
+    o[12] = o[13] = o[14] = 0.0;
+    o[15] = 1.0;
+    return 0;
+}
+
+static void mul44(const double a[16], const double b[16], double o[16])
+{
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) o[4 * r + c] = a[4 * r] * b[c] + a[4 * r + 1] * b[4 + c] + a[4 * r + 2] * b[8 + c] + a[4 * r + 3] * b[12 + c];
+}
+
+static void load44(const float *m, double o[16])
+{
+    for (int k = 0; k < 16; k++) o[k] = m ? (double)m[k] : (k % 5 == 0 ? 1.0 : 0.0);
+}
+
+int sift3d_resample_map(const float moving_to_fixed[16], const float fixed_vox2key[16], const float moving_vox2key[16], float map[12])
+{
+    double t[16], fv[16], mv[16], ti[16], mvi[16], p[16], a[16];
+    load44(moving_to_fixed, t);
+    load44(fixed_vox2key, fv);
+    load44(moving_vox2key, mv);
+    if (affine_inverse(t, ti) != 0 || affine_inverse(mv, mvi) != 0 || affine_inverse(fv, p) != 0) return -1; /* p: scratch */
+    /* A = inv(moving_vox2key) . inv(T) . fixed_vox2key: output (fixed) voxel -> fixed key -> moving key -> moving voxel */
+    mul44(ti, fv, p);
+    mul44(mvi, p, a);
+    for (int k = 0; k < 12; k++) {
+        if (!isfinite(a[k])) return -1;
+        map[k] = (float)a[k];
+    }
+    return 0;
+}
+
+void sift3d_key_vox2key(const float voxel[3], const float world[16], float m[16])
+{
+    /* featExtract's records sit half a voxel past the voxel index.  Under -w the volume is first resampled to isotropic
+     * voxels (world.c): isotropic voxel x' samples the original position x' * f, f = min(voxel) / voxel per axis, and the
+     * matrix columns are scaled by f, so the record of original position x is world . (x + 0.5 f). */
+    double v[16];
+    for (int k = 0; k < 16; k++) v[k] = world ? (double)world[k] : (k % 5 == 0 ? 1.0 : 0.0);
+    float f[3] = {1.0f, 1.0f, 1.0f};
+    if (world) {
+        float mn = voxel[0];
+        if (voxel[1] < mn) mn = voxel[1];
+        if (voxel[2] < mn) mn = voxel[2];
+        for (int a = 0; a < 3; a++) f[a] = mn / voxel[a];
+    }
+    for (int r = 0; r < 4; r++) {
+        for (int c = 0; c < 3; c++) m[4 * r + c] = (float)v[4 * r + c];
+        m[4 * r + 3] = (float)(v[4 * r + 3] + v[4 * r] * 0.5 * f[0] + v[4 * r + 1] * 0.5 * f[1] + v[4 * r + 2] * 0.5 * f[2]);
+    }
 }

@@ -1,0 +1,148 @@
+/*
+ * featResample.c -- the third step after featExtract and featMatchMultiple -a: the moving image resampled onto the fixed
+ * image's grid through the <moving>.trans.txt that -a wrote.  Beyond the reference, which stops at
+ * the matrix.
+ *
+ *   featResample [options] <fixed image> <moving image> <moving.trans.txt> <output image>
+ *
+ * .trans.txt maps the moving image's key coordinates to the fixed image's.  A blob centred on voxel x gets a key at
+ * x + 0.5 by default, and at qto_xyz / sto_xyz . (x + 0.5 f) under featExtract -w / -ws, f = min(voxel) / voxel
+ * (sift3d_key_vox2key; tests/test_resample_cpu.py pins both forms on the oracle's extraction).  Keys of -2+ / -2-
+ * extractions are not supported.  The output is float32 with the fixed image's dims, voxel sizes, qform and sform.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "nifti_min.h"
+#include "sift3d.h"
+
+static void print_options(void)
+{
+    printf("Volumetric image resampling by a feature alignment transform v1.0\n");
+    printf("Usage: %s [options] <fixed image> <moving image> <moving.trans.txt> <output image>\n", "featResample");
+    printf("  <fixed image>: nifti (.nii,.hdr,.nii.gz), the grid of the output.\n");
+    printf("  <moving image>: nifti (.nii,.hdr,.nii.gz), the image to resample.\n");
+    printf("  <moving.trans.txt>: the 4x4 transform featMatchMultiple -a wrote for the moving image.\n");
+    printf("  <output image>: float32 nifti (.nii,.nii.gz) on the fixed image's grid.\n");
+    printf(" [options]\n");
+    printf("  -w         : the features were extracted with -w (world coordinates, NIFTI qto_xyz matrix).\n");
+    printf("  -ws        : the features were extracted with -ws (world coordinates, NIFTI sto_xyz matrix).\n");
+    printf("  -n         : nearest-neighbour interpolation (label maps; default is trilinear).\n");
+    printf("  -f<value>  : value of output voxels that map outside the moving image (default 0).\n");
+    printf("  -d[0-9]    : set device id to be used.\n");
+}
+
+/* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
+static void world_matrix(nifti_min_image *img, int world_mode, float m[16])
+{
+    float(*w)[4] = img->qto_xyz;
+    if (world_mode == 2) {
+        if (img->sform_code > 0) w = img->sto_xyz;
+        else printf("Error: sform_code <= 0, using qto_xyz instead of sto_xyz\n");
+    }
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) m[4 * r + c] = w[r][c];
+    m[12] = m[13] = m[14] = 0.0f;
+    m[15] = 1.0f;
+}
+
+int main(int argc, char **argv)
+{
+    int device = 0, world_mode = 0, interp = SIFT3D_INTERP_LINEAR;
+    float fill = 0.0f;
+    int arg = 1;
+    while (arg < argc && argv[arg][0] == '-') {
+        switch (argv[arg][1]) {
+        case 'w':
+        case 'W':
+            world_mode = 1;
+            if (argv[arg][2] == 's' || argv[arg][2] == 'S') world_mode = 2;
+            break;
+        case 'n':
+            interp = SIFT3D_INTERP_NEAREST;
+            break;
+        case 'f': {
+            char *end = NULL;
+            fill = strtof(argv[arg] + 2, &end);
+            if (end == argv[arg] + 2 || *end != 0) {
+                printf("Error: bad fill value: %s\n", argv[arg]);
+                print_options();
+                return -1;
+            }
+            break;
+        }
+        case 'd':
+            if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count()) {
+                printf("Error: unknown device: %s\n", argv[arg] + 2);
+                print_options();
+                return -1;
+            }
+            device = argv[arg][2] - '0';
+            break;
+        default:
+            printf("Error: unknown command line argument: %s\n", argv[arg]);
+            print_options();
+            return -1;
+        }
+        arg++;
+    }
+    if (argc - arg != 4) {
+        print_options();
+        return -1;
+    }
+    const char *fixed_path = argv[arg], *moving_path = argv[arg + 1], *trans_path = argv[arg + 2], *out_path = argv[arg + 3];
+
+    nifti_min_image fixed, moving;
+    nifti_min_stream *fs = NULL;
+    if (nifti_min_open(fixed_path, &fixed, &fs) != 0) { /* the header is all the fixed image gives */
+        printf("Error: could not read input file: %s\n", fixed_path);
+        return -1;
+    }
+    nifti_min_close(fs);
+    if (nifti_min_read(moving_path, &moving) != 0) {
+        printf("Error: could not read input file: %s\n", moving_path);
+        return -1;
+    }
+    float t[16], fw[16], mw[16], fv[16], mv[16], map[12];
+    if (sift3d_read_similarity(trans_path, t) != 0) {
+        printf("Error: could not read transform file: %s\n", trans_path);
+        return -1;
+    }
+    const float fvox[3] = {fixed.dx, fixed.dy, fixed.dz}, mvox[3] = {moving.dx, moving.dy, moving.dz};
+    if (world_mode) {
+        world_matrix(&fixed, world_mode, fw);
+        world_matrix(&moving, world_mode, mw);
+    }
+    sift3d_key_vox2key(fvox, world_mode ? fw : NULL, fv);
+    sift3d_key_vox2key(mvox, world_mode ? mw : NULL, mv);
+    if (sift3d_resample_map(t, fv, mv, map) != 0) {
+        printf("Error: singular transform: %s\n", trans_path);
+        return -1;
+    }
+    printf("Resampling: %s (i=%d j=%d k=%d) onto %s (i=%d j=%d k=%d)\n", moving_path, moving.nx, moving.ny, moving.nz, fixed_path, fixed.nx,
+           fixed.ny, fixed.nz);
+    const size_t n_out = (size_t)fixed.nx * fixed.ny * fixed.nz;
+    float *out = (float *)malloc(sizeof(float) * n_out);
+    if (!out) {
+        printf("Error: could not resample, insufficient memory.\n");
+        return -1;
+    }
+    char err[512] = "";
+    double ms = 0;
+    /* the first volume of a 4-D moving image */
+    const int rc = sift3d_resample_affine(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map, interp,
+                                          fill, &ms, err, sizeof err);
+    if (rc != SIFT3D_OK) {
+        printf("Error: could not resample: %s\n", err);
+        return -1;
+    }
+    if (nifti_min_write_f32_geom(out_path, out, fixed_path) != 0) {
+        printf("Error: could not write output file: %s\n", out_path);
+        return -1;
+    }
+    printf("\nDone.\n");
+    free(out);
+    nifti_min_free(&moving);
+    return 0;
+}

@@ -409,8 +409,9 @@ int nifti_min_write_f32(const char *path, const float *data, int nx, int ny, int
     return nifti_min_write_f32_ex(path, data, nx, ny, nz, dx, dy, dz, 0, 0);
 }
 
-int nifti_min_write_f32_ex(const char *path, const float *data, int nx, int ny, int nz, float dx, float dy, float dz,
-                           const float *q, const float *srow)
+/* the header of a float32 single-file .nii: qform / sform codes and parameters as given (codes 0: not written) */
+static int write_f32_hdr(const char *path, const float *data, int nx, int ny, int nz, const float pixdim4[4], int16_t qcode,
+                         const float *quatern6, int16_t scode, const float *srow, unsigned char xyzt_units)
 {
     unsigned char h[352];
     memset(h, 0, sizeof(h));
@@ -421,21 +422,18 @@ int nifti_min_write_f32_ex(const char *path, const float *data, int nx, int ny, 
     int16_t dt = 16, bp = 32;
     memcpy(h + 70, &dt, 2);
     memcpy(h + 72, &bp, 2);
-    float pixdim[8] = {1.0f, dx, dy, dz, 1.0f, 1.0f, 1.0f, 1.0f};
+    float pixdim[8] = {pixdim4[0], pixdim4[1], pixdim4[2], pixdim4[3], 1.0f, 1.0f, 1.0f, 1.0f};
     memcpy(h + 76, pixdim, 32);
     float vo = 352.0f, slope = 1.0f;
     memcpy(h + 108, &vo, 4);
     memcpy(h + 112, &slope, 4);
-    h[123] = 2; /* xyzt_units: mm */
-    if (q) {
-        int16_t code = 1;
-        memcpy(h + 252, &code, 2);
-        memcpy(h + 256, q, 24); /* quatern_b,c,d, qoffset_x,y,z */
-        memcpy(h + 76, q + 6, 4); /* pixdim[0] = qfac */
+    h[123] = xyzt_units;
+    if (qcode > 0) {
+        memcpy(h + 252, &qcode, 2);
+        memcpy(h + 256, quatern6, 24); /* quatern_b,c,d, qoffset_x,y,z */
     }
-    if (srow) {
-        int16_t code = 1;
-        memcpy(h + 254, &code, 2);
+    if (scode > 0) {
+        memcpy(h + 254, &scode, 2);
         memcpy(h + 280, srow, 48);
     }
     memcpy(h + 344, "n+1", 4);
@@ -458,6 +456,39 @@ int nifti_min_write_f32_ex(const char *path, const float *data, int nx, int ny, 
     int ok = fwrite(h, 1, 352, f) == 352 && fwrite(data, 1, n, f) == n;
     fclose(f);
     return ok ? 0 : -1;
+}
+
+int nifti_min_write_f32_ex(const char *path, const float *data, int nx, int ny, int nz, float dx, float dy, float dz,
+                           const float *q, const float *srow)
+{
+    const float pixdim[4] = {q ? q[6] : 1.0f, dx, dy, dz}; /* pixdim[0] = qfac */
+    return write_f32_hdr(path, data, nx, ny, nz, pixdim, q ? 1 : 0, q, srow ? 1 : 0, srow, 2 /* mm */);
+}
+
+int nifti_min_write_f32_geom(const char *path, const float *data, const char *geom_path)
+{
+    unsigned char h[348];
+    gzFile f = gzopen(geom_path, "rb");
+    if (!f) return -1;
+    const int got = gzread(f, h, 348);
+    gzclose(f);
+    if (got != 348) return -1;
+    int sw = 0;
+    if (rd32(h, 0, 0) != 348) {
+        sw = 1;
+        if (rd32(h, 0, 1) != 348) return -1;
+    }
+    const int ndim = rd16(h, 40, sw);
+    if (ndim < 1 || ndim > 7) return -1;
+    const int nx = rd16(h, 42, sw), ny = ndim >= 2 ? rd16(h, 44, sw) : 1, nz = ndim >= 3 ? rd16(h, 46, sw) : 1;
+    if (nx < 1 || ny < 1 || nz < 1) return -1;
+    const int is_nifti = (h[344] == 'n' && (h[345] == 'i' || h[345] == '+') && h[346] >= '1' && h[346] <= '9' && h[347] == 0);
+    float pixdim[4], quatern[6], srow[12];
+    for (int k = 0; k < 4; k++) pixdim[k] = rdf(h, 76 + 4 * k, sw);
+    for (int k = 0; k < 6; k++) quatern[k] = rdf(h, 256 + 4 * k, sw);
+    for (int k = 0; k < 12; k++) srow[k] = rdf(h, 280 + 4 * k, sw);
+    const int16_t qcode = is_nifti ? rd16(h, 252, sw) : 0, scode = is_nifti ? rd16(h, 254, sw) : 0;
+    return write_f32_hdr(path, data, nx, ny, nz, pixdim, qcode, quatern, scode, srow, is_nifti ? h[123] : 2);
 }
 
 void nifti_min_free(nifti_min_image *img)

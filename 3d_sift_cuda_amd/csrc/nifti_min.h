@@ -48,6 +48,10 @@ int nifti_min_write_f32(const char *path, const float *data, int nx, int ny, int
  * pass NULL to leave the corresponding code 0.  For tests of the -w / -ws options. */
 int nifti_min_write_f32_ex(const char *path, const float *data, int nx, int ny, int nz, float dx, float dy, float dz,
                            const float *quatern_bcd_xyz_qfac /* 7 floats */, const float *srow /* 12 floats */);
+/* A float32 single-file .nii (or .nii.gz) with the grid of the image at geom_path: its dims (data holds that many voxels),
+ * voxel sizes, qfac, qform and sform with their codes, and units -- what featResample writes, so that a viewer overlays
+ * the output on that image.  Returns 0 or -1. */
+int nifti_min_write_f32_geom(const char *path, const float *data, const char *geom_path);
 void nifti_min_free(nifti_min_image *img);
 
 #ifdef __cplusplus

@@ -34,8 +34,8 @@
  * INTEGRATION.md shows the reference-side edit for each.  Section index:
  * operator level; pipeline level; tuning; timing; Z-slab building blocks and
  * sift3d_extract_zslab (several GPUs, beyond the reference); host helpers
- * (.key, NIfTI, world coordinates); matcher.  Development hooks and the one
- * hardware self-test are in sift3d_dev.h, not here.
+ * (.key, NIfTI, world coordinates); matcher; resampling (featResample).
+ * Development hooks and the one hardware self-test are in sift3d_dev.h, not here.
  */
 #ifndef SIFT3D_H
 #define SIFT3D_H
@@ -541,6 +541,38 @@ int sift3d_write_similarity(const char *path, const sift3d_similarity *t);
  * t's arrays must hold its n_matches entries.  Returns 0 or -1. */
 int sift3d_write_alignment_matches(const char *base, const char *fixed_name, const char *moving_name, const sift3d_feature *fixed,
                                    int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving, const sift3d_similarity *t);
+
+/* ---- resampling: the moving image on the fixed image's grid (featResample; beyond the reference) ----------------------
+ * DESIGN.md section 7c states the arithmetic; tests/resample_oracle.c restates it.  Volumes are dense float32, x fastest.
+ * map: 3 x 4 row-major, output voxel index (i, j, k) -> source voxel position
+ *   q_r = ((map[4r] * i + map[4r + 1] * j) + map[4r + 2] * k) + map[4r + 3]  (i, j, k as floats, no fused multiply-add).
+ * A sample is taken where 0 <= q <= n - 1 on every axis (a NaN position fails); every other output voxel gets fill.
+ * Linear: trilinear over the eight corners, x then y then z, each step (1 - w) * a + w * b -- a NaN or infinite corner of
+ * weight 0 still reaches the result.  Nearest: the voxel min(floorf(q + 0.5f), n - 1).  Source extents 1 .. 2^24, output
+ * extents 1 .. 2^31 - 1 with at most 2^40 voxels; 64-bit indices throughout. */
+typedef enum { SIFT3D_INTERP_LINEAR = 0, SIFT3D_INTERP_NEAREST = 1 } sift3d_interp;
+/* Host arrays in and out, on `device`.  *kernel_ms (may be NULL): device time of the resampling kernel. */
+int sift3d_resample_affine(int device, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
+                           int64_t oz, const float map[12], int interp, float fill, double *kernel_ms, char *err, int64_t err_len);
+/* Device buffers, on the context's stream and ordered like every other *_dev entry point (any context, a slab one too). */
+int sift3d_resample_affine_dev(sift3d_ctx *ctx, const float *d_src, int64_t nx, int64_t ny, int64_t nz, float *d_dst, int64_t ox,
+                               int64_t oy, int64_t oz, const float map[12], int interp, float fill);
+/* Host helpers (also in libsift3d_host.so).  The 4 x 4 row-major matrix WriteMatrix prints for t, before its %f rounding:
+ * x_fixed_key = m . x_moving_key. */
+void sift3d_similarity_matrix(const sift3d_similarity *t, float m[16]);
+/* Parses a .trans.txt (sixteen numbers, nothing after them).  Returns 0, or -1 when the file cannot be read, holds
+ * another count of numbers, or its last row is not 0 0 0 1. */
+int sift3d_read_similarity(const char *path, float m[16]);
+/* The map of sift3d_resample_affine that puts the moving image on the fixed grid: A = inv(moving_vox2key) .
+ * inv(moving_to_fixed) . fixed_vox2key, in double, rounded to float once.  vox2key: voxel index -> key coordinates (the
+ * identity for keys in voxel units; qto_xyz / sto_xyz of the image for featExtract -w / -ws); NULL means identity.
+ * Returns 0, or -1 when a matrix's last row is not 0 0 0 1 or a matrix is singular. */
+int sift3d_resample_map(const float moving_to_fixed[16], const float fixed_vox2key[16], const float moving_vox2key[16], float map[12]);
+/* vox2key of an image whose keys featExtract wrote: the records of a blob centred on voxel x sit at x + 0.5 (voxel units,
+ * world == NULL), or at world . (x + 0.5 f) under -w / -ws, world = that image's qto_xyz / sto_xyz (row-major 4 x 4) and
+ * f = min(voxel) / voxel per axis (the isotropic resampling of -w).  voxel: the image's voxel sizes (used with world only).
+ * Keys of -2+ / -2- extractions follow neither form. */
+void sift3d_key_vox2key(const float voxel[3], const float world[16], float m[16]);
 
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
