@@ -168,6 +168,8 @@ def hip_lib():
     _sig(L.sift3d_get_level_slice, I, P, I, I, I64, P, P, P)
     _sig(L.sift3d_resample_affine, I, I, P, I64, I64, I64, P, I64, I64, I64, P, I, F, P, C.c_char_p, I64)
     _sig(L.sift3d_resample_affine_dev, I, P, P, I64, I64, I64, P, I64, I64, I64, P, I, F)
+    _sig(L.sift3d_guided_search_params, I, I, P, I64, P, I64, P, F, P, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_refine_similarity, I, I, P, I64, P, I64, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -206,6 +208,8 @@ def host_lib():
     _sig(L.sift3d_read_similarity, I, C.c_char_p, P)
     _sig(L.sift3d_resample_map, I, P, P, P, P)
     _sig(L.sift3d_key_vox2key, None, P, P, P)
+    _sig(L.sift3d_fit_similarity, I, P, P, I64, P)
+    _sig(L.sift3d_refine_defaults, None, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -507,6 +511,97 @@ def write_alignment_matches(base, fixed_name, moving_name, fixed, moving, d):
     if host_lib().sift3d_write_alignment_matches(os.fsencode(base), os.fsencode(fixed_name), os.fsencode(moving_name), f.ctypes.data, len(f),
                                                  m.ctypes.data, len(m), C.byref(t)) != 0:
         raise Sift3DError("could not write the match files of %s" % base)
+
+
+# ---- guided re-matching (featMatchMultiple -a -e), DESIGN.md section 7d ---------------------------------------------------
+class RefineParams(C.Structure):
+    """sift3d_refine_params"""
+    _fields_ = [("max_rounds", C.c_int32), ("min_radius", C.c_float), ("max_radius", C.c_float), ("ratio_num", C.c_int32),
+                ("ratio_den", C.c_int32), ("stop_shift", C.c_float), ("index_cells_max", C.c_int64)]
+
+
+REFINE_MAX_ROUNDS = 16
+REFINE_STOPS = ("rounds", "converged", "fit", "none")   # sift3d_refine_stop
+
+
+class RefineRound(C.Structure):
+    _fields_ = [("radius", C.c_float), ("visited", C.c_int64), ("accepted", C.c_int32), ("kept", C.c_int32), ("rms", C.c_double),
+                ("shift", C.c_double), ("kernel_ms", C.c_double)]
+
+
+class RefineReport(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("stop", C.c_int32), ("round", RefineRound * REFINE_MAX_ROUNDS)]
+
+
+def refine_params(**kw):
+    """sift3d_refine_defaults, then the given fields (max_rounds, min_radius, max_radius, ratio_num, ratio_den, stop_shift,
+    index_cells_max)."""
+    p = RefineParams()
+    host_lib().sift3d_refine_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(RefineParams._fields_):
+            raise ValueError("no refine parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def guided_search(fixed, moving, t, radius, device=0, index_cells_max=None):
+    """sift3d_guided_search: for every moving record the best and second-best fixed records near its prediction under t (a
+    match_keys-style dict), ordered by (squared descriptor distance, fixed index).  Returns (i1, d1, i2, d2, visited,
+    kernel_ms); -1 / INT32_MAX where there is no candidate.  index_cells_max: the index form (1 forces sorted cell keys)."""
+    f = np.ascontiguousarray(fixed, FEATURE_DTYPE)
+    m = np.ascontiguousarray(moving, FEATURE_DTYPE)
+    st, _keep = _similarity_struct(t)
+    p = refine_params() if index_cells_max is None else refine_params(index_cells_max=int(index_cells_max))
+    out = [np.empty(len(m), np.int32) for _ in range(5)]
+    ms, err = C.c_double(0.0), C.create_string_buffer(256)
+    rc = hip_lib().sift3d_guided_search_params(int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), C.byref(st), float(radius), C.byref(p),
+                                               *[o.ctypes.data for o in out], C.byref(ms), err, 256)
+    if rc != 0:
+        _raise("sift3d_guided_search", rc, err)
+    return tuple(out) + (ms.value,)
+
+
+def fit_similarity(p_moving, p_fixed, center0=(0.0, 0.0, 0.0)):
+    """sift3d_fit_similarity: the least-squares similarity p_moving -> p_fixed (n x 3 each, n >= 3, not collinear).  Returns a
+    dict scale, rot (3 x 3), trans, center0, center1 (the fit applied to center0), or None where the fit is refused."""
+    a = np.ascontiguousarray(p_moving, np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(p_fixed, np.float32).reshape(-1, 3)
+    if len(a) != len(b):
+        raise ValueError("p_moving and p_fixed differ in length")
+    t = Similarity()
+    t.center0[:] = [float(v) for v in np.asarray(center0, np.float32).reshape(3)]
+    if host_lib().sift3d_fit_similarity(a.ctypes.data, b.ctypes.data, len(a), C.byref(t)) != 0:
+        return None
+    return {"scale": np.float32(t.scale), "rot": np.array(t.rot, np.float32).reshape(3, 3), "trans": np.array(t.trans, np.float32),
+            "center0": np.array(t.center0, np.float32), "center1": np.array(t.center1, np.float32)}
+
+
+def _report_dict(r):
+    rounds = [{"radius": np.float32(x.radius), "visited": int(x.visited), "accepted": int(x.accepted), "kept": int(x.kept), "rms": float(x.rms),
+               "shift": float(x.shift), "kernel_ms": float(x.kernel_ms)} for x in r.round[:r.rounds]]
+    return {"rounds": int(r.rounds), "stop": REFINE_STOPS[r.stop], "round": rounds}
+
+
+def refine_similarity(fixed, moving, init, device=0, **params):
+    """sift3d_refine_similarity: the guided re-matching loop from init (match_keys' dict, arrays included).  params: fields of
+    sift3d_refine_params.  Returns (dict like match_keys' with the kept pairs as matches, report dict)."""
+    f = np.ascontiguousarray(fixed, FEATURE_DTYPE)
+    m = np.ascontiguousarray(moving, FEATURE_DTYPE)
+    st, _keep = _similarity_struct(init)
+    p = refine_params(**params)
+    cap = max(1, len(m), int(init.get("n_matches", 0)))
+    arrays = {k: np.zeros(cap, np.int32) for k in ("moving_idx", "fixed_idx", "inlier", "dist2")}
+    t = Similarity()
+    t.capacity = cap
+    for k, a in arrays.items():
+        setattr(t, k, a.ctypes.data)
+    rep, err = RefineReport(), C.create_string_buffer(256)
+    rc = hip_lib().sift3d_refine_similarity(int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), C.byref(st), C.byref(p), C.byref(t),
+                                            C.byref(rep), err, 256)
+    if rc != 0:
+        _raise("sift3d_refine_similarity", rc, err)
+    return _similarity_dict(t, arrays), _report_dict(rep)
 
 
 # ---- resampling (featResample), DESIGN.md section 7c ----------------------------------------------------------------------

@@ -17,6 +17,10 @@
  * :297-358 are written beside each moving key file: .matches.info.txt, .matches.img1.txt, .matches.img2.txt, .trans.txt,
  * .trans-inverse.txt, .update.key; stdout gets one "inliers" line per moving image.  -s2 runs three passes (all records,
  * peaks, valleys), each overwriting the files, as :640-644 does.
+ * -a -e adds the expanded matching the reference names and leaves off (bExpandedMatching, :148-390):
+ * the Hough transform is refined by guided re-matching and least-squares fits (sift3d_refine_similarity).  The refined
+ * transform goes to .trans.txt / .trans-inverse.txt, the kept pairs to the three match files, their count to the
+ * "inliers" line's second field (the reference's iInliers2, 0 without -e), and one line per round to <moving>.refine.txt.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +38,7 @@ static void usage(void)
     printf("  <input keys 1, ...>: input key files, produced from featExtract.\n");
     printf("  <output transform>: output text file with linear transform from keys 2 -> keys 1.\n");
     printf("  -a: align keys 2, 3, ... to keys 1 (ratio matching + Hough similarity; default: all-to-all votes).\n");
+    printf("  -e: with -a, refine each alignment by guided re-matching and a least-squares similarity.\n");
 }
 
 typedef struct {
@@ -88,11 +93,48 @@ done:
     return rc;
 }
 
-/* one matchAllToOne pass (featMatchMultiple.cpp:148-390): image 0 fixed, every other image aligned to it */
-static int align_all(char **names, key_set *sets, int n_sets, int device)
+static const char *const STOP_NAMES[] = {"rounds", "converged", "fit refused", "nothing to refine"};
+
+/* -e: t refined in place (its arrays re-pointed at *pairs, n_moving entries each); one line per round to <name>.refine.txt */
+static int refine(const char *name, const key_set *fixed, const key_set *moving, sift3d_similarity *t, int32_t **pairs, int device)
+{
+    char err[256] = "";
+    const int64_t cap = moving->n > t->n_matches ? moving->n : t->n_matches;
+    int32_t *buf = (int32_t *)realloc(*pairs, sizeof(int32_t) * 4 * (size_t)(cap > 0 ? cap : 1));
+    if (!buf) return -1;
+    *pairs = buf;
+    sift3d_similarity r;
+    memset(&r, 0, sizeof r);
+    r.capacity = (int32_t)cap;
+    r.moving_idx = buf;
+    r.fixed_idx = buf + cap;
+    r.inlier = buf + 2 * cap;
+    r.dist2 = buf + 3 * cap;
+    sift3d_refine_report rep;
+    if (sift3d_refine_similarity(device, fixed->f, fixed->n, moving->f, moving->n, t, NULL, &r, &rep, err, sizeof err) != SIFT3D_OK) {
+        printf("Error: refinement of %s failed: %s\n", name, err);
+        return -1;
+    }
+    *t = r;
+    char *path = (char *)malloc(strlen(name) + 16);
+    if (!path) return -1;
+    sprintf(path, "%s.refine.txt", name);
+    FILE *f = fopen(path, "wt");
+    free(path);
+    if (!f) return -1;
+    fprintf(f, "# round radius visited accepted kept rms shift\n");
+    for (int k = 0; k < rep.rounds; k++)
+        fprintf(f, "%d\t%f\t%lld\t%d\t%d\t%f\t%f\n", k, rep.round[k].radius, (long long)rep.round[k].visited, rep.round[k].accepted, rep.round[k].kept,
+                rep.round[k].rms, rep.round[k].shift);
+    fprintf(f, "# stop: %s\n", STOP_NAMES[rep.stop >= 0 && rep.stop <= 3 ? rep.stop : 0]);
+    return fclose(f) == 0 ? 0 : -1;
+}
+
+/* one matchAllToOne pass (featMatchMultiple.cpp:148-390): image 0 fixed, every other image aligned to it (and refined: -e) */
+static int align_all(char **names, key_set *sets, int n_sets, int device, int expand)
 {
     enum { MAX_MATCHES = 3000 }; /* MatchKeys' iMaxMatches */
-    int32_t mi[MAX_MATCHES], fi[MAX_MATCHES], in[MAX_MATCHES], d2[MAX_MATCHES];
+    int32_t mi[MAX_MATCHES], fi[MAX_MATCHES], in[MAX_MATCHES], d2[MAX_MATCHES], *pairs = NULL;
     char err[256] = "", *path = NULL;
     for (int i = 1; i < n_sets; i++) {
         sift3d_similarity t, inv;
@@ -105,27 +147,43 @@ static int align_all(char **names, key_set *sets, int n_sets, int device)
         if (sift3d_match_keys(device, sets[0].f, sets[0].n, sets[i].f, sets[i].n, MAX_MATCHES, &t, err, sizeof err) != SIFT3D_OK) {
             printf("Error: alignment of %s failed: %s\n", names[i], err);
             free(path);
+            free(pairs);
             return -1;
         }
+        const int inliers_hough = t.inliers;
+        int refined = 0;
+        if (expand) {
+            if (refine(names[i], &sets[0], &sets[i], &t, &pairs, device) != 0) {
+                free(path);
+                free(pairs);
+                return -1;
+            }
+            refined = t.inliers;
+        }
         path = (char *)realloc(path, strlen(names[i]) + 32);
-        if (!path) return -1;
+        if (!path) {
+            free(pairs);
+            return -1;
+        }
         int rc = sift3d_write_alignment_matches(names[i], names[0], names[i], sets[0].f, sets[0].n, sets[i].f, sets[i].n, &t);
         sprintf(path, "%s.trans.txt", names[i]);
         if (rc == 0) rc = sift3d_write_similarity(path, &t);
         sift3d_similarity_invert(&t, &inv);
         sprintf(path, "%s.trans-inverse.txt", names[i]);
         if (rc == 0) rc = sift3d_write_similarity(path, &inv);
-        printf("%s: inliers %d\t%d\t%d\t%f\n", names[i], t.inliers, 0, 0, t.scale);
+        printf("%s: inliers %d\t%d\t%d\t%f\n", names[i], expand ? inliers_hough : t.inliers, refined, 0, t.scale);
         sprintf(path, "%s.update.key", names[i]);
         if (rc == 0) rc = sift3d_write_key(path, sets[i].f, sets[i].n, -1.0f, 0, NULL);
         if (rc != 0) {
             printf("Error: could not write the alignment files of %s\n", names[i]);
             free(path);
+            free(pairs);
             return -1;
         }
     }
     printf("\n");
     free(path);
+    free(pairs);
     return 0;
 }
 
@@ -145,7 +203,7 @@ int main(int argc, char **argv)
         fprintf(cf, "\n");
         fclose(cf);
     }
-    int a = 1, only_reoriented = 1, peaks_mode = 4, neighbours = 5, align = 0;
+    int a = 1, only_reoriented = 1, peaks_mode = 4, neighbours = 5, align = 0, expand = 0;
     const char *report = "report.txt", *list_file = NULL;
     while (a < argc && argv[a][0] == '-') {
         switch (argv[a][1]) {
@@ -171,6 +229,10 @@ int main(int argc, char **argv)
             align = 1;
             a++;
             break;
+        case 'e': case 'E':
+            expand = 1;
+            a++;
+            break;
         case 'f': case 'F':
             a++;
             if (a >= argc) { usage(); return -1; }
@@ -180,6 +242,10 @@ int main(int argc, char **argv)
             printf("Error: unknown command line argument: %s\n", argv[a]);
             return -1;
         }
+    }
+    if (expand && !align) {
+        printf("Error: -e refines an alignment and needs -a\n");
+        return -1;
     }
     if (neighbours < 1 || neighbours > 32) {
         printf("Error: the number of neighbours must be 1..32\n");
@@ -269,10 +335,10 @@ int main(int argc, char **argv)
     /* -s2: all three passes append to matching_votes.txt / vote_count.txt (featMatchMultiple.cpp:58-65: "at" whenever
      * bOnlyPeaksFeatures == 2, the first pass included) */
     if (align) {
-        int rc = align_all(names, sets, n_read, 0);
+        int rc = align_all(names, sets, n_read, 0, expand);
         if (rc == 0 && peaks_mode == 2) {
-            rc = align_all(names, peaks, n_read, 0);
-            if (rc == 0) rc = align_all(names, valleys, n_read, 0);
+            rc = align_all(names, peaks, n_read, 0, expand);
+            if (rc == 0) rc = align_all(names, valleys, n_read, 0, expand);
         }
         return rc == 0 ? 0 : -1;
     }

@@ -34,7 +34,7 @@
  * INTEGRATION.md shows the reference-side edit for each.  Section index:
  * operator level; pipeline level; tuning; timing; Z-slab building blocks and
  * sift3d_extract_zslab (several GPUs, beyond the reference); host helpers
- * (.key, NIfTI, world coordinates); matcher; resampling (featResample).
+ * (.key, NIfTI, world coordinates); matcher; guided re-matching (featMatchMultiple -a -e); resampling (featResample).
  * Development hooks and the one hardware self-test are in sift3d_dev.h, not here.
  */
 #ifndef SIFT3D_H
@@ -541,6 +541,80 @@ int sift3d_write_similarity(const char *path, const sift3d_similarity *t);
  * t's arrays must hold its n_matches entries.  Returns 0 or -1. */
 int sift3d_write_alignment_matches(const char *base, const char *fixed_name, const char *moving_name, const sift3d_feature *fixed,
                                    int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving, const sift3d_similarity *t);
+
+/* ---- guided re-matching: refine an alignment over many pairs (featMatchMultiple -a -e; beyond the reference) ----------
+ * The reference names this step (MatchKeys' bExpand, matchAllToOne's bExpandedMatching: "try to find some additional
+ * correspondences (inliers of inliers)") and always leaves it off.  DESIGN.md section 7d states the contract;
+ * tests/refine_oracle.c restates the search.
+ *
+ * sift3d_guided_search: for every moving record m the best and second-best fixed records f, ordered by (squared descriptor
+ * distance over the 64 rank components, fixed index), among those that pass, in float and in this order:
+ *   - the line flags are equal (AM_INFO_LINE of the info words);
+ *   - r = f.scale / (m.scale * t->scale) lies in the interval sift3d_log_ratio_interval(0.4054651) gives (NaN, 0 and
+ *     infinite ratios fail);
+ *   - with q = t->scale * t->rot (x_m - t->center0) + t->center1 (similarity_transform_3point's order), the squared distance
+ *     ((dx * dx + dy * dy) + dz * dz) from f to q is below radius * radius (a NaN position fails).
+ * i1 / d1, i2 / d2: n_moving entries each, -1 / INT32_MAX where there is no candidate.  visited (may be NULL): candidates
+ * the spatial index made the query examine.  The index is a uniform grid of cell edge radius * (1 + 2^-10) over the
+ * fixed records' finite bounding box, records with a non-finite position in no cell; it only skips records.  Descriptors
+ * as sift3d_match_descriptors takes them.  *kernel_ms (may be NULL): device time of the search kernel. */
+int sift3d_guided_search(int device, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving,
+                         const sift3d_similarity *t, float radius, int32_t *i1, int32_t *d1, int32_t *i2, int32_t *d2, int32_t *visited,
+                         double *kernel_ms, char *err, int64_t err_len);
+
+/* A least-squares similarity over n point pairs, p_moving -> p_fixed (3 floats each): Umeyama (1991) in double with
+ * det R = +1, the 3 x 3 SVD by one-sided Jacobi sweeps, rounded to float once.  Fills out->scale, rot, trans and center1 =
+ * the fit applied to out->center0 (the caller's), so am_sim_point and sift3d_similarity_matrix describe the same map;
+ * nothing else of *out is touched.  Returns 0, or -1 for fewer than 3 pairs, a non-finite coordinate, or centred points of
+ * rank < 2 (collinear). */
+int sift3d_fit_similarity(const float *p_moving, const float *p_fixed, int64_t n, sift3d_similarity *out);
+
+typedef struct {
+    int32_t max_rounds;     /* 3 */
+    float min_radius;       /* 1.0 key units */
+    float max_radius;       /* 16.0 */
+    int32_t ratio_num;      /* 4: accept when i2 == -1 or ratio_num * d2 > ratio_den * d1 (int64, squared distances) */
+    int32_t ratio_den;      /* 5 */
+    float stop_shift;       /* 0.01: stop when the moving box's eight corners move by less */
+    int64_t index_cells_max; /* 2^26: dense cell-start table up to this many cells, sorted cell keys above */
+} sift3d_refine_params;
+void sift3d_refine_defaults(sift3d_refine_params *p);
+/* sift3d_guided_search with the index form of p->index_cells_max (the only field it reads; NULL: defaults). */
+int sift3d_guided_search_params(int device, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving,
+                                const sift3d_similarity *t, float radius, const sift3d_refine_params *p, int32_t *i1, int32_t *d1, int32_t *i2,
+                                int32_t *d2, int32_t *visited, double *kernel_ms, char *err, int64_t err_len);
+
+#define SIFT3D_REFINE_MAX_ROUNDS 16
+typedef enum {
+    SIFT3D_REFINE_STOP_ROUNDS = 0,    /* max_rounds rounds ran */
+    SIFT3D_REFINE_STOP_CONVERGED = 1, /* the corners moved by less than stop_shift */
+    SIFT3D_REFINE_STOP_FIT = 2,       /* a fit was refused (too few or collinear pairs): the previous transform is kept */
+    SIFT3D_REFINE_STOP_NONE = 3       /* nothing to refine (no fixed or no moving record) */
+} sift3d_refine_stop;
+typedef struct {
+    float radius;      /* the search radius of the round */
+    int64_t visited;   /* candidates examined, summed over the queries */
+    int32_t accepted;  /* pairs accepted by the ratio test, one per fixed record */
+    int32_t kept;      /* pairs kept by the trim (0 when the round's fit was refused) */
+    double rms;        /* RMS residual of the kept pairs under the round's transform */
+    double shift;      /* largest move of the eight corners against the round before */
+    double kernel_ms;  /* device time of the round's search kernel */
+} sift3d_refine_round;
+typedef struct {
+    int32_t rounds;    /* rounds run (a refused round counts) */
+    int32_t stop;      /* sift3d_refine_stop */
+    sift3d_refine_round round[SIFT3D_REFINE_MAX_ROUNDS];
+} sift3d_refine_report;
+
+/* The refinement loop, every choice in double on the host: predict, search (the fixed set and its
+ * index stay on the device across rounds), accept by the ratio test, keep one pair per fixed record (least (d1, moving
+ * index)), fit, trim to residuals <= 3 x the lower median, refit.  init: sift3d_match_keys' result with its arrays (the
+ * Hough inliers set round 0's radius, 3 x their RMS residual clamped to [min_radius, max_radius]).  p NULL: defaults.
+ * out: scale / rot / trans / center0 / center1 of the refined map; its arrays (capacity n_moving) hold the kept pairs by
+ * moving index with inlier = 1, n_matches = inliers = their count, winner = -1.  rep (may be NULL): per round. */
+int sift3d_refine_similarity(int device, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving,
+                             const sift3d_similarity *init, const sift3d_refine_params *p, sift3d_similarity *out, sift3d_refine_report *rep,
+                             char *err, int64_t err_len);
 
 /* ---- resampling: the moving image on the fixed image's grid (featResample; beyond the reference) ----------------------
  * DESIGN.md section 7c states the arithmetic; tests/resample_oracle.c restates it.  Volumes are dense float32, x fastest.
