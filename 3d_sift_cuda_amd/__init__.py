@@ -363,13 +363,9 @@ def knn64(db, queries, k, device=0, repeats=1):
     assert db.ndim == 2 and db.shape[1] == 64 and queries.ndim == 2 and queries.shape[1] == 64
     idx = np.empty((len(queries), k), np.int32)
     d2 = np.empty((len(queries), k), np.int32)
-    ms, err = C.c_double(0.0), C.create_string_buffer(256)
-    rc = hip_lib().sift3d_knn64(int(device), db.ctypes.data, len(db), queries.ctypes.data, len(queries), int(k), idx.ctypes.data,
-                                d2.ctypes.data, int(repeats), C.byref(ms), err, 256)
-    if rc != 0:
-        e = Sift3DError("sift3d_knn64 -> %d: %s" % (rc, err.value.decode(errors="replace")))
-        e.code = rc
-        raise e
+    ms = C.c_double(0.0)
+    _call("sift3d_knn64", int(device), db.ctypes.data, len(db), queries.ctypes.data, len(queries), int(k), idx.ctypes.data, d2.ctypes.data,
+          int(repeats), C.byref(ms))
     return idx, d2, ms.value
 
 
@@ -397,10 +393,28 @@ class Similarity(C.Structure):
                 ("dist2", C.c_void_p)]
 
 
-def _raise(name, rc, err):
-    e = Sift3DError("%s -> %d: %s" % (name, rc, err.value.decode(errors="replace")))
-    e.code = rc
-    raise e
+_PAIRS = ("moving_idx", "fixed_idx", "inlier", "dist2")   # the per-match arrays of sift3d_similarity
+
+
+def _call(entry, *args, name=None):
+    """libsift3d_hip.so's host-array entry point `entry` on args and an error buffer; where it returns nonzero, raises
+    Sift3DError "<name> -> <code>: <the library's message>" (name: entry by default) with the code in .code."""
+    err = C.create_string_buffer(512)
+    rc = getattr(hip_lib(), entry)(*args, err, len(err))
+    if rc != 0:
+        e = Sift3DError("%s -> %d: %s" % (name or entry, rc, err.value.decode(errors="replace")))
+        e.code = rc
+        raise e
+
+
+def _similarity_out(cap):
+    """a Similarity with room for cap matches: (struct, {name: the int32 array it points to})"""
+    arrays = {k: np.zeros(cap, np.int32) for k in _PAIRS}
+    t = Similarity()
+    t.capacity = cap
+    for k, a in arrays.items():
+        setattr(t, k, a.ctypes.data)
+    return t, arrays
 
 
 def match_ratio(db_feats, q_feats, device=0):
@@ -409,10 +423,8 @@ def match_ratio(db_feats, q_feats, device=0):
     db = np.ascontiguousarray(db_feats, FEATURE_DTYPE)
     q = np.ascontiguousarray(q_feats, FEATURE_DTYPE)
     out = [np.empty(len(q), np.int32) for _ in range(4)]
-    ms, err = C.c_double(0.0), C.create_string_buffer(256)
-    rc = hip_lib().sift3d_match_ratio(int(device), db.ctypes.data, len(db), q.ctypes.data, len(q), *[o.ctypes.data for o in out], C.byref(ms), err, 256)
-    if rc != 0:
-        _raise("sift3d_match_ratio", rc, err)
+    ms = C.c_double(0.0)
+    _call("sift3d_match_ratio", int(device), db.ctypes.data, len(db), q.ctypes.data, len(q), *[o.ctypes.data for o in out], C.byref(ms))
     return tuple(out) + (ms.value,)
 
 
@@ -425,11 +437,8 @@ def hough_similarity(p0, p1, s0, s1, o0, o1, device=0):
     assert arr[0].size == 3 * m and arr[1].size == 3 * m and arr[3].size == m and arr[4].size == 9 * m and arr[5].size == 9 * m
     counts, flags = np.empty(m, np.int32), np.empty(m, np.int32)
     rot, scale, winner = np.zeros(9, np.float32), C.c_float(0.0), C.c_int32(-1)
-    err = C.create_string_buffer(256)
-    rc = hip_lib().sift3d_hough_similarity(int(device), *[a.ctypes.data for a in arr], m, counts.ctypes.data, C.byref(winner), rot.ctypes.data,
-                                           C.byref(scale), flags.ctypes.data, err, 256)
-    if rc != 0:
-        _raise("sift3d_hough_similarity", rc, err)
+    _call("sift3d_hough_similarity", int(device), *[a.ctypes.data for a in arr], m, counts.ctypes.data, C.byref(winner), rot.ctypes.data,
+          C.byref(scale), flags.ctypes.data)
     return {"counts": counts, "winner": winner.value, "rot": rot.reshape(3, 3), "scale": np.float32(scale.value), "flags": flags}
 
 
@@ -453,7 +462,7 @@ def _similarity_struct(d):
     t.center1[:] = [float(v) for v in np.asarray(d.get("center1", np.zeros(3)), np.float32)]
     t.n_matches, t.inliers, t.winner = int(d.get("n_matches", 0)), int(d.get("inliers", 0)), int(d.get("winner", -1))
     keep = {}
-    for k in ("moving_idx", "fixed_idx", "inlier", "dist2"):
+    for k in _PAIRS:
         a = np.ascontiguousarray(d.get(k, np.zeros(0)), np.int32)
         keep[k] = a
         setattr(t, k, a.ctypes.data if len(a) else None)
@@ -467,16 +476,8 @@ def match_keys(fixed, moving, device=0, max_matches=3000):
     dist2.  x_fixed = scale * rot @ x_moving + trans."""
     f = np.ascontiguousarray(fixed, FEATURE_DTYPE)
     m = np.ascontiguousarray(moving, FEATURE_DTYPE)
-    cap = max(1, min(len(m), int(max_matches)))
-    arrays = {k: np.zeros(cap, np.int32) for k in ("moving_idx", "fixed_idx", "inlier", "dist2")}
-    t = Similarity()
-    t.capacity = cap
-    for k, a in arrays.items():
-        setattr(t, k, a.ctypes.data)
-    err = C.create_string_buffer(256)
-    rc = hip_lib().sift3d_match_keys(int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), int(max_matches), C.byref(t), err, 256)
-    if rc != 0:
-        _raise("sift3d_match_keys", rc, err)
+    t, arrays = _similarity_out(max(1, min(len(m), int(max_matches))))
+    _call("sift3d_match_keys", int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), int(max_matches), C.byref(t))
     return _similarity_dict(t, arrays)
 
 
@@ -554,11 +555,9 @@ def guided_search(fixed, moving, t, radius, device=0, index_cells_max=None):
     st, _keep = _similarity_struct(t)
     p = refine_params() if index_cells_max is None else refine_params(index_cells_max=int(index_cells_max))
     out = [np.empty(len(m), np.int32) for _ in range(5)]
-    ms, err = C.c_double(0.0), C.create_string_buffer(256)
-    rc = hip_lib().sift3d_guided_search_params(int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), C.byref(st), float(radius), C.byref(p),
-                                               *[o.ctypes.data for o in out], C.byref(ms), err, 256)
-    if rc != 0:
-        _raise("sift3d_guided_search", rc, err)
+    ms = C.c_double(0.0)
+    _call("sift3d_guided_search_params", int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), C.byref(st), float(radius), C.byref(p),
+          *[o.ctypes.data for o in out], C.byref(ms), name="sift3d_guided_search")
     return tuple(out) + (ms.value,)
 
 
@@ -590,17 +589,9 @@ def refine_similarity(fixed, moving, init, device=0, **params):
     m = np.ascontiguousarray(moving, FEATURE_DTYPE)
     st, _keep = _similarity_struct(init)
     p = refine_params(**params)
-    cap = max(1, len(m), int(init.get("n_matches", 0)))
-    arrays = {k: np.zeros(cap, np.int32) for k in ("moving_idx", "fixed_idx", "inlier", "dist2")}
-    t = Similarity()
-    t.capacity = cap
-    for k, a in arrays.items():
-        setattr(t, k, a.ctypes.data)
-    rep, err = RefineReport(), C.create_string_buffer(256)
-    rc = hip_lib().sift3d_refine_similarity(int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), C.byref(st), C.byref(p), C.byref(t),
-                                            C.byref(rep), err, 256)
-    if rc != 0:
-        _raise("sift3d_refine_similarity", rc, err)
+    t, arrays = _similarity_out(max(1, len(m), int(init.get("n_matches", 0))))
+    rep = RefineReport()
+    _call("sift3d_refine_similarity", int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), C.byref(st), C.byref(p), C.byref(t), C.byref(rep))
     return _similarity_dict(t, arrays), _report_dict(rep)
 
 
@@ -624,11 +615,9 @@ def resample_affine(vol, out_shape, map, interp="linear", fill=0.0, device=0, re
     oz, oy, ox = (int(d) for d in out_shape)
     out = np.empty((oz, oy, ox), np.float32)
     m = _map12(map)
-    ms, err = C.c_double(0.0), C.create_string_buffer(512)
-    rc = hip_lib().sift3d_resample_affine(int(device), v.ctypes.data, nx, ny, nz, out.ctypes.data, ox, oy, oz, m.ctypes.data,
-                                          INTERP[interp], float(fill), C.byref(ms), err, 512)
-    if rc != 0:
-        _raise("sift3d_resample_affine", rc, err)
+    ms = C.c_double(0.0)
+    _call("sift3d_resample_affine", int(device), v.ctypes.data, nx, ny, nz, out.ctypes.data, ox, oy, oz, m.ctypes.data, INTERP[interp],
+          float(fill), C.byref(ms))
     return (out, ms.value) if return_ms else out
 
 

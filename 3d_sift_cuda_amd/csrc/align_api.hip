@@ -7,51 +7,47 @@
  */
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
 
 #include "align_math.h"
+#include "device_call.h"
 #include "match.h"
-#include "sift3d_internal.h"
 
-hipError_t sift3d_launch_knn_norms(hipStream_t s, const signed char *v, int64_t n, int *norms, unsigned long long *stats);
-hipError_t sift3d_launch_ratio(hipStream_t s, const signed char *db, const int *db_norm, int64_t n_db, const signed char *q, const int *q_norm,
-                               int64_t n_q, const float *geo, const unsigned *info, float lo, float hi, int *i1, int *d1, int *i2, int *d2);
-hipError_t sift3d_launch_hough(hipStream_t s, const float *p0, const float *p1, const float *s0, const float *s1, const float *o0, const float *o1,
-                               int M, float lo, float hi, int one, int *counts, int *flags, float *hyp);
-
-#define ACHK(call)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) {                                                                          \
-            if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s failed: %s", #call, hipGetErrorString(e_)); \
-            rc = SIFT3D_ERR_DEVICE;                                                                      \
-            goto done;                                                                                   \
-        }                                                                                                \
-    } while (0)
-
-/* the ratio intervals of the two scale thresholds, computed once from the host's logf */
 static std::once_flag g_iv_once;
-static int g_iv_ok = 0;
-static float g_iv_lo[2], g_iv_hi[2]; /* [0]: LOG_1_5 (ratio search), [1]: HOUGH_THRES_SCALE */
+static sift3d_scale_intervals g_iv;
 
-static int intervals(char *err, int64_t err_len)
+const sift3d_scale_intervals &sift3d_scale_ivs()
 {
     std::call_once(g_iv_once, [] {
-        g_iv_ok = sift3d_log_ratio_interval(AM_LOG_1_5, &g_iv_lo[0], &g_iv_hi[0]) == 0 &&
-                  sift3d_log_ratio_interval(AM_HOUGH_SCALE, &g_iv_lo[1], &g_iv_hi[1]) == 0;
+        g_iv.ok[0] = sift3d_log_ratio_interval(AM_LOG_1_5, &g_iv.lo[0], &g_iv.hi[0]) == 0;
+        g_iv.ok[1] = sift3d_log_ratio_interval(AM_HOUGH_SCALE, &g_iv.lo[1], &g_iv.hi[1]) == 0;
     });
-    if (!g_iv_ok && err && err_len > 0) snprintf(err, (size_t)err_len, "this host's logf is not monotonic near the scale thresholds");
-    return g_iv_ok ? SIFT3D_OK : SIFT3D_ERR_DEVICE;
+    return g_iv;
 }
 
-static int bad_arg(char *err, int64_t err_len, const char *what)
+int sift3d_put_pairs(sift3d_similarity *out, int32_t n, const int32_t *moving, const int32_t *fixed, const int32_t *inlier, const int32_t *dist2,
+                     const char *what, char *err, int64_t err_len)
 {
-    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", what);
-    return SIFT3D_ERR_ARG;
+    if (out->capacity < n)
+        return call_fail(err, err_len, out->capacity > 0 || out->moving_idx ? SIFT3D_ERR_CAPACITY : SIFT3D_OK, "%d %s, arrays for %d", n, what,
+                         out->capacity);
+    for (int32_t k = 0; k < n; k++) {
+        if (out->moving_idx) out->moving_idx[k] = moving[k];
+        if (out->fixed_idx) out->fixed_idx[k] = fixed[k];
+        if (out->inlier) out->inlier[k] = inlier[k];
+        if (out->dist2) out->dist2[k] = dist2[k];
+    }
+    return SIFT3D_OK;
+}
+
+/* both scale intervals, or SIFT3D_ERR_DEVICE */
+static int intervals(char *err, int64_t err_len)
+{
+    const sift3d_scale_intervals &iv = sift3d_scale_ivs();
+    if (iv.ok[0] && iv.ok[1]) return SIFT3D_OK;
+    return call_fail(err, err_len, SIFT3D_ERR_DEVICE, "this host's logf is not monotonic near the scale thresholds");
 }
 
 /* the ratio search into host arrays (n_db >= 2, n_q >= 1) */
@@ -61,8 +57,8 @@ static int ratio_search(int device, const sift3d_feature *db, int64_t n_db, cons
     int rc = intervals(err, err_len);
     if (rc != SIFT3D_OK) return rc;
     std::vector<int8_t> bdb((size_t)n_db * SIFT3D_DESC_LEN), bq((size_t)n_q * SIFT3D_DESC_LEN);
-    if (sift3d_match_descriptors(db, n_db, bdb.data()) != 0) return bad_arg(err, err_len, "a database descriptor value is outside 0..127");
-    if (sift3d_match_descriptors(q, n_q, bq.data()) != 0) return bad_arg(err, err_len, "a query descriptor value is outside 0..127");
+    if (sift3d_match_descriptors(db, n_db, bdb.data()) != 0) return call_fail(err, err_len, SIFT3D_ERR_ARG, "a database descriptor value is outside 0..127");
+    if (sift3d_match_descriptors(q, n_q, bq.data()) != 0) return call_fail(err, err_len, SIFT3D_ERR_ARG, "a query descriptor value is outside 0..127");
     std::vector<float> geo((size_t)n_db * 13);
     std::vector<unsigned> info((size_t)n_db);
     for (int64_t j = 0; j < n_db; j++) {
@@ -73,54 +69,38 @@ static int ratio_search(int device, const sift3d_feature *db, int64_t n_db, cons
         for (int k = 0; k < 9; k++) geo[(4 + k) * n_db + j] = db[j].ori[k];
         info[j] = db[j].info;
     }
-    signed char *d_db = nullptr, *d_q = nullptr;
-    int *d_dbn = nullptr, *d_qn = nullptr, *d_out = nullptr;
-    float *d_geo = nullptr;
-    unsigned *d_info = nullptr;
-    unsigned long long *d_stats = nullptr, stats[6];
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ACHK(hipSetDevice(device));
-    ACHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    ACHK(hipEventCreate(&e0));
-    ACHK(hipEventCreate(&e1));
-    ACHK(hipMalloc((void **)&d_db, (size_t)n_db * 64));
-    ACHK(hipMalloc((void **)&d_q, (size_t)n_q * 64));
-    ACHK(hipMalloc((void **)&d_dbn, sizeof(int) * (size_t)n_db));
-    ACHK(hipMalloc((void **)&d_qn, sizeof(int) * (size_t)n_q));
-    ACHK(hipMalloc((void **)&d_out, sizeof(int) * (size_t)n_q * 4));
-    ACHK(hipMalloc((void **)&d_geo, sizeof(float) * geo.size()));
-    ACHK(hipMalloc((void **)&d_info, sizeof(unsigned) * info.size()));
-    ACHK(hipMalloc((void **)&d_stats, sizeof(stats)));
-    ACHK(hipMemcpyAsync(d_db, bdb.data(), bdb.size(), hipMemcpyHostToDevice, s));
-    ACHK(hipMemcpyAsync(d_q, bq.data(), bq.size(), hipMemcpyHostToDevice, s));
-    ACHK(hipMemcpyAsync(d_geo, geo.data(), sizeof(float) * geo.size(), hipMemcpyHostToDevice, s));
-    ACHK(hipMemcpyAsync(d_info, info.data(), sizeof(unsigned) * info.size(), hipMemcpyHostToDevice, s));
+    device_call dc(err, err_len);
+    signed char *d_db, *d_q;
+    int *d_dbn, *d_qn, *d_out;
+    float *d_geo;
+    unsigned *d_info;
+    unsigned long long *d_stats, stats[6];
+    DEVCHK(dc, dc.open(device));
+    DEVCHK(dc, dc.upload(&d_db, bdb.data(), bdb.size()));
+    DEVCHK(dc, dc.upload(&d_q, bq.data(), bq.size()));
+    DEVCHK(dc, dc.alloc(&d_dbn, (size_t)n_db));
+    DEVCHK(dc, dc.alloc(&d_qn, (size_t)n_q));
+    DEVCHK(dc, dc.alloc(&d_out, (size_t)n_q * 4));
+    DEVCHK(dc, dc.upload(&d_geo, geo.data(), geo.size()));
+    DEVCHK(dc, dc.upload(&d_info, info.data(), info.size()));
+    /* the norms kernel writes its verdict on the bytes into stats; nothing reads it here (sift3d_match_descriptors checked them) */
     stats[0] = stats[1] = stats[3] = stats[4] = ~0ull;
     stats[2] = stats[5] = 0;
-    ACHK(hipMemcpyAsync(d_stats, stats, sizeof(stats), hipMemcpyHostToDevice, s));
-    ACHK(sift3d_launch_knn_norms(s, d_db, n_db, d_dbn, d_stats));
-    ACHK(sift3d_launch_knn_norms(s, d_q, n_q, d_qn, d_stats + 3));
-    ACHK(hipEventRecord(e0, s));
-    ACHK(sift3d_launch_ratio(s, d_db, d_dbn, n_db, d_q, d_qn, n_q, d_geo, d_info, g_iv_lo[0], g_iv_hi[0], d_out, d_out + n_q, d_out + 2 * n_q,
-                             d_out + 3 * n_q));
-    ACHK(hipEventRecord(e1, s));
-    ACHK(hipMemcpyAsync(i1, d_out, sizeof(int) * (size_t)n_q, hipMemcpyDeviceToHost, s));
-    ACHK(hipMemcpyAsync(d1, d_out + n_q, sizeof(int) * (size_t)n_q, hipMemcpyDeviceToHost, s));
-    ACHK(hipMemcpyAsync(i2, d_out + 2 * n_q, sizeof(int) * (size_t)n_q, hipMemcpyDeviceToHost, s));
-    ACHK(hipMemcpyAsync(d2, d_out + 3 * n_q, sizeof(int) * (size_t)n_q, hipMemcpyDeviceToHost, s));
-    ACHK(hipStreamSynchronize(s));
-    if (kernel_ms) {
-        float ms = 0;
-        ACHK(hipEventElapsedTime(&ms, e0, e1));
-        *kernel_ms = ms;
-    }
-done:
-    hipFree(d_db); hipFree(d_q); hipFree(d_dbn); hipFree(d_qn); hipFree(d_out); hipFree(d_geo); hipFree(d_info); hipFree(d_stats);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (s) hipStreamDestroy(s);
-    return rc;
+    DEVCHK(dc, dc.upload(&d_stats, stats, 6));
+    DEVCHK(dc, sift3d_launch_knn_norms(dc.s, d_db, n_db, d_dbn, d_stats));
+    DEVCHK(dc, sift3d_launch_knn_norms(dc.s, d_q, n_q, d_qn, d_stats + 3));
+    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    const sift3d_scale_intervals &iv = sift3d_scale_ivs();
+    DEVCHK(dc, sift3d_launch_ratio(dc.s, d_db, d_dbn, n_db, d_q, d_qn, n_q, d_geo, d_info, iv.lo[0], iv.hi[0], d_out, d_out + n_q, d_out + 2 * n_q,
+                                   d_out + 3 * n_q));
+    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.download(i1, d_out, (size_t)n_q));
+    DEVCHK(dc, dc.download(d1, d_out + n_q, (size_t)n_q));
+    DEVCHK(dc, dc.download(i2, d_out + 2 * n_q, (size_t)n_q));
+    DEVCHK(dc, dc.download(d2, d_out + 3 * n_q, (size_t)n_q));
+    DEVCHK(dc, dc.sync());
+    DEVCHK(dc, dc.elapsed_ms(kernel_ms));
+    return SIFT3D_OK;
 }
 
 extern "C" int sift3d_match_ratio(int device, const sift3d_feature *db, int64_t n_db, const sift3d_feature *q, int64_t n_q, int32_t *i1,
@@ -130,7 +110,7 @@ extern "C" int sift3d_match_ratio(int device, const sift3d_feature *db, int64_t 
     if (kernel_ms) *kernel_ms = 0.0;
     /* 32-bit row indices, the last tile padded to a whole one (as sift3d_knn64) */
     if (!db || !q || !i1 || !d1 || !i2 || !d2 || n_db < 2 || n_q < 1 || n_db > (1ll << 31) - 4096 || n_q > (1ll << 31) - 4096)
-        return bad_arg(err, err_len, "bad arguments (2 <= n_db, 1 <= n_q, both at most 2^31 - 4096)");
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "bad arguments (2 <= n_db, 1 <= n_q, both at most 2^31 - 4096)");
     return ratio_search(device, db, n_db, q, n_q, i1, d1, i2, d2, kernel_ms, err, err_len);
 }
 
@@ -140,30 +120,28 @@ static int hough(int device, const float *p0, const float *p1, const float *s0, 
 {
     int rc = intervals(err, err_len);
     if (rc != SIFT3D_OK) return rc;
-    float *d_in = nullptr, *d_hyp = nullptr;
-    int *d_counts = nullptr, *d_flags = nullptr;
-    hipStream_t s = nullptr;
+    const float lo = sift3d_scale_ivs().lo[1], hi = sift3d_scale_ivs().hi[1];
     const float *src[6] = {p0, p1, s0, s1, o0, o1};
     const size_t width[6] = {3, 3, 1, 1, 9, 9};
-    float *dev[6];
+    device_call dc(err, err_len);
+    float *d_in, *d_hyp, *dev[6], hyp[10];
+    int *d_counts, *d_flags;
     size_t off = 0;
-    float hyp[10];
     int w = -1, best = 0;
     *winner = -1;
-    ACHK(hipSetDevice(device));
-    ACHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    ACHK(hipMalloc((void **)&d_in, sizeof(float) * (size_t)M * 26));
-    ACHK(hipMalloc((void **)&d_counts, sizeof(int) * (size_t)M));
-    ACHK(hipMalloc((void **)&d_flags, sizeof(int) * (size_t)M));
-    ACHK(hipMalloc((void **)&d_hyp, sizeof(float) * 10));
+    DEVCHK(dc, dc.open(device, false));
+    DEVCHK(dc, dc.alloc(&d_in, (size_t)M * 26));
+    DEVCHK(dc, dc.alloc(&d_counts, (size_t)M));
+    DEVCHK(dc, dc.alloc(&d_flags, (size_t)M));
+    DEVCHK(dc, dc.alloc(&d_hyp, 10));
     for (int a = 0; a < 6; a++) {
         dev[a] = d_in + off;
-        ACHK(hipMemcpyAsync(dev[a], src[a], sizeof(float) * width[a] * (size_t)M, hipMemcpyHostToDevice, s));
+        DEVCHK(dc, dc.to_device(dev[a], src[a], width[a] * (size_t)M));
         off += width[a] * (size_t)M;
     }
-    ACHK(sift3d_launch_hough(s, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], M, g_iv_lo[1], g_iv_hi[1], -1, d_counts, nullptr, nullptr));
-    ACHK(hipMemcpyAsync(counts_h, d_counts, sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, s));
-    ACHK(hipStreamSynchronize(s));
+    DEVCHK(dc, sift3d_launch_hough(dc.s, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], M, lo, hi, -1, d_counts, nullptr, nullptr));
+    DEVCHK(dc, dc.download(counts_h, d_counts, (size_t)M));
+    DEVCHK(dc, dc.sync());
     for (int i = 0; i < M; i++) /* fInlierProb > fMaxInlierProb: the first of the most, at least one */
         if (counts_h[i] > best) {
             best = counts_h[i];
@@ -172,27 +150,19 @@ static int hough(int device, const float *p0, const float *p1, const float *s0, 
     if (w < 0) {
         if (flags)
             for (int j = 0; j < M; j++) flags[j] = 0;
-        goto done;
+        return SIFT3D_OK;
     }
-    ACHK(sift3d_launch_hough(s, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], M, g_iv_lo[1], g_iv_hi[1], w, d_counts, d_flags, d_hyp));
-    if (flags) ACHK(hipMemcpyAsync(flags, d_flags, sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, s));
-    ACHK(hipMemcpyAsync(hyp, d_hyp, sizeof hyp, hipMemcpyDeviceToHost, s));
-    ACHK(hipStreamSynchronize(s));
-    {
-        float hrot[9], hs = 0;
-        if (am_hough_hypothesis(p0, p1, s0, s1, o0, o1, w, hrot, &hs) != 0 || memcmp(hrot, hyp, sizeof hrot) != 0 || memcmp(&hs, hyp + 9, sizeof hs) != 0) {
-            if (err && err_len > 0) snprintf(err, (size_t)err_len, "the device's transform of hypothesis %d differs from the host's", w);
-            rc = SIFT3D_ERR_DEVICE;
-            goto done;
-        }
-        memcpy(rot, hrot, sizeof hrot);
-        *scale = hs;
-        *winner = w;
-    }
-done:
-    hipFree(d_in); hipFree(d_counts); hipFree(d_flags); hipFree(d_hyp);
-    if (s) hipStreamDestroy(s);
-    return rc;
+    DEVCHK(dc, sift3d_launch_hough(dc.s, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], M, lo, hi, w, d_counts, d_flags, d_hyp));
+    if (flags) DEVCHK(dc, dc.download(flags, d_flags, (size_t)M));
+    DEVCHK(dc, dc.download(hyp, d_hyp, 10));
+    DEVCHK(dc, dc.sync());
+    float hrot[9], hs = 0;
+    if (am_hough_hypothesis(p0, p1, s0, s1, o0, o1, w, hrot, &hs) != 0 || memcmp(hrot, hyp, sizeof hrot) != 0 || memcmp(&hs, hyp + 9, sizeof hs) != 0)
+        return call_fail(err, err_len, SIFT3D_ERR_DEVICE, "the device's transform of hypothesis %d differs from the host's", w);
+    memcpy(rot, hrot, sizeof hrot);
+    *scale = hs;
+    *winner = w;
+    return SIFT3D_OK;
 }
 
 extern "C" int sift3d_hough_similarity(int device, const float *p0, const float *p1, const float *s0, const float *s1, const float *o0,
@@ -201,7 +171,7 @@ extern "C" int sift3d_hough_similarity(int device, const float *p0, const float 
 {
     if (err && err_len > 0) err[0] = 0;
     if (!p0 || !p1 || !s0 || !s1 || !o0 || !o1 || !winner || !rot || !scale || m < 1 || m > (1 << 24))
-        return bad_arg(err, err_len, "bad arguments (1 <= m <= 2^24)");
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "bad arguments (1 <= m <= 2^24)");
     std::vector<int32_t> c((size_t)m);
     const int rc = hough(device, p0, p1, s0, s1, o0, o1, m, c.data(), winner, rot, scale, flags, err, err_len);
     if (rc == SIFT3D_OK && counts) memcpy(counts, c.data(), sizeof(int32_t) * (size_t)m);
@@ -225,7 +195,7 @@ extern "C" int sift3d_match_keys(int device, const sift3d_feature *fixed, int64_
     if (err && err_len > 0) err[0] = 0;
     if (!out || (n_fixed > 0 && !fixed) || (n_moving > 0 && !moving) || n_fixed < 0 || n_moving < 0 || max_matches < 0 ||
         n_fixed > (1ll << 31) - 4096 || n_moving > (1ll << 31) - 4096)
-        return bad_arg(err, err_len, "bad arguments");
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "bad arguments");
     /* getMinMaxDim over the moving records: comparisons from record 0 on (a NaN coordinate never replaces an extreme) */
     for (int k = 0; k < 3; k++) out->center0[k] = 0;
     if (n_moving > 0) {
@@ -263,9 +233,11 @@ extern "C" int sift3d_match_keys(int device, const sift3d_feature *fixed, int64_
     const int M = (int)std::min<int64_t>(n_moving, max_matches);
     out->n_matches = M;
     std::vector<float> p0((size_t)M * 3), p1((size_t)M * 3), s0((size_t)M), s1((size_t)M), o0((size_t)M * 9), o1((size_t)M * 9);
-    std::vector<int32_t> flags((size_t)M, 0);
+    std::vector<int32_t> flags((size_t)M, 0), fixed_idx((size_t)M), dist2((size_t)M);
     for (int k = 0; k < M; k++) {
-        const sift3d_feature &a = moving[order[k]], &b = fixed[i1[order[k]]];
+        fixed_idx[k] = i1[order[k]];
+        dist2[k] = d1[order[k]];
+        const sift3d_feature &a = moving[order[k]], &b = fixed[fixed_idx[k]];
         p0[3 * k] = a.x; p0[3 * k + 1] = a.y; p0[3 * k + 2] = a.z;
         p1[3 * k] = b.x; p1[3 * k + 1] = b.y; p1[3 * k + 2] = b.z;
         s0[k] = a.scale;
@@ -291,15 +263,5 @@ extern "C" int sift3d_match_keys(int device, const sift3d_feature *fixed, int64_
             am_sim_point(zero, out->trans, out->center0, out->center1, rot, s);
         }
     }
-    if (out->capacity < M) {
-        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%d matches, arrays for %d", M, out->capacity);
-        return out->capacity > 0 || out->moving_idx ? SIFT3D_ERR_CAPACITY : SIFT3D_OK;
-    }
-    for (int k = 0; k < M; k++) {
-        if (out->moving_idx) out->moving_idx[k] = order[k];
-        if (out->fixed_idx) out->fixed_idx[k] = i1[order[k]];
-        if (out->inlier) out->inlier[k] = flags[k];
-        if (out->dist2) out->dist2[k] = d1[order[k]];
-    }
-    return SIFT3D_OK;
+    return sift3d_put_pairs(out, M, order.data(), fixed_idx.data(), flags.data(), dist2.data(), "matches", err, err_len);
 }

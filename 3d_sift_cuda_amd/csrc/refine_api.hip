@@ -5,35 +5,11 @@
  */
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "align_math.h"
-#include "sift3d_internal.h"
-
-hipError_t sift3d_launch_guided(hipStream_t s, const void *f_rows, const int *f_norm, const float *f_pos, const unsigned *f_info, const int *f_idx,
-                                int n_f, const int *cell_start, const long long *keys, const double grid_o[3], double edge, const long long grid_n[3],
-                                int dense, const void *m_rows, const float *m_pos, const unsigned *m_info, const int *order, int n_m,
-                                const float c0[3], const float c1[3], const float rot[9], float scale, float radius, float lo, float hi, int *i1,
-                                int *d1, int *i2, int *d2, int *visited);
-
-static int fail(char *err, int64_t err_len, int rc, const char *what)
-{
-    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", what);
-    return rc;
-}
-
-#define RCHK(call)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) {                                                                          \
-            if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s failed: %s", #call, hipGetErrorString(e_)); \
-            return SIFT3D_ERR_DEVICE;                                                                    \
-        }                                                                                                \
-    } while (0)
+#include "device_call.h"
 
 /* What the index and the loop read of a record set, compact: one pass over the 332-byte records converts the descriptors
  * (sift3d_match_descriptors' accepted set -- whole numbers 0..127 -- without its early exit, so the inner loop vectorises; NaN
@@ -81,6 +57,23 @@ struct RecordSet {
     bool finite(int64_t i) const { return std::isfinite(x(i)) && std::isfinite(y(i)) && std::isfinite(z(i)); }
 };
 
+/* the bounding box of a record set's finite records; false (and 0 .. 0) where there is none */
+static bool finite_box(const RecordSet &r, double mn[3], double mx[3])
+{
+    bool any = false;
+    for (int k = 0; k < 3; k++) mn[k] = mx[k] = 0;
+    for (int64_t i = 0; i < r.n; i++) {
+        if (!r.finite(i)) continue;
+        const double v[3] = {r.x(i), r.y(i), r.z(i)};
+        for (int k = 0; k < 3; k++) {
+            if (!any || v[k] < mn[k]) mn[k] = v[k];
+            if (!any || v[k] > mx[k]) mx[k] = v[k];
+        }
+        any = true;
+    }
+    return any;
+}
+
 /* A uniform grid over the finite bounding box of a record set: edge = radius (1 + 2^-10), widened to min_edge and where an
  * axis would get more than 2^20 cells (a wider cell only makes a query visit more records). */
 struct Grid {
@@ -89,17 +82,8 @@ struct Grid {
 
     void fit(const RecordSet &r, float radius, double min_edge)
     {
-        double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
-        bool any = false;
-        for (int64_t i = 0; i < r.n; i++) {
-            if (!r.finite(i)) continue;
-            const double v[3] = {r.x(i), r.y(i), r.z(i)};
-            for (int k = 0; k < 3; k++) {
-                if (!any || v[k] < mn[k]) mn[k] = v[k];
-                if (!any || v[k] > mx[k]) mx[k] = v[k];
-            }
-            any = true;
-        }
+        double mn[3], mx[3];
+        finite_box(r, mn, mx);
         edge = (double)radius * (1.0 + 1.0 / 1024.0);
         double ext = 0;
         for (int k = 0; k < 3; k++) ext = std::max(ext, mx[k] - mn[k]);
@@ -121,53 +105,28 @@ struct Grid {
     long long cells() const { return n[0] * n[1] * n[2]; }
 };
 
-/* the ratio interval of the scale test, computed once from the host's logf (as align_api.hip's) */
-static std::once_flag g_iv_once;
-static int g_iv_ok = 0;
-static float g_iv_lo, g_iv_hi;
-
-static int ratio_interval(float *lo, float *hi)
-{
-    std::call_once(g_iv_once, [] { g_iv_ok = sift3d_log_ratio_interval(AM_LOG_1_5, &g_iv_lo, &g_iv_hi) == 0; });
-    *lo = g_iv_lo;
-    *hi = g_iv_hi;
-    return g_iv_ok ? 0 : -1;
-}
-
 /* the fixed set on the device in cell order (rows in the callers' order, read through the original index), and the moving set
  * with its query order: built once per call */
 struct GuidedIndex {
-    int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float lo = 0, hi = 0;
+    device_call dc{nullptr, 0}; /* the stream, the events and the buffers, kept across the rounds of the loop; each call reports into its own err */
     Grid g;
     int dense = 1, n_f = 0, n_m = 0;
-    void *d_frows = nullptr, *d_mrows = nullptr;
+    int8_t *d_frows = nullptr, *d_mrows = nullptr;
     int *d_fnorm = nullptr, *d_fidx = nullptr, *d_cell = nullptr, *d_order = nullptr, *d_out = nullptr;
     float *d_fpos = nullptr, *d_mpos = nullptr;
     unsigned *d_finfo = nullptr, *d_minfo = nullptr;
     long long *d_keys = nullptr;
 
-    ~GuidedIndex()
-    {
-        hipFree(d_frows); hipFree(d_mrows); hipFree(d_fnorm); hipFree(d_fidx); hipFree(d_cell); hipFree(d_order); hipFree(d_out);
-        hipFree(d_fpos); hipFree(d_mpos); hipFree(d_finfo); hipFree(d_minfo); hipFree(d_keys);
-        if (e0) hipEventDestroy(e0);
-        if (e1) hipEventDestroy(e1);
-        if (s) hipStreamDestroy(s);
-    }
-
     RecordSet F, M; /* host copies in the callers' index order: the loop fits and measures residuals on them */
 
-    int build(int dev, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving, float max_radius,
+    int build(int device, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving, float max_radius,
               int64_t cells_max, char *err, int64_t err_len)
     {
-        device = dev;
-        if (ratio_interval(&lo, &hi) != 0)
-            return fail(err, err_len, SIFT3D_ERR_DEVICE, "this host's logf is not monotonic near the scale threshold");
-        if (F.load(fixed, n_fixed) != 0) return fail(err, err_len, SIFT3D_ERR_ARG, "a fixed descriptor value is outside 0..127");
-        if (M.load(moving, n_moving) != 0) return fail(err, err_len, SIFT3D_ERR_ARG, "a moving descriptor value is outside 0..127");
+        dc.err = err;
+        dc.err_len = err_len;
+        if (!sift3d_scale_ivs().ok[0]) return call_fail(err, err_len, SIFT3D_ERR_DEVICE, "this host's logf is not monotonic near the scale threshold");
+        if (F.load(fixed, n_fixed) != 0) return call_fail(err, err_len, SIFT3D_ERR_ARG, "a fixed descriptor value is outside 0..127");
+        if (M.load(moving, n_moving) != 0) return call_fail(err, err_len, SIFT3D_ERR_ARG, "a moving descriptor value is outside 0..127");
         /* fixed: counting sort of the finite records by cell (dense) or a sort by cell key (sorted form); ties keep index order */
         g.fit(F, max_radius, 0);
         const long long nc = g.cells();
@@ -219,37 +178,20 @@ struct GuidedIndex {
         for (long long c = 0; c <= mc; c++) mstart[c + 1] += mstart[c];
         for (int i = 0; i < n_m; i++) order[mstart[mkey[i]]++] = i;
         const size_t MS = M.stride();
-        RCHK(hipSetDevice(device));
-        RCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        RCHK(hipEventCreate(&e0));
-        RCHK(hipEventCreate(&e1));
-        RCHK(hipMalloc(&d_frows, fs * 64));
-        RCHK(hipMalloc((void **)&d_fnorm, FS * 4));
-        RCHK(hipMalloc((void **)&d_fidx, FS * 4));
-        RCHK(hipMalloc((void **)&d_fpos, FS * 16));
-        RCHK(hipMalloc((void **)&d_finfo, FS * 4));
-        RCHK(hipMalloc(&d_mrows, MS * 64));
-        RCHK(hipMalloc((void **)&d_mpos, MS * 16));
-        RCHK(hipMalloc((void **)&d_minfo, MS * 4));
-        RCHK(hipMalloc((void **)&d_order, MS * 4));
-        RCHK(hipMalloc((void **)&d_out, MS * 4 * 5));
-        RCHK(hipMemcpyAsync(d_frows, F.rows.data(), fs * 64, hipMemcpyHostToDevice, s));
-        RCHK(hipMemcpyAsync(d_fnorm, norm.data(), FS * 4, hipMemcpyHostToDevice, s));
-        RCHK(hipMemcpyAsync(d_fidx, idx.data(), FS * 4, hipMemcpyHostToDevice, s));
-        RCHK(hipMemcpyAsync(d_fpos, pos.data(), FS * 16, hipMemcpyHostToDevice, s));
-        RCHK(hipMemcpyAsync(d_finfo, info.data(), FS * 4, hipMemcpyHostToDevice, s));
-        RCHK(hipMemcpyAsync(d_mrows, M.rows.data(), MS * 64, hipMemcpyHostToDevice, s));
-        RCHK(hipMemcpyAsync(d_mpos, M.pos.data(), MS * 16, hipMemcpyHostToDevice, s));
-        RCHK(hipMemcpyAsync(d_minfo, M.info.data(), MS * 4, hipMemcpyHostToDevice, s));
-        RCHK(hipMemcpyAsync(d_order, order.data(), MS * 4, hipMemcpyHostToDevice, s));
-        if (dense) {
-            RCHK(hipMalloc((void **)&d_cell, sizeof(int32_t) * start.size()));
-            RCHK(hipMemcpyAsync(d_cell, start.data(), sizeof(int32_t) * start.size(), hipMemcpyHostToDevice, s));
-        } else {
-            RCHK(hipMalloc((void **)&d_keys, sizeof(long long) * FS));
-            RCHK(hipMemcpyAsync(d_keys, skey.data(), sizeof(long long) * FS, hipMemcpyHostToDevice, s));
-        }
-        RCHK(hipStreamSynchronize(s)); /* the host vectors go out of scope */
+        DEVCHK(dc, dc.open(device));
+        DEVCHK(dc, dc.upload(&d_frows, F.rows.data(), fs * 64));
+        DEVCHK(dc, dc.upload(&d_fnorm, norm.data(), FS));
+        DEVCHK(dc, dc.upload(&d_fidx, idx.data(), FS));
+        DEVCHK(dc, dc.upload(&d_fpos, pos.data(), FS * 4));
+        DEVCHK(dc, dc.upload(&d_finfo, info.data(), FS));
+        DEVCHK(dc, dc.upload(&d_mrows, M.rows.data(), MS * 64));
+        DEVCHK(dc, dc.upload(&d_mpos, M.pos.data(), MS * 4));
+        DEVCHK(dc, dc.upload(&d_minfo, M.info.data(), MS));
+        DEVCHK(dc, dc.upload(&d_order, order.data(), MS));
+        DEVCHK(dc, dc.alloc(&d_out, MS * 5));
+        if (dense) DEVCHK(dc, dc.upload(&d_cell, start.data(), start.size()));
+        else DEVCHK(dc, dc.upload(&d_keys, skey.data(), FS));
+        DEVCHK(dc, dc.sync()); /* the host vectors go out of scope */
         return SIFT3D_OK;
     }
 
@@ -258,26 +200,25 @@ struct GuidedIndex {
                char *err, int64_t err_len)
     {
         if (n_m == 0) return SIFT3D_OK;
+        dc.err = err;
+        dc.err_len = err_len;
         const size_t nq = (size_t)n_m;
         int *o = d_out;
         const long long gn[3] = {g.n[0], g.n[1], g.n[2]};
-        RCHK(hipSetDevice(device));
-        RCHK(hipEventRecord(e0, s));
-        RCHK(sift3d_launch_guided(s, d_frows, d_fnorm, d_fpos, d_finfo, d_fidx, n_f, d_cell, d_keys, g.o, g.edge, gn, dense, d_mrows, d_mpos, d_minfo,
-                                  d_order, n_m, t->center0, t->center1, t->rot, t->scale, radius, lo, hi, o, o + nq, o + 2 * nq, o + 3 * nq,
-                                  visited ? o + 4 * nq : nullptr));
-        RCHK(hipEventRecord(e1, s));
-        RCHK(hipMemcpyAsync(i1, o, nq * 4, hipMemcpyDeviceToHost, s));
-        RCHK(hipMemcpyAsync(d1, o + nq, nq * 4, hipMemcpyDeviceToHost, s));
-        RCHK(hipMemcpyAsync(i2, o + 2 * nq, nq * 4, hipMemcpyDeviceToHost, s));
-        RCHK(hipMemcpyAsync(d2, o + 3 * nq, nq * 4, hipMemcpyDeviceToHost, s));
-        if (visited) RCHK(hipMemcpyAsync(visited, o + 4 * nq, nq * 4, hipMemcpyDeviceToHost, s));
-        RCHK(hipStreamSynchronize(s));
-        if (kernel_ms) {
-            float ms = 0;
-            RCHK(hipEventElapsedTime(&ms, e0, e1));
-            *kernel_ms = ms;
-        }
+        const float lo = sift3d_scale_ivs().lo[0], hi = sift3d_scale_ivs().hi[0];
+        DEVCHK(dc, hipSetDevice(dc.device));
+        DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+        DEVCHK(dc, sift3d_launch_guided(dc.s, d_frows, d_fnorm, d_fpos, d_finfo, d_fidx, n_f, d_cell, d_keys, g.o, g.edge, gn, dense, d_mrows, d_mpos,
+                                        d_minfo, d_order, n_m, t->center0, t->center1, t->rot, t->scale, radius, lo, hi, o, o + nq, o + 2 * nq,
+                                        o + 3 * nq, visited ? o + 4 * nq : nullptr));
+        DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+        DEVCHK(dc, dc.download(i1, o, nq));
+        DEVCHK(dc, dc.download(d1, o + nq, nq));
+        DEVCHK(dc, dc.download(i2, o + 2 * nq, nq));
+        DEVCHK(dc, dc.download(d2, o + 3 * nq, nq));
+        if (visited) DEVCHK(dc, dc.download(visited, o + 4 * nq, nq));
+        DEVCHK(dc, dc.sync());
+        DEVCHK(dc, dc.elapsed_ms(kernel_ms));
         return SIFT3D_OK;
     }
 };
@@ -298,11 +239,10 @@ extern "C" int sift3d_guided_search_params(int device, const sift3d_feature *fix
     const int64_t cells_max = p ? p->index_cells_max : dp.index_cells_max;
     if (!t || !sizes_ok(n_fixed, n_moving) || (n_fixed > 0 && !fixed) || (n_moving > 0 && (!moving || !i1 || !d1 || !i2 || !d2)) ||
         !(radius >= 0) || !std::isfinite(radius) || cells_max < 1)
-        return fail(err, err_len, SIFT3D_ERR_ARG, "bad arguments (0 <= n <= 2^31 - 4096, a finite radius >= 0)");
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "bad arguments (0 <= n <= 2^31 - 4096, a finite radius >= 0)");
     GuidedIndex ix;
-    int rc = ix.build(device, fixed, n_fixed, moving, n_moving, radius, cells_max, err, err_len);
-    if (rc == SIFT3D_OK) rc = ix.search(t, radius, i1, d1, i2, d2, visited, kernel_ms, err, err_len);
-    return rc;
+    const int rc = ix.build(device, fixed, n_fixed, moving, n_moving, radius, cells_max, err, err_len);
+    return rc == SIFT3D_OK ? ix.search(t, radius, i1, d1, i2, d2, visited, kernel_ms, err, err_len) : rc;
 }
 
 extern "C" int sift3d_guided_search(int device, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving,
@@ -367,10 +307,10 @@ extern "C" int sift3d_refine_similarity(int device, const sift3d_feature *fixed,
         p.max_rounds > SIFT3D_REFINE_MAX_ROUNDS || !(p.min_radius > 0) || !(p.max_radius >= p.min_radius) || !std::isfinite(p.max_radius) ||
         p.ratio_num < 1 || p.ratio_den < 1 || !(p.stop_shift >= 0) || p.index_cells_max < 1 ||
         (init->n_matches > 0 && (init->capacity < init->n_matches || !init->moving_idx || !init->fixed_idx || !init->inlier || !init->dist2)))
-        return fail(err, err_len, SIFT3D_ERR_ARG, "bad arguments");
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "bad arguments");
     for (int32_t k = 0; k < init->n_matches; k++)
         if (init->moving_idx[k] < 0 || init->moving_idx[k] >= n_moving || init->fixed_idx[k] < 0 || init->fixed_idx[k] >= n_fixed)
-            return fail(err, err_len, SIFT3D_ERR_ARG, "init's match arrays index outside the record sets");
+            return call_fail(err, err_len, SIFT3D_ERR_ARG, "init's match arrays index outside the record sets");
     /* init's matches, read before anything of *out is written (out may share them) */
     const int32_t n0 = init->n_matches;
     std::vector<int32_t> im(init->moving_idx, init->moving_idx + n0), ifx(init->fixed_idx, init->fixed_idx + n0), iin(init->inlier, init->inlier + n0),
@@ -402,17 +342,8 @@ extern "C" int sift3d_refine_similarity(int device, const sift3d_feature *fixed,
         if (rc != SIFT3D_OK) return rc;
         const RecordSet &FS = ix.F, &MS = ix.M;
         /* the moving records' finite bounding box: its eight corners measure how far a round moves the map */
-        double bmn[3] = {0, 0, 0}, bmx[3] = {0, 0, 0};
-        bool bany = false;
-        for (int64_t i = 0; i < n_moving; i++) {
-            if (!MS.finite(i)) continue;
-            const double v[3] = {MS.x(i), MS.y(i), MS.z(i)};
-            for (int k = 0; k < 3; k++) {
-                if (!bany || v[k] < bmn[k]) bmn[k] = v[k];
-                if (!bany || v[k] > bmx[k]) bmx[k] = v[k];
-            }
-            bany = true;
-        }
+        double bmn[3], bmx[3];
+        const bool bany = finite_box(MS, bmn, bmx);
         const size_t M = (size_t)n_moving;
         std::vector<int32_t> i1(M), d1(M), i2(M), d2(M), vis(M), best((size_t)n_fixed);
         rp.stop = SIFT3D_REFINE_STOP_ROUNDS;
@@ -511,16 +442,5 @@ extern "C" int sift3d_refine_similarity(int device, const sift3d_feature *fixed,
         out->winner = -1;
         iin.assign(keep_m.size(), 1);
     }
-    const int32_t n = (int32_t)keep_m.size();
-    if (out->capacity < n) {
-        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%d pairs, arrays for %d", n, out->capacity);
-        return out->capacity > 0 || out->moving_idx ? SIFT3D_ERR_CAPACITY : SIFT3D_OK;
-    }
-    for (int32_t k = 0; k < n; k++) {
-        if (out->moving_idx) out->moving_idx[k] = keep_m[k];
-        if (out->fixed_idx) out->fixed_idx[k] = keep_f[k];
-        if (out->inlier) out->inlier[k] = iin[k];
-        if (out->dist2) out->dist2[k] = keep_d[k];
-    }
-    return SIFT3D_OK;
+    return sift3d_put_pairs(out, (int32_t)keep_m.size(), keep_m.data(), keep_f.data(), iin.data(), keep_d.data(), "pairs", err, err_len);
 }

@@ -178,4 +178,40 @@ hipError_t sift3d_sort_candidates(hipStream_t s, void *temp, size_t temp_bytes, 
 size_t sift3d_scan_temp_bytes(int64_t n);
 hipError_t sift3d_scan_counts(hipStream_t s, void *temp, size_t temp_bytes, const int *in, int *out, int64_t n);
 
+/* ---- matcher (kernels_match.hip) ---- */
+/* stats: three words the caller has preset to {~0, ~0, 0} */
+hipError_t sift3d_launch_knn_norms(hipStream_t s, const signed char *v, int64_t n, int *norms, unsigned long long *stats);
+hipError_t sift3d_launch_knn(hipStream_t s, const signed char *db, const int *db_norm, int64_t n_db, const signed char *q, const int *q_norm,
+                             int64_t n_q, int k, int const_norm, int groups, int segments, int *part_d, int *part_i, int *out_i, int *out_d);
+int sift3d_knn_list_length(int k);
+void sift3d_knn_plan(int64_t n_db, int64_t n_q, int k, int *groups, int *segments);
+
+/* ---- alignment (kernels_align.hip), resampling (kernels_resample.hip), guided re-matching (kernels_refine.hip) ---- */
+hipError_t sift3d_launch_ratio(hipStream_t s, const signed char *db, const int *db_norm, int64_t n_db, const signed char *q, const int *q_norm,
+                               int64_t n_q, const float *geo, const unsigned *info, float lo, float hi, int *i1, int *d1, int *i2, int *d2);
+hipError_t sift3d_launch_hough(hipStream_t s, const float *p0, const float *p1, const float *s0, const float *s1, const float *o0, const float *o1,
+                               int M, float lo, float hi, int one, int *counts, int *flags, float *hyp);
+hipError_t sift3d_launch_resample(hipStream_t s, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
+                                  int64_t oz, const float *map, int nearest, float fill);
+hipError_t sift3d_launch_guided(hipStream_t s, const void *f_rows, const int *f_norm, const float *f_pos, const unsigned *f_info, const int *f_idx,
+                                int n_f, const int *cell_start, const long long *keys, const double grid_o[3], double edge, const long long grid_n[3],
+                                int dense, const void *m_rows, const float *m_pos, const unsigned *m_info, const int *order, int n_m,
+                                const float c0[3], const float c1[3], const float rot[9], float scale, float radius, float lo, float hi, int *i1,
+                                int *d1, int *i2, int *d2, int *visited);
+
+/* ---- host code the alignment and the guided re-matching share (align_api.hip) ---- */
+#pragma GCC visibility push(hidden)
+/* the ratio intervals of the two scale thresholds, computed once from the host's logf: [0] LOG_1_5 (ratio and guided
+ * search), [1] HOUGH_THRES_SCALE; ok[k] == 0 where that logf is not monotonic near threshold k */
+struct sift3d_scale_intervals {
+    float lo[2], hi[2];
+    int ok[2];
+};
+const sift3d_scale_intervals &sift3d_scale_ivs();
+/* The capacity rule of sift3d_similarity: with room for the n pairs, the arrays out names get them (moving, fixed, inlier, dist2)
+ * and SIFT3D_OK; else "<n> <what>, arrays for <capacity>" in err and SIFT3D_ERR_CAPACITY, or SIFT3D_OK where out has no arrays. */
+int sift3d_put_pairs(sift3d_similarity *out, int32_t n, const int32_t *moving, const int32_t *fixed, const int32_t *inlier, const int32_t *dist2,
+                     const char *what, char *err, int64_t err_len);
+#pragma GCC visibility pop
+
 #endif

@@ -2,12 +2,11 @@
 built with cc -O2 -ffp-contract=off into a temporary directory and bound with ctypes, and the constructed record sets."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "align_oracle.c")
+from _helpers import c_oracle
+
 FEAT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("scale", "<f4"), ("ori", "<f4", (9,)), ("eigs", "<f4", (3,)),
                  ("info", "<u4"), ("desc", "<f4", (64,))])
 LINE = 0x100
@@ -22,9 +21,7 @@ class Sim(C.Structure):
 
 class AlignOracle:
     def __init__(self, tmpdir):
-        so = os.path.join(str(tmpdir), "libalign_oracle.so")
-        subprocess.run(["cc", "-O2", "-ffp-contract=off", "-std=c11", "-fPIC", "-shared", "-o", so, SRC, "-lm"], check=True)
-        L = C.CDLL(so)
+        L = c_oracle("align_oracle", tmpdir)
         P, I64, I = C.c_void_p, C.c_int64, C.c_int
         for name, res, args in [("orc_ratio", I, [P, I64, P, I64, P, P, P, P, P]),
                                 ("orc_hough", I, [P, P, P, P, P, P, I, P, P, P, P, P]),

@@ -7,18 +7,15 @@ import subprocess
 
 import numpy as np
 
+from _helpers import c_oracle
 from align_cases import FEAT, LOG_1_5
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "refine_oracle.c")
 INT32_MAX = 2 ** 31 - 1
 
 
 class RefineOracle:
     def __init__(self, tmpdir):
-        so = os.path.join(str(tmpdir), "librefine_oracle.so")
-        subprocess.run(["cc", "-O2", "-ffp-contract=off", "-std=c11", "-fPIC", "-shared", "-o", so, SRC, "-lm"], check=True)
-        L = C.CDLL(so)
+        L = c_oracle("refine_oracle", tmpdir)
         P, I64, F = C.c_void_p, C.c_int64, C.c_float
         L.orf_search.restype = C.c_int
         L.orf_search.argtypes = [P, I64, P, I64, P, P, P, F, F, F, F, P, P, P, P]

@@ -1,21 +1,17 @@
 """Shared pieces of the resampling tests (test_resample_cpu.py, test_gpu_resample.py): the CPU oracle tests/resample_oracle.c,
 built with cc -O2 -ffp-contract=off into a temporary directory and bound with ctypes, and the maps and volumes the tests use."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "resample_oracle.c")
+from _helpers import c_oracle
+
 MODES = {"linear": 0, "nearest": 1}
 
 
 class ResampleOracle:
     def __init__(self, tmpdir):
-        so = os.path.join(str(tmpdir), "libresample_oracle.so")
-        subprocess.run(["cc", "-O2", "-ffp-contract=off", "-std=c11", "-fPIC", "-shared", "-o", so, SRC, "-lm"], check=True)
-        L = C.CDLL(so)
+        L = c_oracle("resample_oracle", tmpdir)
         P, I64 = C.c_void_p, C.c_int64
         L.orc_resample.restype = C.c_int
         L.orc_resample.argtypes = [P, I64, I64, I64, P, I64, I64, I64, P, C.c_int, C.c_float, I64, I64]

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import align_cases as ac
+from _helpers import extract
 
 pytestmark = pytest.mark.gpu
 
@@ -137,17 +138,10 @@ def _volumes(built):
                    "half": np.ascontiguousarray(fixed[::2, ::2, ::2])}              # every other voxel: x_f ~ 2 x_m
 
 
-def _extract(built, vol):
-    nz, ny, nx = vol.shape
-    with built.Context(nx, ny, nz, device=0) as ctx:
-        ctx.set_volume(vol)
-        return ctx.extract()
-
-
 @pytest.fixture(scope="module")
 def extractions(built):
     fixed, moving = _volumes(built)
-    return _extract(built, fixed), {k: _extract(built, v) for k, v in moving.items()}
+    return extract(built, fixed), {k: extract(built, v) for k, v in moving.items()}
 
 
 # Tolerances fixed beforehand from the CPU oracle on the oracle's own extractions of the same volumes (which the GPU's

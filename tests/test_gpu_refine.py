@@ -6,6 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from _helpers import extract, run as _run
 from align_cases import LINE, AlignOracle, random_records, random_rotation
 from refine_cases import (RefineOracle, cpu_refine, interval, noisy_case, scenario_cpu, scenario_map, scenario_score,
                           scenario_volumes)
@@ -121,18 +122,11 @@ def test_guided_search_tiny_fixed_sets(built, rorc, n_f):
     assert (want[0] == 0).sum() >= 50 if n_f else (want[0] == -1).all()
 
 
-def _extract(built, vol):
-    nz, ny, nx = vol.shape
-    with built.Context(nx, ny, nz, device=0) as ctx:
-        ctx.set_volume(vol)
-        return ctx.extract()
-
-
 @pytest.fixture(scope="module")
 def extractions_256(built):
     v = built.synth_blobs(256, 256, 256, seed=12345)
     w = np.ascontiguousarray(np.roll(v, (3, -5, 7), axis=(0, 1, 2)))
-    return _extract(built, v), _extract(built, w)
+    return extract(built, v), extract(built, w)
 
 
 @pytest.mark.parametrize("radius", [4.0, 16.0])
@@ -190,12 +184,6 @@ def test_refine_similarity_parameters_and_refusal(built, rorc):
     # no moving record
     got, rep = built.refine_similarity(f, m[:0], built.match_keys(f, m[:0]))
     assert rep["stop"] == "none" and rep["rounds"] == 0
-
-
-def _run(argv, cwd):
-    r = subprocess.run([str(a) for a in argv], cwd=cwd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return r
 
 
 @pytest.fixture(scope="module")

@@ -1,11 +1,11 @@
 """GPU tests of featResample: sift3d_resample_affine against the CPU oracle tests/resample_oracle.c
 (equal bits wherever the result is a number, NaN where it is NaN -- the NaN payload an x86 multiply makes is not the
 device's), an output beyond 2^31 voxels, and the three command lines end to end."""
-import subprocess
 
 import numpy as np
 import pytest
 
+from _helpers import run as _run
 from resample_cases import ResampleOracle, about_centre, rot, special_volume
 
 pytestmark = pytest.mark.gpu
@@ -161,12 +161,6 @@ def test_output_beyond_32_bit_indices(built, rorc):
 
 
 # ---- end to end: featExtract -> featMatchMultiple -a -> featResample -----------------------------------------------------
-def _run(argv, cwd):
-    r = subprocess.run(argv, cwd=cwd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, " ".join(argv) + "\n" + r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
 def _end_to_end(built, rorc, tmp_path, world):
     n, N = 128, 192
     V = built.synth_blobs(n, n, n, seed=31)
