@@ -32,7 +32,10 @@ those only rank 0 extracts the whole volume (the single-GPU records the merged
 ones are compared with), there is no replica leg.
 
 Rank 0 prints ONE JSON line: metric = keypoints/s (.key records per second,
-whole job), plus
+whole job).  A plain run does only what that figure needs: set-up, warm-up, the
+timed steps, --dump-outputs if given, the line.  `--full` adds what takes runs
+or measurements of its own, computed after the timed steps:
+  stages       kernel time per stage from extra steps with every launch bracketed
   roofline     the dominant pyramid kernel (the fused x+y+z+DoG blur, one launch per
                level): algorithmic = compulsory bytes (12 B/voxel,
                8 where only the level or only the DoG is kept) / launch time over its
@@ -43,7 +46,8 @@ whole job), plus
   pyramid      Gauss-pyramid + DoG GB/s over all blur launches of a step
   cpu_baseline the CPU restatement (oracle/, single thread like the reference's
                extractor) timed on this box on the 512^3 metric volume, N = 1 only;
-               cpu_baseline_ncores: its OpenMP build on all host cores of the box
+               cpu_baseline_ncores: its OpenMP build on all host cores of the box;
+               records_match_cpu: the timed step's records against its records
 
 `--dump-outputs DIR` (N = 1) also writes the records of the last timed step to DIR
 as .npy files (dump_outputs), so that two builds can be compared output for output.
@@ -550,8 +554,11 @@ def main():
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="a BASELINE.json configuration instead of the metric volume: c4 = 1024 x 1024 x 512 (start it with --gpus 4), "
                          "c5 = 2048 x 2048 x 1024 with the NRRIEF descriptor (--gpus 8); N > 1 only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, the per-stage breakdown steps, `roofline` (with its in-process ceiling), "
+                         "`pyramid`, `stages` and, at N = 1, the CPU baselines and records_match_cpu (default: the headline only)")
     ap.add_argument("--cpu-sample", type=int, default=512,
-                    help="edge of the CPU-baseline volume (0 = skip); 512 = the metric volume itself, about 25 s on one core")
+                    help="--full: edge of the CPU-baseline volume (0 = skip); 512 = the metric volume itself, about 25 s on one core")
     ap.add_argument("--desc", type=int, default=None, help="0 SIFT-rank (default), 1 BRIEF, 2 RRIEF, 3 NRRIEF")
     ap.add_argument("--mode", default="auto", choices=["auto", "volumes", "zslab", "zslab_c"],
                     help="N > 1: 'auto' (default) = the ranks' own volumes first (weak scaling, `volumes_value`), then the Z-slab "
@@ -713,7 +720,7 @@ def main():
     tim = ctx.timings()
     gpu_recs = feats.copy() if rank == 0 else None   # the timed region's last step (the pinned view is reused by the next call)
     full_logs, excl_logs = [], []
-    if rank == 0:
+    if rank == 0 and args.full:
         # The breakdown steps run the one-list schedule (SIFT3D_TUNE_SPLIT_TAIL 0): on the production schedule the launches that
         # build the coarse octaves queue behind the first part's keypoint kernel, and an event pair around such a launch
         # times that wait (3 ms), not the kernel.  The timed region above ran the production schedule.
@@ -746,6 +753,26 @@ def main():
     phase("volumes: result line (rank 0: breakdown, CPU baseline)", 0)
 
     if rank == 0:
+        out = {
+            "metric": "keypoints/s (.key records per second; Gauss-pyramid GB/s vs HBM roofline in `pyramid`/`roofline`)",
+            "value": round(total_records / (ms_per_step * 1e-3), 1),
+            "unit": "keypoints/s",
+            "n_gpus": world, "devices_used": min(world, ndev), "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic", "full": bool(args.full),
+            "config": {"workload": "%s float32 blob-field volume per GPU, full featExtract path (pyramid + DoG + extrema + keypoints + %s descriptor), all octaves"
+                                   % (vol_label, ["SIFT-rank", "BRIEF", "RRIEF", "NRRIEF"][args.desc]),
+                       "records_per_volume": int(nrec), "octaves": int(tim["n_octaves"]), "extrema": int(tim["n_extrema"]),
+                       "keypoints": int(tim["n_keypoints"]),
+                       "parallelism": "1 volume per GPU (independent volumes, no collective)" if world > 1 else "single GPU",
+                       "tuning": args.tune or "defaults",
+                       "descriptor_parity": ("SIFT-rank: pinned against the reference (see DESIGN.md section 2)" if args.desc == 0 else
+                                             "BRIEF / RRIEF / NRRIEF exist in the reference only as commented alternatives "
+                                             "(MultiScale.cpp:1037-1045): HIP == oracle bit for bit, but the oracle rows are unpinned "
+                                             "against the reference")},
+        }
+    if rank == 0 and args.full:   # everything below takes runs or measurements of its own beside the headline figure
         nfullvox = ((nx + 3) // 4 * 4) * ny * nz   # rows are padded to whole 16-byte vectors inside the pipeline
         log = np.concatenate(logs)            # timed region: the blur launches on the n^3 volume
         full = np.concatenate(full_logs)      # two extra steps with every launch bracketed (per-stage breakdown)
@@ -937,26 +964,7 @@ def main():
                     "time the pyramid's blur launches take here; the fused launches move a third of those bytes, which is why `equivalent_GBs` "
                     "may exceed the HBM peak.  The north star's 0.70 of the HBM roofline is judged on roofline.frac (compulsory bytes of what is "
                     "launched) and is NOT met at 0.61 - 0.62; see roofline.ceiling for what the access shape allows"}
-        out = {
-            "metric": "keypoints/s (.key records per second; Gauss-pyramid GB/s vs HBM roofline in `pyramid`/`roofline`)",
-            "value": round(total_records / (ms_per_step * 1e-3), 1),
-            "unit": "keypoints/s",
-            "n_gpus": world, "devices_used": min(world, ndev), "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s float32 blob-field volume per GPU, full featExtract path (pyramid + DoG + extrema + keypoints + %s descriptor), all octaves"
-                                   % (vol_label, ["SIFT-rank", "BRIEF", "RRIEF", "NRRIEF"][args.desc]),
-                       "records_per_volume": int(nrec), "octaves": int(tim["n_octaves"]), "extrema": int(tim["n_extrema"]),
-                       "keypoints": int(tim["n_keypoints"]),
-                       "parallelism": "1 volume per GPU (independent volumes, no collective)" if world > 1 else "single GPU",
-                       "tuning": args.tune or "defaults",
-                       "descriptor_parity": ("SIFT-rank: pinned against the reference (see DESIGN.md section 2)" if args.desc == 0 else
-                                             "BRIEF / RRIEF / NRRIEF exist in the reference only as commented alternatives "
-                                             "(MultiScale.cpp:1037-1045): HIP == oracle bit for bit, but the oracle rows are unpinned "
-                                             "against the reference")},
-            "roofline": roofline, "pyramid": pyramid, "stages": stages,
-        }
+        out.update({"roofline": roofline, "pyramid": pyramid, "stages": stages})
         if world == 1 and args.cpu_sample > 0:
             # CPU baseline: the C restatement of the reference's CPU path, timed on this box's host
             # cores on the same blob-field volume the GPU step works on (one step of the same workload).  One thread is
@@ -1047,7 +1055,7 @@ def main():
     out["config"]["workload"] = z.get("workload") or ("ONE %s float32 blob-field volume cut into %d Z-slabs (the child job failed: see `zslab`)" % (vol_label, world))
     out["config"]["parallelism"] = z.get("parallelism") or "zslab%d" % world
     out["config"]["records_to_rank0"] = z.get("records_to_rank0")
-    out["config"]["single_gpu_workload"] = "%s volume on one GPU (`volumes_*`; `roofline`, `pyramid`, `stages` are rank 0's single-GPU kernels)" % vol_label
+    out["config"]["single_gpu_workload"] = "%s volume on one GPU (`volumes_*`; with --full, `roofline`, `pyramid`, `stages` are rank 0's single-GPU kernels)" % vol_label
     out["value_source"] = value_source if ok else None
     out["zslab"] = z
     out["zslab_c"] = zc

@@ -93,6 +93,14 @@ def test_steps_and_dump_outputs_are_checked_before_any_gpu_call(tmp_path):
     assert not os.path.exists(tmp_path / "d")
 
 
+def test_full_is_an_option_of_its_own():
+    """--full (the breakdown, roofline and CPU-baseline legs beside the headline) is there and says what it adds."""
+    r = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, env=_env(), timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    help_text = " ".join(r.stdout.split())
+    assert "--full" in help_text and "roofline" in help_text and "CPU baselines" in help_text
+
+
 def test_dump_outputs_writes_the_records_within_the_budget(tmp_path):
     """bench.dump_outputs: every record field as float32 (info as float64, exact for uint32) and the record numbers; above the
     byte budget a sample drawn with a fixed seed, the same on every call, in record order."""

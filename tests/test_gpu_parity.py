@@ -1734,3 +1734,28 @@ def test_bench_dump_outputs_are_the_timed_steps_records(built, oracle, tmp_path)
     assert (got["info"] == want["info"]).all() and (got["desc"] == want["desc"]).all()
     for f in ("x", "y", "z", "scale", "ori", "eigs"):
         assert np.abs(got[f] - want[f]).max() <= TOL, f
+
+
+def test_bench_plain_line_and_full_line(built):
+    """bench.py without --full prints the headline only; with --full the same line also carries the breakdown, roofline and
+    CPU-baseline legs, and the timed step's records match the CPU restatement's."""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def line(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--size", "256", "--steps", "1",
+                            "--warmup", "1"] + list(extra), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    plain = line()
+    full = line("--full", "--cpu-sample", "256")
+    extras = ("roofline", "pyramid", "stages", "cpu_baseline", "cpu_baseline_ncores", "records_match_cpu")
+    for d, is_full in ((plain, False), (full, True)):
+        for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert k in d, k
+        assert d["full"] is is_full and d["steps"] == 1 and d["warmup"] == 1
+        assert all((k in d) == is_full for k in extras), sorted(d)
+    assert plain["metric"] == full["metric"] and plain["config"]["records_per_volume"] == full["config"]["records_per_volume"]
+    assert full["records_match_cpu"]["match"] and full["cpu_baseline"]["cores"] == 1
+    assert full["roofline"]["bound"] == "hbm" and full["stages"]["_note"]

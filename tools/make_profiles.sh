@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: regenerates the rocprofv3 evidence that profiles/ holds for one build.
 #   bash tools/make_profiles.sh <tag>       (e.g. r01_c) -> gpurun_out/prof_<tag>/...
-# 1. rocprofv3 --kernel-trace --stats over `python3 bench.py --steps 5 --warmup 2 --cpu-sample 0`
+# 1. rocprofv3 --kernel-trace --stats over `python3 bench.py --full --steps 5 --warmup 2 --cpu-sample 0`
 # 2. PMC passes (separate runs, kernel trace only): FETCH_SIZE, WRITE_SIZE over `python3 tools/bench_blur.py 512 3`
 set -e
 TAG=$1
@@ -9,12 +9,12 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $ROOT/bench.py --steps 5 --warmup 2 --cpu-sample 0 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 --cpu-sample 0 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$c -o pmc --output-format csv -- python3 $ROOT/tools/bench_blur.py 512 3 > $OUT/pmc_$c.log 2>&1
 done
 cd $ROOT
-python3 bench.py --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 python3 - $TAG <<'PY'
 import csv, glob, json, sys, collections, statistics
 tag = sys.argv[1]

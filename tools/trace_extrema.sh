@@ -7,7 +7,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/trace_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 1 --cpu-sample 0 "$@" > $OUT/bench.json 2> $OUT/err.log
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --cpu-sample 0 "$@" > $OUT/bench.json 2> $OUT/err.log
 cd $ROOT
 python3 - $OUT <<'PY'
 import csv, glob, sys, collections
