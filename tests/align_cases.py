@@ -26,6 +26,7 @@ class AlignOracle:
         for name, res, args in [("orc_ratio", I, [P, I64, P, I64, P, P, P, P, P]),
                                 ("orc_hough", I, [P, P, P, P, P, P, I, P, P, P, P, P]),
                                 ("orc_match_keys", I, [P, I64, P, I64, I, P]),
+                                ("orc_match_keys_from_ratio", I, [P, I64, P, I64, I, P, P, P, P, P]),
                                 ("orc_invert", None, [P, P]),
                                 ("orc_write_matrix", I, [C.c_char_p, P]),
                                 ("orc_write_matches", I, [C.c_char_p, C.c_char_p, C.c_char_p, P, I64, P, P]),
@@ -59,6 +60,22 @@ class AlignOracle:
         for k, a in arrays.items():
             setattr(t, k, a.ctypes.data)
         self.L.orc_match_keys(f.ctypes.data, len(f), m.ctypes.data, len(m), int(max_matches), C.byref(t))
+        return sim_dict(t, arrays)
+
+    def match_keys_from_ratio(self, fixed, moving, ratio, max_matches=3000):
+        """match_keys with the ratio search replaced by given (i1, d1, i2, d2) of every moving record (test only: for record
+        sets whose CPU ratio search is too slow, fed with GPU ratio results that were sample-checked against ratio())"""
+        f, m = np.ascontiguousarray(fixed, FEAT), np.ascontiguousarray(moving, FEAT)
+        r = [np.ascontiguousarray(a, np.int32) for a in ratio[:4]]
+        assert all(len(a) == len(m) for a in r)
+        cap = max(1, min(len(m), max_matches))
+        arrays = {k: np.zeros(cap, np.int32) for k in ("moving_idx", "fixed_idx", "inlier", "dist2")}
+        t = Sim()
+        t.capacity = cap
+        for k, a in arrays.items():
+            setattr(t, k, a.ctypes.data)
+        assert self.L.orc_match_keys_from_ratio(f.ctypes.data, len(f), m.ctypes.data, len(m), int(max_matches), *[a.ctypes.data for a in r],
+                                                C.byref(t)) == 0
         return sim_dict(t, arrays)
 
     def _struct(self, d):

@@ -263,7 +263,10 @@ static int cmp_match(const void *a, const void *b)
     return i < j ? -1 : (i > j);
 }
 
-int orc_match_keys(const Rec *fixed, int64_t nf, const Rec *moving, int64_t nm, int max_matches, Sim *out)
+/* MatchKeys from the ratio search's results i1, d1, i2, d2 of every moving record (NULL when nf < 2 or nm == 0): the centre,
+ * the sort by ratio, the cut at max_matches and the Hough */
+static int match_keys_from(const Rec *fixed, int64_t nf, const Rec *moving, int64_t nm, int max_matches, const int32_t *i1, const int32_t *d1,
+                           const int32_t *d2, Sim *out)
 {
     memset(out->c0, 0, sizeof out->c0);
     if (nm > 0) {
@@ -287,10 +290,8 @@ int orc_match_keys(const Rec *fixed, int64_t nf, const Rec *moving, int64_t nm, 
     out->n_matches = out->inliers = 0;
     out->winner = -1;
     if (nf < 2 || nm == 0) return 0;
-    int32_t *i1 = malloc(sizeof(int32_t) * nm), *d1 = malloc(sizeof(int32_t) * nm), *i2 = malloc(sizeof(int32_t) * nm), *d2 = malloc(sizeof(int32_t) * nm);
     float *ratio = malloc(sizeof(float) * nm);
     int32_t *order = malloc(sizeof(int32_t) * nm);
-    orc_ratio(fixed, nf, moving, nm, i1, d1, i2, d2, NULL);
     for (int64_t i = 0; i < nm; i++) {
         ratio[i] = (float)d1[i] / (float)d2[i];
         order[i] = (int32_t)i;
@@ -334,9 +335,32 @@ int orc_match_keys(const Rec *fixed, int64_t nf, const Rec *moving, int64_t nm, 
             out->inlier[k] = flags[k];
             out->dist2[k] = d1[order[k]];
         }
-    free(i1); free(d1); free(i2); free(d2); free(ratio); free(order);
+    free(ratio); free(order);
     free(p0); free(p1); free(s0); free(s1); free(o0); free(o1); free(counts); free(flags);
     return 0;
+}
+
+int orc_match_keys(const Rec *fixed, int64_t nf, const Rec *moving, int64_t nm, int max_matches, Sim *out)
+{
+    if (nf < 2 || nm == 0) return match_keys_from(fixed, nf, moving, nm, max_matches, NULL, NULL, NULL, out);
+    int32_t *i1 = malloc(sizeof(int32_t) * nm), *d1 = malloc(sizeof(int32_t) * nm), *i2 = malloc(sizeof(int32_t) * nm), *d2 = malloc(sizeof(int32_t) * nm);
+    orc_ratio(fixed, nf, moving, nm, i1, d1, i2, d2, NULL);
+    const int rc = match_keys_from(fixed, nf, moving, nm, max_matches, i1, d1, d2, out);
+    free(i1); free(d1); free(i2); free(d2);
+    return rc;
+}
+
+/* TEST ONLY: orc_match_keys with the ratio search replaced by given results (i1, d1, i2, d2 per moving record, as orc_ratio
+ * writes them), for record sets whose full CPU ratio search is too slow; i2 is not read (MatchKeys does not use it).  An i1
+ * outside the fixed set is refused (-1). */
+int orc_match_keys_from_ratio(const Rec *fixed, int64_t nf, const Rec *moving, int64_t nm, int max_matches, const int32_t *i1, const int32_t *d1,
+                              const int32_t *i2, const int32_t *d2, Sim *out)
+{
+    (void)i2;
+    if (nf >= 2)
+        for (int64_t i = 0; i < nm; i++)
+            if (i1[i] < 0 || i1[i] >= nf) return -1;
+    return match_keys_from(fixed, nf, moving, nm, max_matches, nf >= 2 && nm > 0 ? i1 : NULL, d1, d2, out);
 }
 
 /* TransformSimilarity::Invert */

@@ -96,3 +96,32 @@ def test_edge_cases_at_the_host_level(alib, aorc, tmp_path):
     assert h["counts"][0] == -1 and h["counts"][2] == -1 and h["winner"] == 1
     h = aorc.hough(p, p, np.zeros(m, np.float32), s, o, o)
     assert (h["counts"] == -1).all() and h["winner"] == -1 and (h["flags"] == 0).all()
+
+
+def _same_keys(a, b):
+    for k in ("scale", "rot", "trans", "center0", "center1"):
+        assert np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes(), k
+    for k in ("n_matches", "inliers", "winner"):
+        assert a[k] == b[k], k
+    for k in ("moving_idx", "fixed_idx", "inlier", "dist2"):
+        assert np.array_equal(a[k], b[k]), k
+
+
+@pytest.mark.parametrize("seed,n,max_matches", [(5, 300, 3000), (6, 400, 150), (7, 2, 3000), (8, 3, 3000), (9, 60, 4)])
+def test_match_keys_from_ratio_equals_match_keys(alib, aorc, seed, n, max_matches):
+    """orc_match_keys_from_ratio (the GPU scale tests feed it the GPU's ratio arrays) is orc_match_keys with the ratio search
+    taken out: fed orc_ratio's own arrays it must give the same result, bit for bit -- here also with duplicated descriptors
+    (0 / 0 ratios sorted last), a cut at max_matches, and too few matches for a Hough"""
+    fixed, moving, R, s, t, _n, _p = ac.recovery_case(seed, n=n)
+    rng = np.random.default_rng(seed)
+    moving["desc"][::5] = fixed["desc"][rng.integers(0, len(fixed), len(moving[::5]))]
+    fixed["desc"][1::9] = fixed["desc"][0]
+    ratio = aorc.ratio(fixed, moving)
+    _same_keys(aorc.match_keys_from_ratio(fixed, moving, ratio, max_matches=max_matches), aorc.match_keys(fixed, moving, max_matches=max_matches))
+    for f, m in ((fixed[:1], moving), (fixed, moving[:0])):   # no ratio search at all: the centre and the identity
+        empty = [np.zeros(len(m), np.int32)] * 4
+        _same_keys(aorc.match_keys_from_ratio(f, m, empty), aorc.match_keys(f, m))
+    bad = [a.copy() for a in ratio[:4]]
+    bad[0][len(moving) // 2] = len(fixed)
+    with pytest.raises(AssertionError):
+        aorc.match_keys_from_ratio(fixed, moving, bad)

@@ -138,9 +138,13 @@ def test_guided_search_on_256_extractions(built, rorc, extractions_256, radius):
     assert (want[0] >= 0).mean() > 0.5
 
 
-def _same_refine(built, got, rep, f, m, init, rorc, **params):
+def _same_refine(built, got, rep, f, m, init, rorc, search=None, **params):
+    """search(t, radius) -> (i1, d1, i2, d2): the loop's search; None: the brute-force oracle's (record sets too large for it
+    pass a search whose results were checked against it on a sample)"""
     lo, hi = interval()
-    cur, kept, want = cpu_refine(f, m, init, lambda t, r: rorc.search(f, m, t, r, lo, hi), built.fit_similarity, **params)
+    if search is None:
+        search = lambda t, r: rorc.search(f, m, t, r, lo, hi)
+    cur, kept, want = cpu_refine(f, m, init, search, built.fit_similarity, **params)
     assert rep["rounds"] == want["rounds"] and rep["stop"] == want["stop"], (rep, want)
     for a, b in zip(rep["round"], want["round"]):
         assert a["radius"].tobytes() == np.float32(b["radius"]).tobytes()
