@@ -170,6 +170,9 @@ def hip_lib():
     _sig(L.sift3d_resample_affine_dev, I, P, P, I64, I64, I64, P, I64, I64, I64, P, I, F)
     _sig(L.sift3d_guided_search_params, I, I, P, I64, P, I64, P, F, P, P, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_refine_similarity, I, I, P, I64, P, I64, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_fit_field, I, I, P, P, I64, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_refine_field, I, I, P, I64, P, I64, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_resample_field, I, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, I, F, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -210,6 +213,14 @@ def host_lib():
     _sig(L.sift3d_key_vox2key, None, P, P, P)
     _sig(L.sift3d_fit_similarity, I, P, P, I64, P)
     _sig(L.sift3d_refine_defaults, None, P)
+    _sig(L.sift3d_field_defaults, None, P)
+    _sig(L.sift3d_field_size, I, P, I64, P, P)
+    _sig(L.sift3d_field_samples, None, P, P, P, I64, P, P)
+    _sig(L.sift3d_field_warp_terms, I, P, P, P, P)
+    _sig(L.sift3d_field_eval, None, P, P, I64, P)
+    _sig(L.sift3d_field_folds, I64, P, P, P)
+    _sig(L.sift3d_write_field, I, C.c_char_p, P)
+    _sig(L.sift3d_read_field, I, C.c_char_p, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -597,6 +608,182 @@ def refine_similarity(fixed, moving, init, device=0, **params):
 
 # ---- resampling (featResample), DESIGN.md section 7c ----------------------------------------------------------------------
 INTERP = {"linear": 0, "nearest": 1}   # include/sift3d.h: sift3d_interp
+
+
+# ---- nonrigid alignment (featMatchMultiple -a -e -u, featResample -u), DESIGN.md section 7e ----------------------------------
+FIELD_MAX_DISP = 128.0   # SIFT3D_FIELD_MAX_DISP
+
+
+class Field(C.Structure):
+    """sift3d_field"""
+    _fields_ = [("n", C.c_int64 * 3), ("origin", C.c_float * 3), ("spacing", C.c_float), ("capacity", C.c_int64), ("disp", C.c_void_p)]
+
+
+class FieldParams(C.Structure):
+    """sift3d_field_params"""
+    _fields_ = [("spacing", C.c_float), ("radius", C.c_float), ("lambda_", C.c_float), ("search_radius", C.c_float), ("min_tol", C.c_float),
+                ("ratio_num", C.c_int32), ("ratio_den", C.c_int32), ("max_nodes", C.c_int64), ("index_cells_max", C.c_int64)]
+
+
+class FieldReport(C.Structure):
+    """sift3d_field_report"""
+    _fields_ = [("accepted", C.c_int32), ("kept", C.c_int32), ("rms_before", C.c_double), ("rms_after", C.c_double), ("max_disp", C.c_double),
+                ("folds", C.c_int64), ("search_ms", C.c_double), ("fit_ms", C.c_double * 2)]
+
+
+def field_params(**kw):
+    """sift3d_field_defaults, then the given fields (spacing, radius, lam (lambda), search_radius, min_tol, ratio_num, ratio_den,
+    max_nodes, index_cells_max)."""
+    p = FieldParams()
+    host_lib().sift3d_field_defaults(C.byref(p))
+    for k, v in kw.items():
+        k = "lambda_" if k in ("lam", "lambda") else k
+        if k not in dict(FieldParams._fields_):
+            raise ValueError("no field parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _pts(a):
+    return np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+
+
+def _field_dict(f, disp):
+    n = tuple(int(x) for x in f.n)
+    return {"n": n, "origin": np.array(f.origin, np.float32), "spacing": np.float32(f.spacing),
+            "disp": disp[:3 * n[0] * n[1] * n[2]].reshape(3, n[2], n[1], n[0])}
+
+
+def _field_struct(d):
+    """a sift3d_field from a field dict (the array kept alive in the returned tuple)"""
+    f = Field()
+    disp = np.ascontiguousarray(d["disp"], np.float32).reshape(-1)
+    f.n[:] = [int(x) for x in d["n"]]
+    f.origin[:] = [float(x) for x in np.asarray(d["origin"], np.float32)]
+    f.spacing = float(d["spacing"])
+    f.capacity = disp.size
+    f.disp = disp.ctypes.data
+    return f, disp
+
+
+def field_size(y, **params):
+    """sift3d_field_size: the grid of samples at y (n x 3): dict n, origin, spacing.  Raises where it is refused."""
+    y = _pts(y)
+    f = Field()
+    if host_lib().sift3d_field_size(y.ctypes.data, len(y), C.byref(field_params(**params)), C.byref(f)) != 0:
+        raise Sift3DError("sift3d_field_size: bad parameters or too many nodes")
+    return {"n": tuple(int(x) for x in f.n), "origin": np.array(f.origin, np.float32), "spacing": np.float32(f.spacing)}
+
+
+def field_samples(t, p_fixed, p_moving):
+    """sift3d_field_samples: (y, v), n x 3 each, of the pairs (p_fixed[i], p_moving[i]) under t (a match_keys-style dict)"""
+    pf, pm = _pts(p_fixed), _pts(p_moving)
+    st, _keep = _similarity_struct(t)
+    y, v = np.empty_like(pf), np.empty_like(pf)
+    host_lib().sift3d_field_samples(C.byref(st), pf.ctypes.data, pm.ctypes.data, len(pf), y.ctypes.data, v.ctypes.data)
+    return y, v
+
+
+def fit_field(y, v, device=0, return_ms=False, **params):
+    """sift3d_fit_field: one fit on the GPU of samples y, v (n x 3 each).  Returns a field dict: n (n0, n1, n2), origin,
+    spacing, disp (3, n2, n1, n0) float32; return_ms=True returns (field, kernel_ms)."""
+    y, v = _pts(y), _pts(v)
+    if len(y) != len(v):
+        raise ValueError("y and v differ in length")
+    p = field_params(**params)
+    g = field_size(y, **params)
+    disp = np.zeros(3 * g["n"][0] * g["n"][1] * g["n"][2], np.float32)
+    f = Field()
+    f.capacity, f.disp = disp.size, disp.ctypes.data
+    ms = C.c_double(0.0)
+    _call("sift3d_fit_field", int(device), y.ctypes.data, v.ctypes.data, len(y), C.byref(p), C.byref(f), C.byref(ms))
+    d = _field_dict(f, disp)
+    return (d, ms.value) if return_ms else d
+
+
+def _field_report_dict(r):
+    return {"accepted": int(r.accepted), "kept": int(r.kept), "rms_before": float(r.rms_before), "rms_after": float(r.rms_after),
+            "max_disp": float(r.max_disp), "folds": int(r.folds), "search_ms": float(r.search_ms), "fit_ms": (float(r.fit_ms[0]), float(r.fit_ms[1]))}
+
+
+def refine_field(fixed, moving, t, device=0, **params):
+    """sift3d_refine_field: search at t (a match_keys-style dict), accept, fit, trim, refit.  Returns (field dict, report dict)."""
+    f = np.ascontiguousarray(fixed, FEATURE_DTYPE)
+    m = np.ascontiguousarray(moving, FEATURE_DTYPE)
+    st, _keep = _similarity_struct(t)
+    p = field_params(**params)
+    g = field_size(np.stack([f["x"], f["y"], f["z"]], 1), **params)   # the fixed records' grid bounds any samples' grid
+    disp = np.zeros(3 * g["n"][0] * g["n"][1] * g["n"][2], np.float32)
+    out = Field()
+    out.capacity, out.disp = disp.size, disp.ctypes.data
+    rep = FieldReport()
+    _call("sift3d_refine_field", int(device), f.ctypes.data, len(f), m.ctypes.data, len(m), C.byref(st), C.byref(p), C.byref(out), C.byref(rep))
+    return _field_dict(out, disp), _field_report_dict(rep)
+
+
+def field_warp_terms(fixed_vox2key=None, moving_vox2key=None):
+    """sift3d_field_warp_terms: (C 3 x 4, K 3 x 3) float32 of the warp"""
+    ms = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(16) for a in (fixed_vox2key, moving_vox2key)]
+    c, k = np.zeros(12, np.float32), np.zeros(9, np.float32)
+    if host_lib().sift3d_field_warp_terms(*[None if a is None else a.ctypes.data for a in ms], c.ctypes.data, k.ctypes.data) != 0:
+        raise Sift3DError("sift3d_field_warp_terms: a last row is not 0 0 0 1 or moving_vox2key is singular")
+    return c.reshape(3, 4), k.reshape(3, 3)
+
+
+def resample_field(vol, out_shape, map, field, fixed_vox2key=None, moving_vox2key=None, interp="linear", fill=0.0, device=0, return_ms=False):
+    """sift3d_resample_field: resample_affine through the map and the displacement field (a field dict); vox2key 4 x 4 (None:
+    identity).  return_ms=True returns (out, kernel_ms)."""
+    v = _f32(vol)
+    nz, ny, nx = v.shape
+    oz, oy, ox = (int(d) for d in out_shape)
+    out = np.empty((oz, oy, ox), np.float32)
+    m = _map12(map)
+    fs, _keep = _field_struct(field)
+    ms_ = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(16) for a in (fixed_vox2key, moving_vox2key)]
+    ms = C.c_double(0.0)
+    _call("sift3d_resample_field", int(device), v.ctypes.data, nx, ny, nz, out.ctypes.data, ox, oy, oz, m.ctypes.data,
+          *[None if a is None else a.ctypes.data for a in ms_], C.byref(fs), INTERP[interp], float(fill), C.byref(ms))
+    return (out, ms.value) if return_ms else out
+
+
+def field_eval(field, y):
+    """sift3d_field_eval: v at key positions y (n x 3), 0 outside the grid"""
+    y = _pts(y)
+    fs, _keep = _field_struct(field)
+    out = np.empty_like(y)
+    host_lib().sift3d_field_eval(C.byref(fs), y.ctypes.data, len(y), out.ctypes.data)
+    return out
+
+
+def field_folds(t, field):
+    """sift3d_field_folds: (nodes with det grad phi <= 0, largest |v| over the nodes)"""
+    st, _keep = _similarity_struct(t)
+    fs, _keep2 = _field_struct(field)
+    big = C.c_double(0.0)
+    n = host_lib().sift3d_field_folds(C.byref(st), C.byref(fs), C.byref(big))
+    return int(n), big.value
+
+
+def write_field(path, field):
+    """sift3d_write_field: <moving>.field.nii"""
+    fs, _keep = _field_struct(field)
+    if host_lib().sift3d_write_field(os.fsencode(path), C.byref(fs)) != 0:
+        raise Sift3DError("could not write %s" % path)
+
+
+def read_field(path):
+    """sift3d_read_field: a field dict; raises Sift3DError (code SIFT3D_ERR_ARG) for anything the writer does not write"""
+    f = Field()
+    rc = host_lib().sift3d_read_field(os.fsencode(path), C.byref(f))
+    if rc == -4:   # SIFT3D_ERR_CAPACITY: the grid is known now
+        disp = np.zeros(3 * f.n[0] * f.n[1] * f.n[2], np.float32)
+        f.capacity, f.disp = disp.size, disp.ctypes.data
+        rc = host_lib().sift3d_read_field(os.fsencode(path), C.byref(f))
+        if rc == 0:
+            return _field_dict(f, disp)
+    e = Sift3DError("sift3d_read_field(%s) -> %d" % (path, rc))
+    e.code = rc
+    raise e
 
 
 def _map12(m):

@@ -21,6 +21,8 @@
  * the Hough transform is refined by guided re-matching and least-squares fits (sift3d_refine_similarity).  The refined
  * transform goes to .trans.txt / .trans-inverse.txt, the kept pairs to the three match files, their count to the
  * "inliers" line's second field (the reference's iInliers2, 0 without -e), and one line per round to <moving>.refine.txt.
+ * -a -e -u[<h>] adds a displacement field over the refined transform (sift3d_refine_field; node
+ * spacing h key units, default 4): <moving>.field.nii and its report <moving>.field.txt.  Every other file is as -a -e's.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -39,6 +41,7 @@ static void usage(void)
     printf("  <output transform>: output text file with linear transform from keys 2 -> keys 1.\n");
     printf("  -a: align keys 2, 3, ... to keys 1 (ratio matching + Hough similarity; default: all-to-all votes).\n");
     printf("  -e: with -a, refine each alignment by guided re-matching and a least-squares similarity.\n");
+    printf("  -u[<h>]: with -a -e, fit a displacement field over the refined alignment (node spacing h, default 4).\n");
 }
 
 typedef struct {
@@ -130,8 +133,60 @@ static int refine(const char *name, const key_set *fixed, const key_set *moving,
     return fclose(f) == 0 ? 0 : -1;
 }
 
-/* one matchAllToOne pass (featMatchMultiple.cpp:148-390): image 0 fixed, every other image aligned to it (and refined: -e) */
-static int align_all(char **names, key_set *sets, int n_sets, int device, int expand)
+/* -u: the displacement field over the refined t, to <name>.field.nii and its report to <name>.field.txt */
+static int fit_field(const char *name, const key_set *fixed, const key_set *moving, const sift3d_similarity *t, float spacing, int device)
+{
+    char err[256] = "";
+    sift3d_field_params p;
+    sift3d_field_defaults(&p);
+    if (spacing > 0) p.spacing = spacing;
+    /* the grid of all fixed positions bounds the grid of any set of samples (their fixed sides) */
+    float *pos = (float *)malloc(sizeof(float) * 3 * (size_t)(fixed->n > 0 ? fixed->n : 1));
+    if (!pos) return -1;
+    for (int64_t i = 0; i < fixed->n; i++) {
+        pos[3 * i] = fixed->f[i].x;
+        pos[3 * i + 1] = fixed->f[i].y;
+        pos[3 * i + 2] = fixed->f[i].z;
+    }
+    sift3d_field f;
+    memset(&f, 0, sizeof f);
+    int rc = sift3d_field_size(pos, fixed->n, &p, &f);
+    free(pos);
+    if (rc != SIFT3D_OK) {
+        printf("Error: the displacement field of %s needs too many nodes\n", name);
+        return -1;
+    }
+    f.capacity = 3 * f.n[0] * f.n[1] * f.n[2];
+    f.disp = (float *)malloc(sizeof(float) * (size_t)f.capacity);
+    if (!f.disp) return -1;
+    sift3d_field_report rep;
+    if (sift3d_refine_field(device, fixed->f, fixed->n, moving->f, moving->n, t, &p, &f, &rep, err, sizeof err) != SIFT3D_OK) {
+        printf("Error: displacement field of %s failed: %s\n", name, err);
+        free(f.disp);
+        return -1;
+    }
+    char *path = (char *)malloc(strlen(name) + 16);
+    if (!path) {
+        free(f.disp);
+        return -1;
+    }
+    sprintf(path, "%s.field.nii", name);
+    rc = sift3d_write_field(path, &f);
+    free(f.disp);
+    sprintf(path, "%s.field.txt", name);
+    FILE *o = rc == 0 ? fopen(path, "wt") : NULL;
+    free(path);
+    if (!o) return -1;
+    fprintf(o, "# nodes %lld %lld %lld spacing %f origin %f %f %f radius %f lambda %f\n", (long long)f.n[0], (long long)f.n[1], (long long)f.n[2],
+            f.spacing, f.origin[0], f.origin[1], f.origin[2], p.radius, p.lambda);
+    fprintf(o, "# accepted kept rms_before rms_after max_disp folds\n");
+    fprintf(o, "%d\t%d\t%f\t%f\t%f\t%lld\n", rep.accepted, rep.kept, rep.rms_before, rep.rms_after, rep.max_disp, (long long)rep.folds);
+    return fclose(o) == 0 ? 0 : -1;
+}
+
+/* one matchAllToOne pass (featMatchMultiple.cpp:148-390): image 0 fixed, every other image aligned to it (and refined: -e;
+ * and a displacement field: -u, field_spacing > 0 or -1 for the default) */
+static int align_all(char **names, key_set *sets, int n_sets, int device, int expand, float field_spacing)
 {
     enum { MAX_MATCHES = 3000 }; /* MatchKeys' iMaxMatches */
     int32_t mi[MAX_MATCHES], fi[MAX_MATCHES], in[MAX_MATCHES], d2[MAX_MATCHES], *pairs = NULL;
@@ -159,6 +214,11 @@ static int align_all(char **names, key_set *sets, int n_sets, int device, int ex
                 return -1;
             }
             refined = t.inliers;
+            if (field_spacing != 0 && fit_field(names[i], &sets[0], &sets[i], &t, field_spacing, device) != 0) {
+                free(path);
+                free(pairs);
+                return -1;
+            }
         }
         path = (char *)realloc(path, strlen(names[i]) + 32);
         if (!path) {
@@ -204,6 +264,7 @@ int main(int argc, char **argv)
         fclose(cf);
     }
     int a = 1, only_reoriented = 1, peaks_mode = 4, neighbours = 5, align = 0, expand = 0;
+    float field_spacing = 0; /* -u: -1 (the default spacing) or the given one */
     const char *report = "report.txt", *list_file = NULL;
     while (a < argc && argv[a][0] == '-') {
         switch (argv[a][1]) {
@@ -238,6 +299,19 @@ int main(int argc, char **argv)
             if (a >= argc) { usage(); return -1; }
             list_file = argv[a++];
             break;
+        case 'u': case 'U': {
+            field_spacing = -1;
+            if (argv[a][2]) {
+                char *end = NULL;
+                field_spacing = strtof(argv[a] + 2, &end);
+                if (*end != 0 || !(field_spacing > 0) || field_spacing > 1e30f) {
+                    printf("Error: bad node spacing: %s\n", argv[a]);
+                    return -1;
+                }
+            }
+            a++;
+            break;
+        }
         default:
             printf("Error: unknown command line argument: %s\n", argv[a]);
             return -1;
@@ -245,6 +319,10 @@ int main(int argc, char **argv)
     }
     if (expand && !align) {
         printf("Error: -e refines an alignment and needs -a\n");
+        return -1;
+    }
+    if (field_spacing != 0 && !expand) {
+        printf("Error: -u fits a displacement field over a refined alignment and needs -a -e\n");
         return -1;
     }
     if (neighbours < 1 || neighbours > 32) {
@@ -335,10 +413,10 @@ int main(int argc, char **argv)
     /* -s2: all three passes append to matching_votes.txt / vote_count.txt (featMatchMultiple.cpp:58-65: "at" whenever
      * bOnlyPeaksFeatures == 2, the first pass included) */
     if (align) {
-        int rc = align_all(names, sets, n_read, 0, expand);
+        int rc = align_all(names, sets, n_read, 0, expand, field_spacing);
         if (rc == 0 && peaks_mode == 2) {
-            rc = align_all(names, peaks, n_read, 0, expand);
-            if (rc == 0) rc = align_all(names, valleys, n_read, 0, expand);
+            rc = align_all(names, peaks, n_read, 0, expand, field_spacing);
+            if (rc == 0) rc = align_all(names, valleys, n_read, 0, expand, field_spacing);
         }
         return rc == 0 ? 0 : -1;
     }

@@ -9,6 +9,8 @@
  * x + 0.5 by default, and at qto_xyz / sto_xyz . (x + 0.5 f) under featExtract -w / -ws, f = min(voxel) / voxel
  * (sift3d_key_vox2key; tests/test_resample_cpu.py pins both forms on the oracle's extraction).  Keys of -2+ / -2-
  * extractions are not supported.  The output is float32 with the fixed image's dims, voxel sizes, qform and sform.
+ * -u <moving.field.nii>: through the transform and the displacement field featMatchMultiple -a -e -u wrote
+ * (sift3d_resample_field).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -31,6 +33,7 @@ static void print_options(void)
     printf("  -n         : nearest-neighbour interpolation (label maps; default is trilinear).\n");
     printf("  -f<value>  : value of output voxels that map outside the moving image (default 0).\n");
     printf("  -d[0-9]    : set device id to be used.\n");
+    printf("  -u <field> : also through the displacement field featMatchMultiple -a -e -u wrote (<moving>.field.nii).\n");
 }
 
 /* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
@@ -51,6 +54,7 @@ int main(int argc, char **argv)
 {
     int device = 0, world_mode = 0, interp = SIFT3D_INTERP_LINEAR;
     float fill = 0.0f;
+    const char *field_path = NULL;
     int arg = 1;
     while (arg < argc && argv[arg][0] == '-') {
         switch (argv[arg][1]) {
@@ -79,6 +83,14 @@ int main(int argc, char **argv)
                 return -1;
             }
             device = argv[arg][2] - '0';
+            break;
+        case 'u':
+            if (argv[arg][2] != 0 || arg + 1 >= argc) {
+                printf("Error: -u needs a field file\n");
+                print_options();
+                return -1;
+            }
+            field_path = argv[++arg];
             break;
         default:
             printf("Error: unknown command line argument: %s\n", argv[arg]);
@@ -130,9 +142,26 @@ int main(int argc, char **argv)
     }
     char err[512] = "";
     double ms = 0;
+    sift3d_field field;
+    memset(&field, 0, sizeof field);
+    if (field_path) {
+        int frc = sift3d_read_field(field_path, &field);
+        if (frc == SIFT3D_ERR_CAPACITY) {
+            field.capacity = 3 * field.n[0] * field.n[1] * field.n[2];
+            field.disp = (float *)malloc(sizeof(float) * (size_t)field.capacity);
+            frc = field.disp ? sift3d_read_field(field_path, &field) : SIFT3D_ERR_MEMORY;
+        }
+        if (frc != SIFT3D_OK) {
+            printf("Error: could not read displacement field file: %s\n", field_path);
+            return -1;
+        }
+    }
     /* the first volume of a 4-D moving image */
-    const int rc = sift3d_resample_affine(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map, interp,
-                                          fill, &ms, err, sizeof err);
+    const int rc = field_path ? sift3d_resample_field(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map,
+                                                      fv, mv, &field, interp, fill, &ms, err, sizeof err)
+                              : sift3d_resample_affine(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map,
+                                                       interp, fill, &ms, err, sizeof err);
+    free(field.disp);
     if (rc != SIFT3D_OK) {
         printf("Error: could not resample: %s\n", err);
         return -1;

@@ -496,3 +496,106 @@ void nifti_min_free(nifti_min_image *img)
     free(img->data);
     img->data = 0;
 }
+
+/* ---- displacement fields: a header of their own, written and read by these two only ---------------------------------- */
+#define FIELD_INTENT 1006 /* NIFTI_INTENT_DISPVECT */
+
+static void field_hdr(unsigned char h[352], const int n[3], float spacing, const float origin[3], const char *descrip)
+{
+    memset(h, 0, 352);
+    int32_t sz = 348;
+    memcpy(h, &sz, 4);
+    int16_t dim[8] = {5, (int16_t)n[0], (int16_t)n[1], (int16_t)n[2], 1, 3, 1, 1};
+    memcpy(h + 40, dim, 16);
+    int16_t intent = FIELD_INTENT, dt = 16, bp = 32, code = 2;
+    memcpy(h + 68, &intent, 2);
+    memcpy(h + 70, &dt, 2);
+    memcpy(h + 72, &bp, 2);
+    float pixdim[8] = {1.0f, spacing, spacing, spacing, 1.0f, 1.0f, 1.0f, 1.0f};
+    memcpy(h + 76, pixdim, 32);
+    float vo = 352.0f, slope = 1.0f;
+    memcpy(h + 108, &vo, 4);
+    memcpy(h + 112, &slope, 4);
+    strncpy((char *)h + 148, descrip ? descrip : "", 79);
+    memcpy(h + 252, &code, 2);
+    memcpy(h + 254, &code, 2);
+    memcpy(h + 268, origin, 12); /* qoffset_x, y, z; quatern_b, c, d = 0: no rotation */
+    float srow[12] = {spacing, 0, 0, origin[0], 0, spacing, 0, origin[1], 0, 0, spacing, origin[2]};
+    memcpy(h + 280, srow, 48);
+    memcpy(h + 344, "n+1", 4);
+}
+
+int nifti_min_write_field(const char *path, const float *disp, const int n[3], float spacing, const float origin[3], const char *descrip)
+{
+    for (int k = 0; k < 3; k++)
+        if (n[k] < 1 || n[k] > 32767) return -1;
+    unsigned char h[352];
+    field_hdr(h, n, spacing, origin, descrip);
+    const size_t bytes = (size_t)n[0] * n[1] * n[2] * 3 * sizeof(float);
+    if (ends_with(path, ".gz")) {
+        gzFile f = gzopen(path, "wb1");
+        if (!f) return -1;
+        int ok = gzwrite(f, h, 352) == 352;
+        size_t put = 0;
+        while (ok && put < bytes) {
+            unsigned chunk = (bytes - put) > (1u << 30) ? (1u << 30) : (unsigned)(bytes - put);
+            if (gzwrite(f, (const unsigned char *)disp + put, chunk) <= 0) break;
+            put += chunk;
+        }
+        return gzclose(f) == Z_OK && ok && put == bytes ? 0 : -1;
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) return -1;
+    int ok = fwrite(h, 1, 352, f) == 352 && fwrite(disp, 1, bytes, f) == bytes;
+    return fclose(f) == 0 && ok ? 0 : -1;
+}
+
+int nifti_min_read_field(const char *path, int n[3], float *spacing, float origin[3], float *disp, size_t capacity)
+{
+    unsigned char h[352], want[352];
+    gzFile f = gzopen(path, "rb");
+    if (!f) return -1;
+    if (gzread(f, h, 352) != 352) {
+        gzclose(f);
+        return -2;
+    }
+    /* what the writer would write for this grid and this description, byte for byte */
+    float o[3], sp = rdf(h, 80, 0);
+    int16_t d[3];
+    for (int k = 0; k < 3; k++) {
+        d[k] = rd16(h, 42 + 2 * k, 0);
+        n[k] = d[k];
+        o[k] = rdf(h, 268 + 4 * k, 0);
+    }
+    char descrip[80];
+    memcpy(descrip, h + 148, 79);
+    descrip[79] = 0;
+    int bad = n[0] < 2 || n[1] < 2 || n[2] < 2 || !(sp > 0) || !isfinite(sp) || !isfinite(o[0]) || !isfinite(o[1]) || !isfinite(o[2]);
+    if (!bad) {
+        field_hdr(want, n, sp, o, descrip);
+        memcpy(want + 148, h + 148, 80); /* the description is free text */
+        bad = memcmp(h, want, 352) != 0;
+    }
+    if (bad) {
+        gzclose(f);
+        return -2;
+    }
+    *spacing = sp;
+    memcpy(origin, o, sizeof o);
+    const size_t nf = (size_t)n[0] * n[1] * n[2] * 3;
+    if (!disp || capacity < nf) {
+        gzclose(f);
+        return -3;
+    }
+    size_t got = 0, bytes = nf * sizeof(float);
+    while (got < bytes) {
+        unsigned chunk = (bytes - got) > (1u << 30) ? (1u << 30) : (unsigned)(bytes - got);
+        int r = gzread(f, (unsigned char *)disp + got, chunk);
+        if (r <= 0) break;
+        got += (size_t)r;
+    }
+    unsigned char extra;
+    const int more = got == bytes && gzread(f, &extra, 1) == 1;
+    gzclose(f);
+    return got == bytes && !more ? 0 : -2;
+}

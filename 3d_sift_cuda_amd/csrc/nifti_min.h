@@ -53,6 +53,13 @@ int nifti_min_write_f32_ex(const char *path, const float *data, int nx, int ny, 
  * the output on that image.  Returns 0 or -1. */
 int nifti_min_write_f32_geom(const char *path, const float *data, const char *geom_path);
 void nifti_min_free(nifti_min_image *img);
+/* A displacement field: float32 single-file .nii (or .nii.gz), dim (5, n0, n1, n2, 1, 3), intent_code
+ * 1006 (DISPVECT), pixdim (1, h, h, h), qform and sform (codes 2) mapping node index -> position: diagonal h, offset origin,
+ * no rotation; disp component-major (3 volumes of n0 n1 n2, x fastest).  n up to 32767 per axis.  Returns 0 or -1. */
+int nifti_min_write_field(const char *path, const float *disp, const int n[3], float spacing, const float origin[3], const char *descrip);
+/* Reads exactly what nifti_min_write_field writes (the description aside).  Fills n, spacing and origin, then the 3 n0 n1 n2
+ * floats when capacity allows.  0; -1 cannot open; -2 not such a file (another header, a short or long file); -3 capacity. */
+int nifti_min_read_field(const char *path, int n[3], float *spacing, float origin[3], float *disp, size_t capacity);
 
 #ifdef __cplusplus
 }

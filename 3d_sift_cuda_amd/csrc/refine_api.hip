@@ -10,6 +10,7 @@
 
 #include "align_math.h"
 #include "device_call.h"
+#include "guided_accept.h"
 
 /* What the index and the loop read of a record set, compact: one pass over the 332-byte records converts the descriptors
  * (sift3d_match_descriptors' accepted set -- whole numbers 0..127 -- without its early exit, so the inner loop vectorises; NaN
@@ -356,22 +357,8 @@ extern "C" int sift3d_refine_similarity(int device, const sift3d_feature *fixed,
             if (rc != SIFT3D_OK) return rc;
             for (size_t m = 0; m < M; m++) R.visited += vis[m];
             /* accept by the ratio test; one pair per fixed record: the least (d1, moving index) */
-            std::fill(best.begin(), best.end(), -1);
-            std::vector<char> acc(M, 0);
-            for (size_t m = 0; m < M; m++) {
-                if (i1[m] < 0) continue;
-                if (!(i2[m] < 0 || (int64_t)p.ratio_num * d2[m] > (int64_t)p.ratio_den * d1[m])) continue;
-                acc[m] = 1;
-                int32_t &b = best[i1[m]];
-                if (b < 0 || d1[m] < d1[b]) b = (int32_t)m; /* m ascending: a tie keeps the lower index */
-            }
             std::vector<int32_t> pm, pf, pd;
-            for (size_t m = 0; m < M; m++)
-                if (acc[m] && best[i1[m]] == (int32_t)m) {
-                    pm.push_back((int32_t)m);
-                    pf.push_back(i1[m]);
-                    pd.push_back(d1[m]);
-                }
+            guided_accept(M, i1.data(), d1.data(), i2.data(), d2.data(), p.ratio_num, p.ratio_den, best, pm, pf, pd);
             R.accepted = (int32_t)pm.size();
             sift3d_similarity t1 = cur;
             if (fit_pairs(FS, MS, pm, pf, &t1) != 0) {

@@ -648,6 +648,104 @@ int sift3d_resample_map(const float moving_to_fixed[16], const float fixed_vox2k
  * Keys of -2+ / -2- extractions follow neither form. */
 void sift3d_key_vox2key(const float voxel[3], const float world[16], float m[16]);
 
+/* ---- nonrigid alignment: a keypoint displacement field (featMatchMultiple -a -e -u, featResample -u; beyond the reference) ---
+ * DESIGN.md section 7e states the contract; tests/field_oracle.c restates the fit and the warp.  T is the refined similarity
+ * (moving key -> fixed key, the .trans.txt).  The field is backward: at a fixed key position y the moving key position is
+ * phi(y) = T^-1(y) + v(y).  v lives on a node grid in fixed key space, its values in moving key units.  Node (a, b, c) sits at
+ * (origin[0] + (float)a * spacing, origin[1] + (float)b * spacing, origin[2] + (float)c * spacing), computed in float.
+ * Everything outside the grid has v = 0; the grid reaches the support radius past every sample, so its border is 0. */
+typedef struct {
+    int64_t n[3];      /* nodes per axis, 2 .. 2^24 each */
+    float origin[3];   /* key position of node (0, 0, 0) */
+    float spacing;     /* h */
+    int64_t capacity;  /* floats disp holds (0: not filled); at least 3 n0 n1 n2 to be filled */
+    float *disp;       /* component-major: disp[comp * N + (c * n1 + b) * n0 + a], N = n0 n1 n2 */
+} sift3d_field;
+
+typedef struct {
+    float spacing;           /* h: 4 key units */
+    float radius;            /* R, the support radius of the triweight kernel: 20 */
+    float lambda;            /* pseudo-weight of zero displacement at every node: 0.1 */
+    float search_radius;     /* sift3d_refine_field's guided search radius: 8; must exceed the largest displacement to capture */
+    float min_tol;           /* the trim keeps e <= max(min_tol, 3 x the lower median of e): 1.0 */
+    int32_t ratio_num;       /* 4: accept when i2 == -1 or ratio_num * d2 > ratio_den * d1 (sift3d_refine_similarity's rule) */
+    int32_t ratio_den;       /* 5 */
+    int64_t max_nodes;       /* 2^26: grids with more nodes are refused */
+    int64_t index_cells_max; /* 2^26: the guided search's index form (sift3d_refine_params) */
+} sift3d_field_params;
+void sift3d_field_defaults(sift3d_field_params *p);
+
+/* Samples |v_c| above this bound are refused: with at most 2^31 samples of weight <= 1 no int64 sum can overflow
+ * (2^31 * (2^7 * 2^24 + 1) < 2^63). */
+#define SIFT3D_FIELD_MAX_DISP 128.0f
+
+/* The grid of a sample set (y: n key positions, 3 floats each; samples with a non-finite component are skipped): per axis
+ * o = (float)(min y - R) in double (min and max 0 where no sample is finite), n = floor((max - min + 2R) / h) + 2.  Fills
+ * f->n, origin and spacing; nothing else.  SIFT3D_ERR_ARG for bad parameters (h, R > 0 and finite, lambda >= 0) or a grid
+ * of more than p->max_nodes nodes or more than 2^24 along an axis.  The grid of a superset is at least as large on every
+ * axis: the fixed records' positions give a capacity for any pairing of them. */
+int sift3d_field_size(const float *y, int64_t n, const sift3d_field_params *p, sift3d_field *f);
+
+/* The samples of accepted pairs (fixed position p_fixed[i], moving position p_moving[i], 3 floats each): y_i = p_fixed[i],
+ * v_i = p_moving[i] - T^-1(p_fixed[i]) with T^-1(y) = center0 + rot^T (y - center1) / scale in double (rows summed
+ * ((r0 d0 + r1 d1) + r2 d2)), rounded to float once. */
+void sift3d_field_samples(const sift3d_similarity *t, const float *p_fixed, const float *p_moving, int64_t n, float *y, float *v);
+
+/* One fit on the GPU (field_fit_kernel) over the grid of sift3d_field_size.  At node P and for every finite sample:
+ * dx = y.x - P.x (float), d2 = ((dx dx + dy dy) + dz dz); only d2 < R R counts: t = 1 - d2 / (R R), w = (t t) t;
+ * W += rint(w 2^24), V_c += rint((w v_c) 2^24) in int64, so the sums are exact and order-free; the node's value is
+ * (float)((double)V_c / ((double)W + lambda 2^24)), 0 where that denominator is 0.  f->capacity < 3N: SIFT3D_ERR_CAPACITY
+ * with the grid filled in.  A finite |v_c| > SIFT3D_FIELD_MAX_DISP: SIFT3D_ERR_ARG.  *kernel_ms (may be NULL): device time. */
+int sift3d_fit_field(int device, const float *y, const float *v, int64_t n, const sift3d_field_params *p, sift3d_field *f, double *kernel_ms,
+                     char *err, int64_t err_len);
+
+typedef struct {
+    int32_t accepted;  /* pairs the ratio test accepted, one per fixed record: the samples of the first pass */
+    int32_t kept;      /* samples the trim kept: the second pass */
+    double rms_before; /* RMS of e_i = |v_i - v(y_i)| over the accepted samples under the first pass */
+    double rms_after;  /* RMS of e_i over the kept samples under the second pass */
+    double max_disp;   /* largest |v| over the nodes of the result */
+    int64_t folds;     /* nodes where det grad phi <= 0 (sift3d_field_folds) */
+    double search_ms;  /* device time of the guided search kernel */
+    double fit_ms[2];  /* device time of the fit kernel, first and second pass */
+} sift3d_field_report;
+
+/* Search, accept, fit, trim, refit: one sift3d_guided_search at t with p->search_radius; the accept rule of
+ * sift3d_refine_similarity (ratio test, the least (d1, moving index) per fixed record); the samples of sift3d_field_samples;
+ * a fit over them on their grid; e_i = |v_i - v(y_i)| (sift3d_field_eval, double norm); keep e_i <= max(min_tol, 3 x the
+ * lower median); a second fit over the kept samples on the same grid.  t: the refined similarity (its arrays are not read).
+ * out: capacity as sift3d_fit_field (SIFT3D_ERR_CAPACITY with the grid filled in).  p NULL: defaults.  rep may be NULL. */
+int sift3d_refine_field(int device, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving,
+                        const sift3d_similarity *t, const sift3d_field_params *p, sift3d_field *out, sift3d_field_report *rep, char *err,
+                        int64_t err_len);
+
+/* sift3d_resample_affine through T and a field (field_warp_kernel).  Per output voxel p: q = map p (section 7c's order);
+ * kappa = C p in the same order, C the first three rows of fixed_vox2key; g = (kappa - origin) / spacing per axis (float
+ * divide); where 0 <= g <= n - 1 on every axis, v = the trilinear interpolation of the nodes (section 7c's floor, weights, clamp
+ * and x -> y -> z order, per component), else v = 0 and q is left as it is; q_r += ((K[r][0] v0 + K[r][1] v1) + K[r][2] v2),
+ * K the linear part of inv(moving_vox2key) (sift3d_field_warp_terms); then section 7c's inside test, gather and fill.  A zero
+ * field gives the bytes of sift3d_resample_affine.  vox2key NULL: identity.  *kernel_ms (may be NULL): device time. */
+int sift3d_resample_field(int device, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy, int64_t oz,
+                          const float map[12], const float fixed_vox2key[16], const float moving_vox2key[16], const sift3d_field *field, int interp,
+                          float fill, double *kernel_ms, char *err, int64_t err_len);
+
+/* Host helpers (also in libsift3d_host.so).
+ * C (3 x 4, the first rows of fixed_vox2key) and K (3 x 3, the linear part of inv(moving_vox2key) in double, rounded to float
+ * once) of sift3d_resample_field.  Returns 0, or -1 when a last row is not 0 0 0 1 or moving_vox2key is singular. */
+int sift3d_field_warp_terms(const float fixed_vox2key[16], const float moving_vox2key[16], float c[12], float k[9]);
+/* v at n key positions y (3 floats each) into out (3 floats each): the interpolation of sift3d_resample_field, 0 outside. */
+void sift3d_field_eval(const sift3d_field *f, const float *y, int64_t n, float *out);
+/* Nodes where det grad phi <= 0: grad phi = rot^T / scale + grad v, grad v by central differences in double over 2h with
+ * v = 0 past the grid; *max_disp (may be NULL): the largest |v| over the nodes, in double. */
+int64_t sift3d_field_folds(const sift3d_similarity *t, const sift3d_field *f, double *max_disp);
+/* <moving>.field.nii: NIfTI-1 float32, dim (5, n0, n1, n2, 1, 3), intent_code 1006 (DISPVECT), pixdim h, qform and sform
+ * (codes 2, aligned) mapping node index -> key position (diagonal h, offset origin), descrip naming the convention.
+ * sift3d_write_field returns 0 or -1.
+ * sift3d_read_field accepts exactly what the writer writes: SIFT3D_ERR_ARG for anything else (another datatype, dim[5] != 3,
+ * a rotated or non-uniform matrix, a short file), SIFT3D_ERR_CAPACITY (the grid filled in) when f->capacity < 3N. */
+int sift3d_write_field(const char *path, const sift3d_field *f);
+int sift3d_read_field(const char *path, sift3d_field *f);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
