@@ -173,6 +173,8 @@ def hip_lib():
     _sig(L.sift3d_fit_field, I, I, P, P, I64, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_refine_field, I, I, P, I64, P, I64, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_resample_field, I, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, I, F, P, C.c_char_p, I64)
+    _sig(L.sift3d_block_match, I, I, P, P, I64, I64, I64, P, I64, P, I, I, I, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_refine_field_intensity, I, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -221,6 +223,12 @@ def host_lib():
     _sig(L.sift3d_field_folds, I64, P, P, P)
     _sig(L.sift3d_write_field, I, C.c_char_p, P)
     _sig(L.sift3d_read_field, I, C.c_char_p, P)
+    _sig(L.sift3d_blockmatch_defaults, None, P)
+    _sig(L.sift3d_blockmatch_range, I, P, I64, P, P)
+    _sig(L.sift3d_blockmatch_lattice, I, I64, I64, I64, P, P, P)
+    _sig(L.sift3d_blockmatch_grid, I, I64, I64, I64, P, P, P)
+    _sig(L.sift3d_blockmatch_samples, I64, P, I64, I64, I64, P, P, P, P, P, P, P)
+    _sig(L.sift3d_blockmatch_folds, I64, P, P, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -784,6 +792,160 @@ def read_field(path):
     e = Sift3DError("sift3d_read_field(%s) -> %d" % (path, rc))
     e.code = rc
     raise e
+
+
+# ---- intensity refinement of the field by block matching (featResample -i), DESIGN.md section 7f ----------------------------
+BLOCKMATCH_WORDS, BLOCKMATCH_NONE, BLOCKMATCH_MAX_ROUNDS = 16, 0xffffffff, 8
+
+
+class BlockmatchParams(C.Structure):
+    """sift3d_blockmatch_params"""
+    _fields_ = [("stride", C.c_int32), ("block", C.c_int32), ("search", C.c_int32), ("rounds", C.c_int32), ("variance_quantile", C.c_float),
+                ("cost_fraction", C.c_float), ("spacing", C.c_float), ("radius", C.c_float), ("lambda_", C.c_float), ("min_tol", C.c_float),
+                ("max_nodes", C.c_int64)]
+
+
+class BlockmatchRound(C.Structure):
+    """sift3d_blockmatch_round"""
+    _fields_ = [("nodes", C.c_int64), ("flagged", C.c_int64), ("gated_variance", C.c_int64), ("gated_border", C.c_int64),
+                ("gated_cost", C.c_int64), ("samples", C.c_int64), ("kept", C.c_int64), ("rms_before", C.c_double), ("rms_after", C.c_double),
+                ("max_disp", C.c_double), ("folds", C.c_int64), ("warp_ms", C.c_double), ("match_ms", C.c_double), ("fit_ms", C.c_double * 2)]
+
+
+class BlockmatchReport(C.Structure):
+    """sift3d_blockmatch_report"""
+    _fields_ = [("rounds", C.c_int32), ("empty_range", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
+                ("round", BlockmatchRound * BLOCKMATCH_MAX_ROUNDS)]
+
+
+def blockmatch_params(**kw):
+    """sift3d_blockmatch_defaults, then the given fields (stride, block, search, rounds, variance_quantile, cost_fraction, spacing,
+    radius, lam (lambda), min_tol, max_nodes)."""
+    p = BlockmatchParams()
+    host_lib().sift3d_blockmatch_defaults(C.byref(p))
+    for k, v in kw.items():
+        k = "lambda_" if k in ("lam", "lambda") else k
+        if k not in dict(BlockmatchParams._fields_):
+            raise ValueError("no block matching parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _m16(m):
+    """a 4 x 4 as 16 contiguous floats; a match_keys-style dict goes through similarity_matrix; None stays None"""
+    if m is None:
+        return None
+    if isinstance(m, dict):
+        m = similarity_matrix(m)
+    return np.ascontiguousarray(m, np.float32).reshape(16)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def blockmatch_range(vol):
+    """sift3d_blockmatch_range: (lo, hi) float32 of the quantisation, or None where vol has no two distinct finite values"""
+    v = np.ascontiguousarray(vol, np.float32)
+    lo, hi = C.c_float(0), C.c_float(0)
+    ok = host_lib().sift3d_blockmatch_range(v.ctypes.data, v.size, C.byref(lo), C.byref(hi))
+    return (np.float32(lo.value), np.float32(hi.value)) if ok else None
+
+
+def blockmatch_lattice(shape, **params):
+    """sift3d_blockmatch_lattice of a volume of shape (nz, ny, nx): (first (x, y, z), count (x, y, z)); raises where it is refused"""
+    nz, ny, nx = (int(d) for d in shape)
+    first, count = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+    if host_lib().sift3d_blockmatch_lattice(nx, ny, nz, C.byref(blockmatch_params(**params)), first, count) != 0:
+        raise Sift3DError("sift3d_blockmatch_lattice: parameters out of range, or the window is wider than the volume")
+    return tuple(first), tuple(count)
+
+
+def blockmatch_grid(shape, fixed_vox2key=None, **params):
+    """sift3d_blockmatch_grid: the output grid (dict n, origin, spacing) of a fixed volume of shape (nz, ny, nx)"""
+    nz, ny, nx = (int(d) for d in shape)
+    f = Field()
+    if host_lib().sift3d_blockmatch_grid(nx, ny, nz, _ptr(_m16(fixed_vox2key)), C.byref(blockmatch_params(**params)), C.byref(f)) != 0:
+        raise Sift3DError("sift3d_blockmatch_grid: bad parameters or too many nodes")
+    return {"n": tuple(int(x) for x in f.n), "origin": np.array(f.origin, np.float32), "spacing": np.float32(f.spacing)}
+
+
+def blockmatch_samples(words, shape, t, field=None, fixed_vox2key=None, **params):
+    """sift3d_blockmatch_samples: (y, v, counts) from the block search's words over the lattice of a volume of shape
+    (nz, ny, nx); counts = (flagged, gated by variance, by border, by cost); t: 4 x 4 or a match_keys-style dict"""
+    nz, ny, nx = (int(d) for d in shape)
+    w = np.ascontiguousarray(words, np.uint32).reshape(-1, BLOCKMATCH_WORDS)
+    _first, count = blockmatch_lattice(shape, **params)
+    if len(w) != count[0] * count[1] * count[2]:
+        raise ValueError("words do not cover the lattice")
+    y, v = np.empty((len(w), 3), np.float32), np.empty((len(w), 3), np.float32)
+    counts = (C.c_int64 * 4)()
+    fs, _keep = _field_struct(field) if field is not None else (None, None)
+    fv, m = _m16(fixed_vox2key), _m16(t)
+    n = host_lib().sift3d_blockmatch_samples(w.ctypes.data, nx, ny, nz, C.byref(blockmatch_params(**params)), _ptr(fv), m.ctypes.data,
+                                             C.byref(fs) if fs is not None else None, y.ctypes.data, v.ctypes.data, counts)
+    if n < 0:
+        raise Sift3DError("sift3d_blockmatch_samples: bad arguments")
+    return y[:n].copy(), v[:n].copy(), tuple(int(c) for c in counts)
+
+
+def blockmatch_folds(t, field):
+    """sift3d_blockmatch_folds: (nodes with det (L + grad v) <= 0, largest |v|); t: 4 x 4 or a match_keys-style dict"""
+    fs, _keep = _field_struct(field)
+    big = C.c_double(0.0)
+    n = host_lib().sift3d_blockmatch_folds(_m16(t).ctypes.data, C.byref(fs), C.byref(big))
+    return int(n), big.value
+
+
+def block_match(fixed, warped, first, stride, count, block, search, device=0, generic=False, return_ms=False):
+    """sift3d_block_match: the block search alone on the GPU.  fixed, warped: (nz, ny, nx) float32 on one grid; first, count:
+    (x, y, z).  generic: 0 the specialised kernel where there is one, 1 the form for any b, r, 2 the specialised form without packed
+    arithmetic (same words).  Returns uint32 words (count z, count y, count x, 16); return_ms=True returns (words, kernel_ms)."""
+    f, w = _f32(fixed), _f32(warped)
+    if f.shape != w.shape:
+        raise ValueError("fixed and warped differ in shape")
+    nz, ny, nx = f.shape
+    fi, cn = (C.c_int64 * 3)(*[int(x) for x in first]), (C.c_int64 * 3)(*[int(x) for x in count])
+    n = max(int(cn[0]), 0) * max(int(cn[1]), 0) * max(int(cn[2]), 0)
+    out = np.zeros((max(n, 1), BLOCKMATCH_WORDS), np.uint32)
+    ms = C.c_double(0.0)
+    _call("sift3d_block_match", int(device), f.ctypes.data, w.ctypes.data, nx, ny, nz, fi, int(stride), cn, int(block), int(search),
+          int(generic), out.ctypes.data, C.byref(ms))
+    out = out[:n].reshape(int(cn[2]), int(cn[1]), int(cn[0]), BLOCKMATCH_WORDS)
+    return (out, ms.value) if return_ms else out
+
+
+def _blockmatch_report_dict(r):
+    rounds = []
+    for k in range(BLOCKMATCH_MAX_ROUNDS):
+        q = r.round[k]
+        d = {name: getattr(q, name) for name, _ in BlockmatchRound._fields_ if name != "fit_ms"}
+        d["fit_ms"] = (float(q.fit_ms[0]), float(q.fit_ms[1]))
+        rounds.append(d)
+    return {"rounds": int(r.rounds), "empty_range": int(r.empty_range), "lo": np.float32(r.lo), "hi": np.float32(r.hi), "round": rounds}
+
+
+def refine_field_intensity(fixed, moving, t, field=None, fixed_vox2key=None, moving_vox2key=None, device=0, **params):
+    """sift3d_refine_field_intensity: refine a displacement field (a field dict, None: zero) from the fixed and the moving
+    volume (nz, ny, nx) by block matching.  t: the moving -> fixed key transform, 4 x 4 or a match_keys-style dict; vox2key
+    4 x 4 (None: identity); params: fields of blockmatch_params.  Returns (field dict, report dict)."""
+    f, m = _f32(fixed), _f32(moving)
+    fz, fy, fx = f.shape
+    mz, my, mx = m.shape
+    p = blockmatch_params(**params)
+    g = blockmatch_grid(f.shape, fixed_vox2key, **params)
+    cap = 3 * g["n"][0] * g["n"][1] * g["n"][2]
+    fs, _keep = _field_struct(field) if field is not None else (None, None)
+    if field is not None:
+        cap = max(cap, 3 * int(np.prod(field["n"])))
+    disp = np.zeros(cap, np.float32)
+    out = Field()
+    out.capacity, out.disp = disp.size, disp.ctypes.data
+    rep = BlockmatchReport()
+    fv, mv, tm = _m16(fixed_vox2key), _m16(moving_vox2key), _m16(t)
+    _call("sift3d_refine_field_intensity", int(device), f.ctypes.data, fx, fy, fz, m.ctypes.data, mx, my, mz, _ptr(fv), _ptr(mv),
+          tm.ctypes.data, C.byref(fs) if fs is not None else None, C.byref(p), C.byref(out), C.byref(rep))
+    return _field_dict(out, disp), _blockmatch_report_dict(rep)
 
 
 def _map12(m):

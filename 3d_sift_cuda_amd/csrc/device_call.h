@@ -87,5 +87,9 @@ struct device_call {
         if (rc_ != SIFT3D_OK) return rc_;                     \
     } while (0)
 
+/* field_api.hip: one fit of the samples y, v (n x 3 floats, host) on the grid g into disp (3 N floats, host) */
+int fit_on_grid(device_call &dc, const float *y, const float *v, int64_t n, const sift3d_field &g, float R, float lambda, float *disp,
+                double *kernel_ms);
+
 #pragma GCC visibility pop
 #endif

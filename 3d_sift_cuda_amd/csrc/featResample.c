@@ -11,6 +11,9 @@
  * extractions are not supported.  The output is float32 with the fixed image's dims, voxel sizes, qform and sform.
  * -u <moving.field.nii>: through the transform and the displacement field featMatchMultiple -a -e -u wrote
  * (sift3d_resample_field).
+ * -i[<rounds>]: refine the field (-u's, or zero) from the two images by block matching first
+ * (sift3d_refine_field_intensity; default 2 rounds), write it to <output image>.field.nii and its
+ * report to <output image>.field.txt, and resample through it.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +37,8 @@ static void print_options(void)
     printf("  -f<value>  : value of output voxels that map outside the moving image (default 0).\n");
     printf("  -d[0-9]    : set device id to be used.\n");
     printf("  -u <field> : also through the displacement field featMatchMultiple -a -e -u wrote (<moving>.field.nii).\n");
+    printf("  -i[rounds] : refine the field (-u's, or zero) from the image intensities by block matching (default 2 rounds),\n");
+    printf("               write <output image>.field.nii and .field.txt, and resample through the refined field.\n");
 }
 
 /* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
@@ -50,11 +55,41 @@ static void world_matrix(nifti_min_image *img, int world_mode, float m[16])
     m[15] = 1.0f;
 }
 
+/* -i: the refined field to <out>.field.nii, its grid and the report of every round to <out>.field.txt */
+static int write_refined(const char *out_path, const sift3d_field *f, const sift3d_blockmatch_params *p, const sift3d_blockmatch_report *rep)
+{
+    char *path = (char *)malloc(strlen(out_path) + 16);
+    if (!path) return -1;
+    sprintf(path, "%s.field.nii", out_path);
+    if (sift3d_write_field(path, f) != 0) {
+        free(path);
+        return -1;
+    }
+    sprintf(path, "%s.field.txt", out_path);
+    FILE *o = fopen(path, "w");
+    free(path);
+    if (!o) return -1;
+    fprintf(o, "# nodes %lld %lld %lld spacing %f origin %f %f %f radius %f lambda %f\n", (long long)f->n[0], (long long)f->n[1], (long long)f->n[2],
+            f->spacing, f->origin[0], f->origin[1], f->origin[2], p->radius, p->lambda);
+    fprintf(o, "# stride %d block %d search %d rounds %d variance_quantile %f cost_fraction %f quantised over %g .. %g%s\n", p->stride, p->block,
+            p->search, p->rounds, p->variance_quantile, p->cost_fraction, rep->lo, rep->hi,
+            rep->empty_range ? " (empty: nothing matched)" : "");
+    fprintf(o, "# round nodes samples kept flagged gated_variance gated_border gated_cost rms_before rms_after max_disp folds\n");
+    for (int k = 0; k < rep->rounds; k++) {
+        const sift3d_blockmatch_round *r = &rep->round[k];
+        fprintf(o, "%d\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%f\t%f\t%f\t%lld\n", k + 1, (long long)r->nodes, (long long)r->samples,
+                (long long)r->kept, (long long)r->flagged, (long long)r->gated_variance, (long long)r->gated_border, (long long)r->gated_cost,
+                r->rms_before, r->rms_after, r->max_disp, (long long)r->folds);
+    }
+    return fclose(o);
+}
+
 int main(int argc, char **argv)
 {
     int device = 0, world_mode = 0, interp = SIFT3D_INTERP_LINEAR;
     float fill = 0.0f;
     const char *field_path = NULL;
+    int intensity = 0, rounds = -1;
     int arg = 1;
     while (arg < argc && argv[arg][0] == '-') {
         switch (argv[arg][1]) {
@@ -84,6 +119,19 @@ int main(int argc, char **argv)
             }
             device = argv[arg][2] - '0';
             break;
+        case 'i':
+            intensity = 1;
+            if (argv[arg][2] != 0) {
+                char *end = NULL;
+                const long v = strtol(argv[arg] + 2, &end, 10);
+                if (*end != 0 || v < 0 || v > SIFT3D_BLOCKMATCH_MAX_ROUNDS) {
+                    printf("Error: bad number of rounds: %s\n", argv[arg]);
+                    print_options();
+                    return -1;
+                }
+                rounds = (int)v;
+            }
+            break;
         case 'u':
             if (argv[arg][2] != 0 || arg + 1 >= argc) {
                 printf("Error: -u needs a field file\n");
@@ -112,6 +160,10 @@ int main(int argc, char **argv)
         return -1;
     }
     nifti_min_close(fs);
+    if (intensity && nifti_min_read(fixed_path, &fixed) != 0) { /* -i matches against the fixed image's voxels */
+        printf("Error: could not read input file: %s\n", fixed_path);
+        return -1;
+    }
     if (nifti_min_read(moving_path, &moving) != 0) {
         printf("Error: could not read input file: %s\n", moving_path);
         return -1;
@@ -156,11 +208,40 @@ int main(int argc, char **argv)
             return -1;
         }
     }
+    if (intensity) {
+        sift3d_blockmatch_params bp;
+        sift3d_blockmatch_defaults(&bp);
+        if (rounds >= 0) bp.rounds = rounds;
+        sift3d_blockmatch_report rep;
+        sift3d_field refined;
+        memset(&refined, 0, sizeof refined);
+        int irc = sift3d_refine_field_intensity(device, fixed.data, fixed.nx, fixed.ny, fixed.nz, moving.data, moving.nx, moving.ny, moving.nz, fv, mv,
+                                                t, field_path ? &field : NULL, &bp, &refined, &rep, err, sizeof err);
+        if (irc == SIFT3D_ERR_CAPACITY) {
+            refined.capacity = 3 * refined.n[0] * refined.n[1] * refined.n[2];
+            if (field_path && field.capacity > refined.capacity) refined.capacity = field.capacity;
+            refined.disp = (float *)malloc(sizeof(float) * (size_t)refined.capacity);
+            irc = refined.disp ? sift3d_refine_field_intensity(device, fixed.data, fixed.nx, fixed.ny, fixed.nz, moving.data, moving.nx, moving.ny,
+                                                               moving.nz, fv, mv, t, field_path ? &field : NULL, &bp, &refined, &rep, err, sizeof err)
+                               : SIFT3D_ERR_MEMORY;
+        }
+        if (irc != SIFT3D_OK) {
+            printf("Error: could not refine the field: %s\n", err);
+            return -1;
+        }
+        if (write_refined(out_path, &refined, &bp, &rep) != 0) {
+            printf("Error: could not write the field files of: %s\n", out_path);
+            return -1;
+        }
+        free(field.disp);
+        field = refined;
+    }
     /* the first volume of a 4-D moving image */
-    const int rc = field_path ? sift3d_resample_field(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map,
-                                                      fv, mv, &field, interp, fill, &ms, err, sizeof err)
-                              : sift3d_resample_affine(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map,
-                                                       interp, fill, &ms, err, sizeof err);
+    const int rc = field_path || intensity
+                       ? sift3d_resample_field(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map, fv, mv,
+                                               &field, interp, fill, &ms, err, sizeof err)
+                       : sift3d_resample_affine(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map,
+                                                interp, fill, &ms, err, sizeof err);
     free(field.disp);
     if (rc != SIFT3D_OK) {
         printf("Error: could not resample: %s\n", err);

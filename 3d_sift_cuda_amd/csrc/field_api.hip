@@ -36,8 +36,9 @@ static const char *check_samples(const float *v, int64_t n)
 /* One fit on the grid g (n, origin, spacing) into disp (3 N floats, host).  The finite samples (all six components) are
  * binned into a uniform grid of cells of edge R (1 + 2^-10) over their bounding box, widened until an axis has at most 2^20
  * cells and the grid at most 2^24: a passing sample is less than R from the node on every axis (plus float rounding, which
- * the margin covers), so the 27 cells around the node's cell hold it. */
-static int fit_on_grid(device_call &dc, const float *y, const float *v, int64_t n, const sift3d_field &g, float R, float lambda, float *disp,
+ * the margin covers), so the 27 cells around the node's cell hold it.  Shared with blockmatch_api.hip (declared in
+ * device_call.h). */
+int fit_on_grid(device_call &dc, const float *y, const float *v, int64_t n, const sift3d_field &g, float R, float lambda, float *disp,
                        double *kernel_ms)
 {
     std::vector<int64_t> keep;

@@ -746,6 +746,105 @@ int64_t sift3d_field_folds(const sift3d_similarity *t, const sift3d_field *f, do
 int sift3d_write_field(const char *path, const sift3d_field *f);
 int sift3d_read_field(const char *path, sift3d_field *f);
 
+/* ---- intensity refinement of the displacement field by block matching (featResample -i; beyond the reference) -------------
+ * DESIGN.md section 7f states the contract; tests/blockmatch_oracle.c restates the block search as a serial brute force.
+ *
+ * The block search.  F (fixed) and W (the moving image already warped onto the fixed grid) are nx ny nz floats, x fastest.
+ * Both are quantised with one affine map fixed from F alone: lo, hi = the least and the largest finite value of F
+ * (sift3d_blockmatch_range; hi > lo is required); q(v) = -1 where v is not finite, else t = (((double)v - lo) / (hi - lo)) * 1023
+ * in double, q = 0 for t <= 0, 1023 for t >= 1023, else rint(t) (ties to even).  The quantisation step is (hi - lo) / 1023.
+ * A lattice node (a, b, c) sits at voxel p = first + stride (a, b, c) and has index (c n1 + b) n0 + a.  For every integer shift
+ * s in [-r, r]^3: cost(s) = sum over u in [-b, b]^3 of (qF(p + u) - qW(p + u + s))^2, an exact integer below 2^32.  The argmin
+ * is the shift of the least (cost, |s|^2, s_z, s_y, s_x) in that order.  A node is flagged where any voxel of p + [-b, b]^3 in
+ * F or of p + [-(b + r), b + r]^3 in W lies outside the volume or has q = -1; a flagged node's other words are 0.  Per node 16
+ * 32-bit words:
+ *   [0..2] argmin shift x, y, z (int32)   [3] flag   [4] cost(argmin)   [5] cost(0)
+ *   [6..11] cost at argmin - x, + x, - y, + y, - z, + z (0xffffffff where that shift is outside the search cube)
+ *   [12] sum of qF over the block   [13] sum of qF^2 over the block   [14], [15] 0 */
+#define SIFT3D_BLOCKMATCH_WORDS 16
+#define SIFT3D_BLOCKMATCH_MAX_B 6 /* 13^3 * 1023^2 < 2^32 */
+#define SIFT3D_BLOCKMATCH_MAX_R 6
+#define SIFT3D_BLOCKMATCH_NONE 0xffffffffu
+#define SIFT3D_BLOCKMATCH_MAX_ROUNDS 8
+
+typedef struct {
+    int32_t stride;          /* node spacing in fixed voxels: 4 */
+    int32_t block;           /* b, the block's half-width: 4 (a 9^3 block); 1 .. SIFT3D_BLOCKMATCH_MAX_B */
+    int32_t search;          /* r, the search half-width: 3; 1 .. SIFT3D_BLOCKMATCH_MAX_R */
+    int32_t rounds;          /* 2; 0 .. SIFT3D_BLOCKMATCH_MAX_ROUNDS (0 returns the input field) */
+    float variance_quantile; /* 0.25: a node needs a block variance above this quantile of the unflagged nodes' */
+    float cost_fraction;     /* 0.8: a nonzero argmin needs cost(argmin) < cost_fraction * cost(0) */
+    float spacing;           /* h of the output grid: 4 key units */
+    float radius;            /* R of the fit (sift3d_field_params): 20 */
+    float lambda;            /* 0.1 */
+    float min_tol;           /* 1.0 */
+    int64_t max_nodes;       /* 2^26: larger lattices and output grids are refused */
+} sift3d_blockmatch_params;
+void sift3d_blockmatch_defaults(sift3d_blockmatch_params *p);
+
+typedef struct {
+    int64_t nodes, flagged;                             /* lattice nodes; flagged by the kernel */
+    int64_t gated_variance, gated_border, gated_cost;   /* unflagged nodes the gates dropped, each counted at its first failing gate */
+    int64_t samples, kept;                              /* into the first fit; into the second, after the trim */
+    double rms_before, rms_after;                       /* RMS of e_i = |v_i - v(y_i)| under the first and the second fit */
+    double max_disp;                                    /* largest |v| over the nodes of the round's field */
+    int64_t folds;                                      /* nodes where det (L + grad v) <= 0 (sift3d_blockmatch_folds) */
+    double warp_ms, match_ms, fit_ms[2];                /* device time: field_warp_kernel, quantisation + block_match_kernel, the fits */
+} sift3d_blockmatch_round;
+
+typedef struct {
+    int32_t rounds;       /* rounds that produced a field */
+    int32_t empty_range;  /* 1: F has no two distinct finite values, nothing was matched and the input field came back */
+    float lo, hi;         /* the quantisation range */
+    sift3d_blockmatch_round round[SIFT3D_BLOCKMATCH_MAX_ROUNDS];
+} sift3d_blockmatch_report;
+
+/* The block search alone on the GPU (bm_quantize_kernel, block_match_kernel): F, W host arrays, out SIFT3D_BLOCKMATCH_WORDS words
+ * per node.  generic: 0 the specialised kernel where one exists (b = 4, r = 3 or 4); 1 the kernel's form for any b, r; 2 the
+ * specialised form with one multiply-add per instruction (same words from all three).  SIFT3D_ERR_ARG
+ * with text: extents outside 1 .. 2^27 - 1, b, r or stride out of range, counts < 1 or more than 2^27 nodes, no finite range. */
+int sift3d_block_match(int device, const float *f, const float *w, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3], int64_t stride,
+                       const int64_t count[3], int32_t b, int32_t r, int32_t generic, uint32_t *out, double *kernel_ms, char *err,
+                       int64_t err_len);
+
+/* Refine a displacement field from the images.  fixed (fx fy fz) and moving (mx my mz): host volumes; vox2key as
+ * sift3d_resample_field (NULL: identity); moving_to_fixed: T as the 4 x 4 of the .trans.txt; in: the field to start from
+ * (NULL: v = 0).  The output grid is sift3d_blockmatch_grid's: it covers the fixed volume's box.  Per round: W = the moving
+ * volume warped through T and the current field onto the fixed grid (field_warp_kernel, linear, fill NaN); the block search
+ * over sift3d_blockmatch_lattice; the gates and samples of sift3d_blockmatch_samples (the current field read through
+ * sift3d_field_eval); a fit on the output grid, the trim of sift3d_refine_field, a second fit.  The round's field replaces the
+ * current one.  A round without samples ends the call.  With no completed round (rounds = 0, an empty range, no sample) out
+ * receives the input field as it is, grid included (a zero field on the output grid for in == NULL).  out->capacity must hold
+ * the larger of the two grids (SIFT3D_ERR_CAPACITY with the output grid filled in).  SIFT3D_ERR_ARG with text: extents the warp
+ * refuses, parameters out of range, a block + search window wider than the volume, a lattice or grid above max_nodes. */
+int sift3d_refine_field_intensity(int device, const float *fixed, int64_t fx, int64_t fy, int64_t fz, const float *moving, int64_t mx,
+                                  int64_t my, int64_t mz, const float fixed_vox2key[16], const float moving_vox2key[16],
+                                  const float moving_to_fixed[16], const sift3d_field *in, const sift3d_blockmatch_params *p, sift3d_field *out,
+                                  sift3d_blockmatch_report *rep, char *err, int64_t err_len);
+
+/* Host helpers (also in libsift3d_host.so).
+ * lo, hi of the quantisation; returns 1, or 0 where F has no two distinct finite values. */
+int sift3d_blockmatch_range(const float *f, int64_t n, float *lo, float *hi);
+/* The lattice of a volume: first = b + r on every axis, count = floor((n - 1 - 2 (b + r)) / stride) + 1, so that no node's
+ * window leaves the volume.  Returns 0, or -1 where 2 (b + r) + 1 exceeds an extent or a parameter is out of range. */
+int sift3d_blockmatch_lattice(int64_t nx, int64_t ny, int64_t nz, const sift3d_blockmatch_params *p, int64_t first[3], int64_t count[3]);
+/* The output grid: sift3d_field_size (p's spacing, radius, max_nodes) over the key positions of the eight corner voxels
+ * (0 or n - 1 per axis), each ((c0 x + c1 y) + c2 z) + c3 in float.  Fills n, origin, spacing. */
+int sift3d_blockmatch_grid(int64_t nx, int64_t ny, int64_t nz, const float fixed_vox2key[16], const sift3d_blockmatch_params *p, sift3d_field *f);
+/* Gates and samples from the kernel's words, all exact.  With N = (2b + 1)^3, a node's variance is N [13] - [12]^2 (int64).
+ * In this order a node is dropped when it is flagged; when its variance is not above the threshold (the ascending variances
+ * of the unflagged nodes at index floor(q m), m their count, q = variance_quantile); when |s| = r on an axis; when s != 0 and
+ * not (double)cost(s) < (double)cost_fraction * (double)cost(0).  counts[4] receives those four tallies.  Per axis the sub-voxel
+ * step is d = 0.5 (c- - c+) / (c- - 2 c0 + c+) in double where that denominator is positive, else 0.  With C the fixed vox2key,
+ * D = s + d in double and L the inverse of moving_to_fixed's linear part (adjugate, double): y = (float)(C p), k = C (p + D) in
+ * double, v = (float)((double)v_in((float)k) + L (C_linear D)), rows summed ((a0 + a1) + a2), v_in by sift3d_field_eval
+ * (0 for in == NULL).  y, v: room for 3 floats per node.  Returns the number of samples, or -1 for bad arguments. */
+int64_t sift3d_blockmatch_samples(const uint32_t *words, int64_t nx, int64_t ny, int64_t nz, const sift3d_blockmatch_params *p,
+                                  const float fixed_vox2key[16], const float moving_to_fixed[16], const sift3d_field *in, float *y, float *v,
+                                  int64_t counts[4]);
+/* sift3d_field_folds for a 4 x 4 T: nodes where det (L + grad v) <= 0, L the inverse of T's linear part */
+int64_t sift3d_blockmatch_folds(const float moving_to_fixed[16], const sift3d_field *f, double *max_disp);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
