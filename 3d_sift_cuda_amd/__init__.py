@@ -175,6 +175,8 @@ def hip_lib():
     _sig(L.sift3d_resample_field, I, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, I, F, P, C.c_char_p, I64)
     _sig(L.sift3d_block_match, I, I, P, P, I64, I64, I64, P, I64, P, I, I, I, P, P, C.c_char_p, I64)
     _sig(L.sift3d_refine_field_intensity, I, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_block_match_ncc, I, I, P, P, I64, I64, I64, P, I64, P, I, I, I, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_refine_field_intensity_metric, I, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P, I, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -901,6 +903,16 @@ def block_match(fixed, warped, first, stride, count, block, search, device=0, ge
     """sift3d_block_match: the block search alone on the GPU.  fixed, warped: (nz, ny, nx) float32 on one grid; first, count:
     (x, y, z).  generic: 0 the specialised kernel where there is one, 1 the form for any b, r, 2 the specialised form without packed
     arithmetic (same words).  Returns uint32 words (count z, count y, count x, 16); return_ms=True returns (words, kernel_ms)."""
+    return _block_match("sift3d_block_match", fixed, warped, first, stride, count, block, search, device, generic, return_ms)
+
+
+def block_match_ncc(fixed, warped, first, stride, count, block, search, device=0, generic=False, return_ms=False):
+    """sift3d_block_match_ncc: block_match under the correlation cost of DESIGN.md section 7g (warped quantised with its own
+    range).  generic: 0 the register form of the kernel where there is one, 1 the form for any b, r (same words)."""
+    return _block_match("sift3d_block_match_ncc", fixed, warped, first, stride, count, block, search, device, generic, return_ms)
+
+
+def _block_match(entry, fixed, warped, first, stride, count, block, search, device, generic, return_ms):
     f, w = _f32(fixed), _f32(warped)
     if f.shape != w.shape:
         raise ValueError("fixed and warped differ in shape")
@@ -909,7 +921,7 @@ def block_match(fixed, warped, first, stride, count, block, search, device=0, ge
     n = max(int(cn[0]), 0) * max(int(cn[1]), 0) * max(int(cn[2]), 0)
     out = np.zeros((max(n, 1), BLOCKMATCH_WORDS), np.uint32)
     ms = C.c_double(0.0)
-    _call("sift3d_block_match", int(device), f.ctypes.data, w.ctypes.data, nx, ny, nz, fi, int(stride), cn, int(block), int(search),
+    _call(entry, int(device), f.ctypes.data, w.ctypes.data, nx, ny, nz, fi, int(stride), cn, int(block), int(search),
           int(generic), out.ctypes.data, C.byref(ms))
     out = out[:n].reshape(int(cn[2]), int(cn[1]), int(cn[0]), BLOCKMATCH_WORDS)
     return (out, ms.value) if return_ms else out
@@ -925,10 +937,16 @@ def _blockmatch_report_dict(r):
     return {"rounds": int(r.rounds), "empty_range": int(r.empty_range), "lo": np.float32(r.lo), "hi": np.float32(r.hi), "round": rounds}
 
 
-def refine_field_intensity(fixed, moving, t, field=None, fixed_vox2key=None, moving_vox2key=None, device=0, **params):
+BLOCKMATCH_METRICS = {"ssd": 0, "ncc": 1}
+
+
+def refine_field_intensity(fixed, moving, t, field=None, fixed_vox2key=None, moving_vox2key=None, device=0, metric="ssd", **params):
     """sift3d_refine_field_intensity: refine a displacement field (a field dict, None: zero) from the fixed and the moving
     volume (nz, ny, nx) by block matching.  t: the moving -> fixed key transform, 4 x 4 or a match_keys-style dict; vox2key
-    4 x 4 (None: identity); params: fields of blockmatch_params.  Returns (field dict, report dict)."""
+    4 x 4 (None: identity); params: fields of blockmatch_params.  Returns (field dict, report dict).
+    metric: "ssd" (that function) or "ncc" (sift3d_refine_field_intensity_metric with the correlation cost of DESIGN.md section
+    7g; the report dict then also holds metric and moving_lo, moving_hi, the range W is quantised with); a number is passed to
+    sift3d_refine_field_intensity_metric as it is."""
     f, m = _f32(fixed), _f32(moving)
     fz, fy, fx = f.shape
     mz, my, mx = m.shape
@@ -943,9 +961,19 @@ def refine_field_intensity(fixed, moving, t, field=None, fixed_vox2key=None, mov
     out.capacity, out.disp = disp.size, disp.ctypes.data
     rep = BlockmatchReport()
     fv, mv, tm = _m16(fixed_vox2key), _m16(moving_vox2key), _m16(t)
-    _call("sift3d_refine_field_intensity", int(device), f.ctypes.data, fx, fy, fz, m.ctypes.data, mx, my, mz, _ptr(fv), _ptr(mv),
-          tm.ctypes.data, C.byref(fs) if fs is not None else None, C.byref(p), C.byref(out), C.byref(rep))
-    return _field_dict(out, disp), _blockmatch_report_dict(rep)
+    if metric == "ssd":
+        _call("sift3d_refine_field_intensity", int(device), f.ctypes.data, fx, fy, fz, m.ctypes.data, mx, my, mz, _ptr(fv), _ptr(mv),
+              tm.ctypes.data, C.byref(fs) if fs is not None else None, C.byref(p), C.byref(out), C.byref(rep))
+        return _field_dict(out, disp), _blockmatch_report_dict(rep)
+    if isinstance(metric, str) and metric not in BLOCKMATCH_METRICS:
+        raise ValueError("no block matching metric %s" % metric)
+    mrange = (C.c_float * 2)()
+    _call("sift3d_refine_field_intensity_metric", int(device), f.ctypes.data, fx, fy, fz, m.ctypes.data, mx, my, mz, _ptr(fv), _ptr(mv),
+          tm.ctypes.data, C.byref(fs) if fs is not None else None, C.byref(p), int(BLOCKMATCH_METRICS.get(metric, metric)), C.byref(out),
+          C.byref(rep), mrange)
+    d = _blockmatch_report_dict(rep)
+    d.update(metric=metric, moving_lo=np.float32(mrange[0]), moving_hi=np.float32(mrange[1]))
+    return _field_dict(out, disp), d
 
 
 def _map12(m):

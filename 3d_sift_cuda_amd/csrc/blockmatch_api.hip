@@ -1,6 +1,7 @@
 /*
- * blockmatch_api.hip -- C-ABI of the intensity refinement (include/sift3d.h, "intensity refinement"):
- * sift3d_block_match and sift3d_refine_field_intensity.  The kernels are in kernels_blockmatch.hip; the warp and the fit are
+ * blockmatch_api.hip -- C-ABI of the intensity refinement (include/sift3d.h, "intensity refinement"; DESIGN.md sections 7f, 7g):
+ * sift3d_block_match and sift3d_refine_field_intensity, and the same two under a chosen cost (sift3d_block_match_ncc,
+ * sift3d_refine_field_intensity_metric).  The kernels are in kernels_blockmatch.hip; the warp and the fit are
  * section 7e's (kernels_field.hip, fit_on_grid of field_api.hip); the range, the lattice, the grid, the gates, the samples and
  * the fold count are host arithmetic (blockmatch_host.c).
  */
@@ -14,6 +15,8 @@
 hipError_t sift3d_launch_bm_quantize(hipStream_t s, const float *src, int64_t n, double lo, double hi, short *dst);
 hipError_t sift3d_launch_block_match(hipStream_t s, const short *qf, const short *qw, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
                                      int64_t stride, const int64_t n[3], int b, int r, int generic, unsigned *out);
+hipError_t sift3d_launch_block_match_ncc(hipStream_t s, const short *qf, const short *qw, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
+                                         int64_t stride, const int64_t n[3], int b, int r, int generic, unsigned *out);
 hipError_t sift3d_launch_field_warp(hipStream_t s, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
                                     int64_t oz, const float *map, const float *c, const float *k, const float o[3], float h, const int64_t n[3],
                                     const float4 *nodes, int nearest, float fill);
@@ -41,9 +44,10 @@ static const char *check_search(int64_t nx, int64_t ny, int64_t nz, const int64_
     return nullptr;
 }
 
-extern "C" int sift3d_block_match(int device, const float *f, const float *w, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
-                                  int64_t stride, const int64_t count[3], int32_t b, int32_t r, int32_t generic, uint32_t *out,
-                                  double *kernel_ms, char *err, int64_t err_len)
+/* the block search under either cost: SSD quantises W with F's range, NCC with W's own */
+static int block_match(int metric, int device, const float *f, const float *w, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
+                       int64_t stride, const int64_t count[3], int32_t b, int32_t r, int32_t generic, uint32_t *out, double *kernel_ms, char *err,
+                       int64_t err_len)
 {
     if (err && err_len > 0) err[0] = 0;
     if (kernel_ms) *kernel_ms = 0.0;
@@ -54,6 +58,9 @@ extern "C" int sift3d_block_match(int device, const float *f, const float *w, in
     float lo, hi;
     if (!sift3d_blockmatch_range(f, (int64_t)nv, &lo, &hi))
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the fixed volume has no two distinct finite values: nothing to quantise");
+    float wlo = lo, whi = hi;
+    if (metric == SIFT3D_BLOCKMATCH_NCC && !sift3d_blockmatch_range(w, (int64_t)nv, &wlo, &whi))
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "the warped volume has no two distinct finite values: nothing to quantise");
     device_call dc(err, err_len);
     float *d_v;
     short *d_qf, *d_qw;
@@ -67,14 +74,29 @@ extern "C" int sift3d_block_match(int device, const float *f, const float *w, in
     DEVCHK(dc, dc.to_device(d_v, f, nv));
     DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_qf));
     DEVCHK(dc, dc.to_device(d_v, w, nv));
-    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_qw));
+    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)wlo, (double)whi, d_qw));
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
-    DEVCHK(dc, sift3d_launch_block_match(dc.s, d_qf, d_qw, nx, ny, nz, first, stride, count, b, r, generic, d_out));
+    if (metric == SIFT3D_BLOCKMATCH_NCC) DEVCHK(dc, sift3d_launch_block_match_ncc(dc.s, d_qf, d_qw, nx, ny, nz, first, stride, count, b, r, generic, d_out));
+    else DEVCHK(dc, sift3d_launch_block_match(dc.s, d_qf, d_qw, nx, ny, nz, first, stride, count, b, r, generic, d_out));
     DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
     DEVCHK(dc, dc.download((unsigned *)out, d_out, N * SIFT3D_BLOCKMATCH_WORDS));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));
     return SIFT3D_OK;
+}
+
+extern "C" int sift3d_block_match(int device, const float *f, const float *w, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
+                                  int64_t stride, const int64_t count[3], int32_t b, int32_t r, int32_t generic, uint32_t *out,
+                                  double *kernel_ms, char *err, int64_t err_len)
+{
+    return block_match(SIFT3D_BLOCKMATCH_SSD, device, f, w, nx, ny, nz, first, stride, count, b, r, generic, out, kernel_ms, err, err_len);
+}
+
+extern "C" int sift3d_block_match_ncc(int device, const float *f, const float *w, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
+                                      int64_t stride, const int64_t count[3], int32_t b, int32_t r, int32_t generic, uint32_t *out,
+                                      double *kernel_ms, char *err, int64_t err_len)
+{
+    return block_match(SIFT3D_BLOCKMATCH_NCC, device, f, w, nx, ny, nz, first, stride, count, b, r, generic, out, kernel_ms, err, err_len);
 }
 
 static int64_t nodes_of(const sift3d_field &f) { return f.n[0] * f.n[1] * f.n[2]; }
@@ -107,13 +129,18 @@ static bool field_ok(const sift3d_field *f)
     return f->n[0] * f->n[1] <= (1ll << 40) / f->n[2] && f->capacity >= 3 * nodes_of(*f);
 }
 
-extern "C" int sift3d_refine_field_intensity(int device, const float *fixed, int64_t fx, int64_t fy, int64_t fz, const float *moving, int64_t mx,
-                                             int64_t my, int64_t mz, const float fixed_vox2key[16], const float moving_vox2key[16],
-                                             const float moving_to_fixed[16], const sift3d_field *in, const sift3d_blockmatch_params *pp,
-                                             sift3d_field *out, sift3d_blockmatch_report *rep, char *err, int64_t err_len)
+extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fixed, int64_t fx, int64_t fy, int64_t fz, const float *moving,
+                                                    int64_t mx, int64_t my, int64_t mz, const float fixed_vox2key[16],
+                                                    const float moving_vox2key[16], const float moving_to_fixed[16], const sift3d_field *in,
+                                                    const sift3d_blockmatch_params *pp, int32_t metric, sift3d_field *out,
+                                                    sift3d_blockmatch_report *rep, float moving_range[2], char *err, int64_t err_len)
 {
     if (err && err_len > 0) err[0] = 0;
     if (rep) memset(rep, 0, sizeof *rep);
+    if (moving_range) moving_range[0] = moving_range[1] = 0.0f;
+    if (metric != SIFT3D_BLOCKMATCH_SSD && metric != SIFT3D_BLOCKMATCH_NCC)
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "unknown metric %d: SIFT3D_BLOCKMATCH_SSD (0) or SIFT3D_BLOCKMATCH_NCC (1)", (int)metric);
+    const bool ncc = metric == SIFT3D_BLOCKMATCH_NCC;
     sift3d_blockmatch_params p;
     if (pp) p = *pp;
     else sift3d_blockmatch_defaults(&p);
@@ -158,7 +185,16 @@ extern "C" int sift3d_refine_field_intensity(int device, const float *fixed, int
     cur.disp = cur_disp.data();
     cur.capacity = (int64_t)cur_disp.size();
     const size_t nf = (size_t)(fx * fy * fz), nm = (size_t)(mx * my * mz);
-    const bool ranged = sift3d_blockmatch_range(fixed, (int64_t)nf, &rp.lo, &rp.hi) != 0;
+    bool ranged = sift3d_blockmatch_range(fixed, (int64_t)nf, &rp.lo, &rp.hi) != 0;
+    /* W's map: F's under SSD; under NCC the moving volume's own range, which trilinear warping cannot leave */
+    float wlo = rp.lo, whi = rp.hi;
+    if (ncc) {
+        if (!sift3d_blockmatch_range(moving, (int64_t)nm, &wlo, &whi)) ranged = false;
+        if (moving_range) {
+            moving_range[0] = wlo;
+            moving_range[1] = whi;
+        }
+    }
     rp.empty_range = !ranged;
     if (ranged && p.rounds > 0) {
         device_call dc(err, err_len);
@@ -195,8 +231,9 @@ extern "C" int sift3d_refine_field_intensity(int device, const float *fixed, int
             DEVCHK(dc, dc.sync());
             DEVCHK(dc, dc.elapsed_ms(&r.warp_ms));
             DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
-            DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, (int64_t)nf, (double)rp.lo, (double)rp.hi, d_qw));
-            DEVCHK(dc, sift3d_launch_block_match(dc.s, d_qf, d_qw, fx, fy, fz, first, p.stride, count, p.block, p.search, 0, d_words));
+            DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, (int64_t)nf, (double)wlo, (double)whi, d_qw));
+            if (ncc) DEVCHK(dc, sift3d_launch_block_match_ncc(dc.s, d_qf, d_qw, fx, fy, fz, first, p.stride, count, p.block, p.search, 0, d_words));
+            else DEVCHK(dc, sift3d_launch_block_match(dc.s, d_qf, d_qw, fx, fy, fz, first, p.stride, count, p.block, p.search, 0, d_words));
             DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
             DEVCHK(dc, dc.download(words.data(), d_words, words.size()));
             DEVCHK(dc, dc.sync());
@@ -254,4 +291,13 @@ extern "C" int sift3d_refine_field_intensity(int device, const float *fixed, int
     std::copy(cur.disp, cur.disp + 3 * nodes_of(cur), out->disp);
     if (rep) *rep = rp;
     return SIFT3D_OK;
+}
+
+extern "C" int sift3d_refine_field_intensity(int device, const float *fixed, int64_t fx, int64_t fy, int64_t fz, const float *moving, int64_t mx,
+                                             int64_t my, int64_t mz, const float fixed_vox2key[16], const float moving_vox2key[16],
+                                             const float moving_to_fixed[16], const sift3d_field *in, const sift3d_blockmatch_params *pp,
+                                             sift3d_field *out, sift3d_blockmatch_report *rep, char *err, int64_t err_len)
+{
+    return sift3d_refine_field_intensity_metric(device, fixed, fx, fy, fz, moving, mx, my, mz, fixed_vox2key, moving_vox2key, moving_to_fixed, in,
+                                                pp, SIFT3D_BLOCKMATCH_SSD, out, rep, nullptr, err, err_len);
 }

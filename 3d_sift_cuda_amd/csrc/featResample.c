@@ -14,6 +14,8 @@
  * -i[<rounds>]: refine the field (-u's, or zero) from the two images by block matching first
  * (sift3d_refine_field_intensity; default 2 rounds), write it to <output image>.field.nii and its
  * report to <output image>.field.txt, and resample through it.
+ * -c (with -i): match the blocks by their normalised correlation instead of their squared differences
+ * (sift3d_refine_field_intensity_metric): for images that do not share an intensity scale.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -39,6 +41,7 @@ static void print_options(void)
     printf("  -u <field> : also through the displacement field featMatchMultiple -a -e -u wrote (<moving>.field.nii).\n");
     printf("  -i[rounds] : refine the field (-u's, or zero) from the image intensities by block matching (default 2 rounds),\n");
     printf("               write <output image>.field.nii and .field.txt, and resample through the refined field.\n");
+    printf("  -c         : with -i, match blocks by normalised correlation: for images on different intensity scales.\n");
 }
 
 /* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
@@ -56,7 +59,8 @@ static void world_matrix(nifti_min_image *img, int world_mode, float m[16])
 }
 
 /* -i: the refined field to <out>.field.nii, its grid and the report of every round to <out>.field.txt */
-static int write_refined(const char *out_path, const sift3d_field *f, const sift3d_blockmatch_params *p, const sift3d_blockmatch_report *rep)
+static int write_refined(const char *out_path, const sift3d_field *f, const sift3d_blockmatch_params *p, const sift3d_blockmatch_report *rep,
+                         int metric, const float moving_range[2])
 {
     char *path = (char *)malloc(strlen(out_path) + 16);
     if (!path) return -1;
@@ -74,6 +78,9 @@ static int write_refined(const char *out_path, const sift3d_field *f, const sift
     fprintf(o, "# stride %d block %d search %d rounds %d variance_quantile %f cost_fraction %f quantised over %g .. %g%s\n", p->stride, p->block,
             p->search, p->rounds, p->variance_quantile, p->cost_fraction, rep->lo, rep->hi,
             rep->empty_range ? " (empty: nothing matched)" : "");
+    if (metric == SIFT3D_BLOCKMATCH_NCC)
+        fprintf(o, "# metric ncc fixed quantised over %g .. %g moving quantised over %g .. %g\n", rep->lo, rep->hi, moving_range[0],
+                moving_range[1]);
     fprintf(o, "# round nodes samples kept flagged gated_variance gated_border gated_cost rms_before rms_after max_disp folds\n");
     for (int k = 0; k < rep->rounds; k++) {
         const sift3d_blockmatch_round *r = &rep->round[k];
@@ -89,7 +96,7 @@ int main(int argc, char **argv)
     int device = 0, world_mode = 0, interp = SIFT3D_INTERP_LINEAR;
     float fill = 0.0f;
     const char *field_path = NULL;
-    int intensity = 0, rounds = -1;
+    int intensity = 0, rounds = -1, metric = SIFT3D_BLOCKMATCH_SSD;
     int arg = 1;
     while (arg < argc && argv[arg][0] == '-') {
         switch (argv[arg][1]) {
@@ -132,6 +139,14 @@ int main(int argc, char **argv)
                 rounds = (int)v;
             }
             break;
+        case 'c':
+            if (argv[arg][2] != 0) {
+                printf("Error: unknown command line argument: %s\n", argv[arg]);
+                print_options();
+                return -1;
+            }
+            metric = SIFT3D_BLOCKMATCH_NCC;
+            break;
         case 'u':
             if (argv[arg][2] != 0 || arg + 1 >= argc) {
                 printf("Error: -u needs a field file\n");
@@ -148,6 +163,11 @@ int main(int argc, char **argv)
         arg++;
     }
     if (argc - arg != 4) {
+        print_options();
+        return -1;
+    }
+    if (metric != SIFT3D_BLOCKMATCH_SSD && !intensity) {
+        printf("Error: -c needs -i\n");
         print_options();
         return -1;
     }
@@ -215,21 +235,23 @@ int main(int argc, char **argv)
         sift3d_blockmatch_report rep;
         sift3d_field refined;
         memset(&refined, 0, sizeof refined);
-        int irc = sift3d_refine_field_intensity(device, fixed.data, fixed.nx, fixed.ny, fixed.nz, moving.data, moving.nx, moving.ny, moving.nz, fv, mv,
-                                                t, field_path ? &field : NULL, &bp, &refined, &rep, err, sizeof err);
+        float mrange[2] = {0, 0};
+        int irc = sift3d_refine_field_intensity_metric(device, fixed.data, fixed.nx, fixed.ny, fixed.nz, moving.data, moving.nx, moving.ny, moving.nz,
+                                                       fv, mv, t, field_path ? &field : NULL, &bp, metric, &refined, &rep, mrange, err, sizeof err);
         if (irc == SIFT3D_ERR_CAPACITY) {
             refined.capacity = 3 * refined.n[0] * refined.n[1] * refined.n[2];
             if (field_path && field.capacity > refined.capacity) refined.capacity = field.capacity;
             refined.disp = (float *)malloc(sizeof(float) * (size_t)refined.capacity);
-            irc = refined.disp ? sift3d_refine_field_intensity(device, fixed.data, fixed.nx, fixed.ny, fixed.nz, moving.data, moving.nx, moving.ny,
-                                                               moving.nz, fv, mv, t, field_path ? &field : NULL, &bp, &refined, &rep, err, sizeof err)
+            irc = refined.disp ? sift3d_refine_field_intensity_metric(device, fixed.data, fixed.nx, fixed.ny, fixed.nz, moving.data, moving.nx,
+                                                                      moving.ny, moving.nz, fv, mv, t, field_path ? &field : NULL, &bp, metric,
+                                                                      &refined, &rep, mrange, err, sizeof err)
                                : SIFT3D_ERR_MEMORY;
         }
         if (irc != SIFT3D_OK) {
             printf("Error: could not refine the field: %s\n", err);
             return -1;
         }
-        if (write_refined(out_path, &refined, &bp, &rep) != 0) {
+        if (write_refined(out_path, &refined, &bp, &rep, metric, mrange) != 0) {
             printf("Error: could not write the field files of: %s\n", out_path);
             return -1;
         }

@@ -822,6 +822,41 @@ int sift3d_refine_field_intensity(int device, const float *fixed, int64_t fx, in
                                   const float moving_to_fixed[16], const sift3d_field *in, const sift3d_blockmatch_params *p, sift3d_field *out,
                                   sift3d_blockmatch_report *rep, char *err, int64_t err_len);
 
+/* ---- the correlation cost of the block search (featResample -i -c; tests/blockmatch_ncc_oracle.c) ----
+ * The sum of squared differences above needs both images on one intensity scale.  The second cost is the zero-mean normalised
+ * cross-correlation of the two blocks, which no gain, offset or slowly varying bias of the moving image changes.
+ * Quantisation: F as above.  W is quantised with the range of the MOVING volume's finite values (sift3d_blockmatch_range on the
+ * moving image, fixed once for all rounds: a trilinear warp cannot leave it); same 10-bit map, same -1 for non-finite values,
+ * same flags.  A moving volume without two distinct finite values is an empty range exactly like F's.
+ * Per node, N = (2b + 1)^3, and shift s, in exact integers (int64; the raw sums stay below 2^32 for b <= 6, |A| and the V's
+ * below 2^43):
+ *   Sf = sum qF, Sff = sum qF^2 over the block (words [12], [13]);  Sw(s) = sum qW, Sww(s) = sum qW^2, Sfw(s) = sum qF qW over
+ *   the block shifted by s;  A(s) = N Sfw - Sf Sw,  Vf = N Sff - Sf^2,  Vw(s) = N Sww - Sw^2
+ * then in IEEE double, each integer converted exactly, one operation at a time, no contraction:
+ *   rho2(s) = A > 0 and Vf > 0 and Vw > 0 ? ((double)A * (double)A) / ((double)Vf * (double)Vw) : 0
+ *   cost(s) = (uint32) rint((1 - (rho2 > 1 ? 1 : rho2)) * 2^31)     0 .. 2^31; anticorrelated, flat F or flat W block: 2^31
+ * (A^2 <= Vf Vw holds in the integers; the comparison only catches a quotient that rounds above 1.)  cost(s) is a 32-bit integer
+ * again and takes the place of the SSD everywhere: the argmin order (cost, |s|^2, s_z, s_y, s_x), the sixteen words (words
+ * [4] .. [11] hold these costs), the flags, sift3d_blockmatch_samples with its gates and parabola step, the fit, the trim and
+ * the report are those stated above. */
+#define SIFT3D_BLOCKMATCH_SSD 0
+#define SIFT3D_BLOCKMATCH_NCC 1
+/* sift3d_block_match under the correlation cost: F quantised with F's range, W with W's own.  generic: 0 the register form of
+ * the kernel where one exists (b = 4, r = 3 or 4), anything else its form for any b, r (same words).  Refuses what
+ * sift3d_block_match refuses, and a W without two distinct finite values. */
+int sift3d_block_match_ncc(int device, const float *f, const float *w, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
+                           int64_t stride, const int64_t count[3], int32_t b, int32_t r, int32_t generic, uint32_t *out, double *kernel_ms,
+                           char *err, int64_t err_len);
+/* sift3d_refine_field_intensity under a chosen cost: metric SIFT3D_BLOCKMATCH_SSD is that function itself, bit for bit (it calls
+ * this one); SIFT3D_BLOCKMATCH_NCC runs the same stage on the correlation cost.  moving_range (may be NULL) receives lo, hi of
+ * W's quantisation under NCC and 0, 0 under SSD; rep->lo, rep->hi stay F's range and rep->empty_range is set where either range
+ * is empty.  Any other metric: SIFT3D_ERR_ARG with text. */
+int sift3d_refine_field_intensity_metric(int device, const float *fixed, int64_t fx, int64_t fy, int64_t fz, const float *moving, int64_t mx,
+                                         int64_t my, int64_t mz, const float fixed_vox2key[16], const float moving_vox2key[16],
+                                         const float moving_to_fixed[16], const sift3d_field *in, const sift3d_blockmatch_params *p,
+                                         int32_t metric, sift3d_field *out, sift3d_blockmatch_report *rep, float moving_range[2], char *err,
+                                         int64_t err_len);
+
 /* Host helpers (also in libsift3d_host.so).
  * lo, hi of the quantisation; returns 1, or 0 where F has no two distinct finite values. */
 int sift3d_blockmatch_range(const float *f, int64_t n, float *lo, float *hi);
