@@ -177,6 +177,9 @@ def hip_lib():
     _sig(L.sift3d_refine_field_intensity, I, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_block_match_ncc, I, I, P, P, I64, I64, I64, P, I64, P, I, I, I, P, P, C.c_char_p, I64)
     _sig(L.sift3d_refine_field_intensity_metric, I, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P, I, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_invert_nodes, I, I, P, P, P, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_invert_field, I, I, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_jacobian_map, I, I, I64, I64, I64, P, P, P, P, P, I, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -231,6 +234,12 @@ def host_lib():
     _sig(L.sift3d_blockmatch_grid, I, I64, I64, I64, P, P, P)
     _sig(L.sift3d_blockmatch_samples, I64, P, I64, I64, I64, P, P, P, P, P, P, P)
     _sig(L.sift3d_blockmatch_folds, I64, P, P, P)
+    _sig(L.sift3d_invert_defaults, None, P)
+    _sig(L.sift3d_invert_grid, I, I64, I64, I64, P, P, P)
+    _sig(L.sift3d_affine_invert, I, P, P)
+    _sig(L.sift3d_affine_invert_d, I, P, P)
+    _sig(L.sift3d_write_matrix, I, C.c_char_p, P)
+    _sig(L.sift3d_jacobian_factor, I, P, P, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -974,6 +983,119 @@ def refine_field_intensity(fixed, moving, t, field=None, fixed_vox2key=None, mov
     d = _blockmatch_report_dict(rep)
     d.update(metric=metric, moving_lo=np.float32(mrange[0]), moving_hi=np.float32(mrange[1]))
     return _field_dict(out, disp), d
+
+
+# ---- the reverse direction: the inverse field and the Jacobian determinant map (featResample -r, -j), DESIGN.md section 7h ----
+INVERT_STATES = ("converged", "not_converged", "diverged")   # SIFT3D_INVERT_STATE of a status word; its low 16 bits are the steps
+
+
+class InvertParams(C.Structure):
+    """sift3d_invert_params"""
+    _fields_ = [("spacing", C.c_float), ("radius", C.c_float), ("max_iter", C.c_int32), ("tol", C.c_float), ("max_nodes", C.c_int64)]
+
+
+class InvertReport(C.Structure):
+    """sift3d_invert_report"""
+    _fields_ = [("nodes", C.c_int64), ("converged", C.c_int64), ("not_converged", C.c_int64), ("diverged", C.c_int64), ("max_steps", C.c_int32),
+                ("rms_residual", C.c_double), ("max_residual", C.c_double), ("max_disp", C.c_double), ("folds", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
+def invert_params(**kw):
+    """sift3d_invert_defaults, then the given fields (spacing, radius, max_iter, tol, max_nodes)."""
+    p = InvertParams()
+    host_lib().sift3d_invert_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(InvertParams._fields_):
+            raise ValueError("no inversion parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def invert_grid(shape, moving_vox2key=None, **params):
+    """sift3d_invert_grid: the inverse grid (dict n, origin, spacing) of a moving volume of shape (nz, ny, nx)"""
+    nz, ny, nx = (int(d) for d in shape)
+    f = Field()
+    if host_lib().sift3d_invert_grid(nx, ny, nz, _ptr(_m16(moving_vox2key)), C.byref(invert_params(**params)), C.byref(f)) != 0:
+        raise Sift3DError("sift3d_invert_grid: bad parameters or too many nodes")
+    return {"n": tuple(int(x) for x in f.n), "origin": np.array(f.origin, np.float32), "spacing": np.float32(f.spacing)}
+
+
+def affine_invert(m, double=False):
+    """sift3d_affine_invert: the inverse of an affine 4 x 4 in double, rounded to float32 once (double=True: not rounded)"""
+    a = _m16(m)
+    out = np.zeros(16, np.float64 if double else np.float32)
+    if (host_lib().sift3d_affine_invert_d if double else host_lib().sift3d_affine_invert)(a.ctypes.data, out.ctypes.data) != 0:
+        raise Sift3DError("sift3d_affine_invert: the matrix is singular or its last row is not 0 0 0 1")
+    return out.reshape(4, 4)
+
+
+def write_matrix(path, m):
+    """sift3d_write_matrix: a 4 x 4 in the .trans.txt layout"""
+    if host_lib().sift3d_write_matrix(os.fsencode(path), _m16(m).ctypes.data) != 0:
+        raise Sift3DError("could not write %s" % path)
+
+
+def jacobian_factor(out_vox2key=None, src_vox2key=None):
+    """sift3d_jacobian_factor: det lin(src_vox2key) / det lin(out_vox2key) as a float (a double)"""
+    f = C.c_double(0.0)
+    if host_lib().sift3d_jacobian_factor(_ptr(_m16(out_vox2key)), _ptr(_m16(src_vox2key)), C.byref(f)) != 0:
+        raise Sift3DError("sift3d_jacobian_factor: a vox2key is singular")
+    return f.value
+
+
+def _grid_struct(grid):
+    g = Field()
+    g.n[:] = [int(x) for x in grid["n"]]
+    g.origin[:] = [float(x) for x in np.asarray(grid["origin"], np.float32)]
+    g.spacing = float(grid["spacing"])
+    return g
+
+
+def invert_nodes(m, m_inv, forward, grid, device=0, return_ms=False, **params):
+    """sift3d_invert_nodes: field_invert_kernel alone over grid (dict n, origin, spacing).  m, m_inv: 4 x 4; forward: a field dict
+    or None.  Returns (u (3, n2, n1, n0) float32, status (n2, n1, n0) uint32, res2 (n2, n1, n0) float64); return_ms=True appends
+    kernel_ms."""
+    n = tuple(int(x) for x in grid["n"])
+    N = max(n[0], 0) * max(n[1], 0) * max(n[2], 0)
+    u, status, res2 = np.zeros(3 * max(N, 1), np.float32), np.zeros(max(N, 1), np.uint32), np.zeros(max(N, 1), np.float64)
+    fs, _keep = _field_struct(forward) if forward is not None else (None, None)
+    g = _grid_struct(grid)
+    ms = C.c_double(0.0)
+    _call("sift3d_invert_nodes", int(device), _m16(m).ctypes.data, _m16(m_inv).ctypes.data, C.byref(fs) if fs is not None else None,
+          C.byref(invert_params(**params)), C.byref(g), u.ctypes.data, status.ctypes.data, res2.ctypes.data, C.byref(ms))
+    out = (u[:3 * N].reshape(3, n[2], n[1], n[0]), status[:N].reshape(n[2], n[1], n[0]), res2[:N].reshape(n[2], n[1], n[0]))
+    return out + (ms.value,) if return_ms else out
+
+
+def _invert_report_dict(r):
+    return {name: getattr(r, name) for name, _ in InvertReport._fields_}
+
+
+def invert_field(m, m_inv, forward, grid, device=0, **params):
+    """sift3d_invert_field: the inverse field on grid (from invert_grid) and its report.  Returns (field dict, report dict)."""
+    n = tuple(int(x) for x in grid["n"])
+    disp = np.zeros(3 * max(n[0] * n[1] * n[2], 1), np.float32)
+    out = _grid_struct(grid)
+    out.capacity, out.disp = disp.size, disp.ctypes.data
+    fs, _keep = _field_struct(forward) if forward is not None else (None, None)
+    rep = InvertReport()
+    _call("sift3d_invert_field", int(device), _m16(m).ctypes.data, _m16(m_inv).ctypes.data, C.byref(fs) if fs is not None else None,
+          C.byref(invert_params(**params)), C.byref(out), C.byref(rep))
+    return _field_dict(out, disp), _invert_report_dict(rep)
+
+
+def jacobian_map(out_shape, map, out_vox2key=None, src_vox2key=None, field=None, form=-1, device=0, return_ms=False):
+    """sift3d_jacobian_map: det grad of the warp resample_field applies for (map, out_vox2key, src_vox2key, field), on the output
+    grid out_shape = (oz, oy, ox).  form 0: six evaluations per voxel, 1: through LDS, -1: the default.  return_ms=True returns
+    (J, kernel_ms)."""
+    oz, oy, ox = (int(d) for d in out_shape)
+    out = np.empty((max(oz, 0), max(oy, 0), max(ox, 0)), np.float32)
+    fs, _keep = _field_struct(field) if field is not None else (None, None)
+    ms = C.c_double(0.0)
+    _call("sift3d_jacobian_map", int(device), ox, oy, oz, _map12(map).ctypes.data, _ptr(_m16(out_vox2key)), _ptr(_m16(src_vox2key)),
+          C.byref(fs) if fs is not None else None, out.ctypes.data, int(form), C.byref(ms))
+    return (out, ms.value) if return_ms else out
 
 
 def _map12(m):

@@ -16,6 +16,13 @@
  * report to <output image>.field.txt, and resample through it.
  * -c (with -i): match the blocks by their normalised correlation instead of their squared differences
  * (sift3d_refine_field_intensity_metric): for images that do not share an intensity scale.
+ * -r: the other direction: <output image> is the FIXED image on the MOVING image's grid.  The inverse of
+ * the transform goes to <output image>.inv.trans.txt; with -u and / or -i the inverse of the field (of the refined one under
+ * -i) goes to <output image>.inv.field.nii and its report to <output image>.inv.field.txt (sift3d_invert_field).  The pair is an
+ * ordinary transform and field with the two images' roles swapped:
+ *   featResample -u <out>.inv.field.nii <moving image> <fixed image> <out>.inv.trans.txt <x>   writes the same voxels.
+ * -j: also <output image>.jac.nii, the Jacobian determinant of the map that was applied, on the output grid
+ * (sift3d_jacobian_map): below or at 0 where the map folds.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,6 +49,9 @@ static void print_options(void)
     printf("  -i[rounds] : refine the field (-u's, or zero) from the image intensities by block matching (default 2 rounds),\n");
     printf("               write <output image>.field.nii and .field.txt, and resample through the refined field.\n");
     printf("  -c         : with -i, match blocks by normalised correlation: for images on different intensity scales.\n");
+    printf("  -r         : reverse: resample the fixed image onto the moving image's grid through the inverse map; writes\n");
+    printf("               <output image>.inv.trans.txt and, with -u or -i, <output image>.inv.field.nii and .inv.field.txt.\n");
+    printf("  -j         : also write <output image>.jac.nii, the Jacobian determinant of the applied map (<= 0: a fold).\n");
 }
 
 /* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
@@ -91,12 +101,126 @@ static int write_refined(const char *out_path, const sift3d_field *f, const sift
     return fclose(o);
 }
 
+/* -r: the inverse field to <out>.inv.field.nii, its grid, the parameters and the report to <out>.inv.field.txt */
+static int write_inverse(const char *out_path, const sift3d_field *f, const sift3d_invert_params *p, const sift3d_invert_report *rep)
+{
+    char *path = (char *)malloc(strlen(out_path) + 24);
+    if (!path) return -1;
+    sprintf(path, "%s.inv.field.nii", out_path);
+    if (sift3d_write_field(path, f) != 0) {
+        free(path);
+        return -1;
+    }
+    sprintf(path, "%s.inv.field.txt", out_path);
+    FILE *o = fopen(path, "w");
+    free(path);
+    if (!o) return -1;
+    fprintf(o, "# nodes %lld %lld %lld spacing %f origin %f %f %f radius %f\n", (long long)f->n[0], (long long)f->n[1], (long long)f->n[2], f->spacing,
+            f->origin[0], f->origin[1], f->origin[2], p->radius);
+    fprintf(o, "# max_iter %d tol %g\n", p->max_iter, p->tol);
+    fprintf(o, "# nodes converged not_converged diverged max_steps rms_residual max_residual max_disp folds\n");
+    fprintf(o, "%lld\t%lld\t%lld\t%lld\t%d\t%g\t%g\t%f\t%lld\n", (long long)rep->nodes, (long long)rep->converged, (long long)rep->not_converged,
+            (long long)rep->diverged, rep->max_steps, rep->rms_residual, rep->max_residual, rep->max_disp, (long long)rep->folds);
+    return fclose(o);
+}
+
+/* -j: the Jacobian determinant map of (map, out_vox2key, src_vox2key, field) to <out>.jac.nii with the geometry of geom_path */
+static int write_jacobian(int device, const char *out_path, const char *geom_path, int nx, int ny, int nz, const float map[12],
+                          const float out_vox2key[16], const float src_vox2key[16], const sift3d_field *field)
+{
+    char err[512] = "";
+    char *path = (char *)malloc(strlen(out_path) + 16);
+    float *jac = (float *)malloc(sizeof(float) * (size_t)nx * ny * nz);
+    int rc = -1;
+    if (path && jac) {
+        sprintf(path, "%s.jac.nii", out_path);
+        if (sift3d_jacobian_map(device, nx, ny, nz, map, out_vox2key, src_vox2key, field, jac, -1, NULL, err, sizeof err) != SIFT3D_OK)
+            printf("Error: could not compute the Jacobian map: %s\n", err);
+        else if (nifti_min_write_f32_geom(path, jac, geom_path) != 0) printf("Error: could not write output file: %s\n", path);
+        else rc = 0;
+    }
+    free(path);
+    free(jac);
+    return rc;
+}
+
+/* -r: everything after the forward field is known.  t: the forward transform; field: the forward field, or NULL. */
+static int reverse(int device, const char *fixed_path, const char *moving_path, const char *out_path, const nifti_min_image *fixed,
+                   const nifti_min_image *moving, const float t[16], const float fv[16], const float mv[16], const sift3d_field *field, int interp,
+                   float fill, int jacobian)
+{
+    char err[512] = "";
+    float ti[16], tr[16], rmap[12];
+    char *path = (char *)malloc(strlen(out_path) + 24);
+    if (!path) return -1;
+    sprintf(path, "%s.inv.trans.txt", out_path);
+    /* the inverse as a reader of the file gets it: the field below is solved against these digits */
+    if (sift3d_affine_invert(t, ti) != 0 || sift3d_write_matrix(path, ti) != 0 || sift3d_read_similarity(path, tr) != 0 ||
+        sift3d_resample_map(tr, mv, fv, rmap) != 0) {
+        printf("Error: could not invert the transform or write: %s\n", path);
+        free(path);
+        return -1;
+    }
+    free(path);
+    const size_t n_out = (size_t)moving->nx * moving->ny * moving->nz;
+    float *out = (float *)malloc(sizeof(float) * n_out);
+    if (!out) {
+        printf("Error: could not resample, insufficient memory.\n");
+        return -1;
+    }
+    sift3d_field inv;
+    memset(&inv, 0, sizeof inv);
+    double ms = 0;
+    int rc;
+    if (field) {
+        sift3d_invert_params ip;
+        sift3d_invert_defaults(&ip);
+        ip.spacing = field->spacing;
+        sift3d_invert_report rep;
+        if (sift3d_invert_grid(moving->nx, moving->ny, moving->nz, mv, &ip, &inv) != SIFT3D_OK) {
+            printf("Error: the inverse field's grid has more than %lld nodes\n", (long long)ip.max_nodes);
+            return -1;
+        }
+        inv.capacity = 3 * inv.n[0] * inv.n[1] * inv.n[2];
+        inv.disp = (float *)malloc(sizeof(float) * (size_t)inv.capacity);
+        if (!inv.disp || sift3d_invert_field(device, t, tr, field, &ip, &inv, &rep, err, sizeof err) != SIFT3D_OK) {
+            printf("Error: could not invert the field: %s\n", inv.disp ? err : "insufficient memory");
+            return -1;
+        }
+        if (write_inverse(out_path, &inv, &ip, &rep) != 0) {
+            printf("Error: could not write the inverse field files of: %s\n", out_path);
+            return -1;
+        }
+        if (rep.not_converged || rep.diverged)
+            printf("Warning: the inverse field did not converge everywhere: %lld of %lld nodes not converged, %lld diverged (set to 0)\n",
+                   (long long)rep.not_converged, (long long)rep.nodes, (long long)rep.diverged);
+        rc = sift3d_resample_field(device, fixed->data, fixed->nx, fixed->ny, fixed->nz, out, moving->nx, moving->ny, moving->nz, rmap, mv, fv, &inv,
+                                   interp, fill, &ms, err, sizeof err);
+    } else {
+        rc = sift3d_resample_affine(device, fixed->data, fixed->nx, fixed->ny, fixed->nz, out, moving->nx, moving->ny, moving->nz, rmap, interp, fill,
+                                    &ms, err, sizeof err);
+    }
+    if (rc != SIFT3D_OK) {
+        printf("Error: could not resample: %s\n", err);
+        return -1;
+    }
+    if (nifti_min_write_f32_geom(out_path, out, moving_path) != 0) {
+        printf("Error: could not write output file: %s\n", out_path);
+        return -1;
+    }
+    free(out);
+    if (jacobian && write_jacobian(device, out_path, moving_path, moving->nx, moving->ny, moving->nz, rmap, mv, fv, field ? &inv : NULL) != 0) return -1;
+    free(inv.disp);
+    (void)fixed_path;
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     int device = 0, world_mode = 0, interp = SIFT3D_INTERP_LINEAR;
     float fill = 0.0f;
     const char *field_path = NULL;
-    int intensity = 0, rounds = -1, metric = SIFT3D_BLOCKMATCH_SSD;
+    int intensity = 0, rounds = -1, metric = SIFT3D_BLOCKMATCH_SSD, backward = 0, jacobian = 0;
     int arg = 1;
     while (arg < argc && argv[arg][0] == '-') {
         switch (argv[arg][1]) {
@@ -147,6 +271,16 @@ int main(int argc, char **argv)
             }
             metric = SIFT3D_BLOCKMATCH_NCC;
             break;
+        case 'r':
+        case 'j':
+            if (argv[arg][2] != 0) {
+                printf("Error: unknown command line argument: %s\n", argv[arg]);
+                print_options();
+                return -1;
+            }
+            if (argv[arg][1] == 'r') backward = 1;
+            else jacobian = 1;
+            break;
         case 'u':
             if (argv[arg][2] != 0 || arg + 1 >= argc) {
                 printf("Error: -u needs a field file\n");
@@ -180,7 +314,7 @@ int main(int argc, char **argv)
         return -1;
     }
     nifti_min_close(fs);
-    if (intensity && nifti_min_read(fixed_path, &fixed) != 0) { /* -i matches against the fixed image's voxels */
+    if ((intensity || backward) && nifti_min_read(fixed_path, &fixed) != 0) { /* -i matches against the fixed image's voxels, -r resamples them */
         printf("Error: could not read input file: %s\n", fixed_path);
         return -1;
     }
@@ -204,8 +338,9 @@ int main(int argc, char **argv)
         printf("Error: singular transform: %s\n", trans_path);
         return -1;
     }
-    printf("Resampling: %s (i=%d j=%d k=%d) onto %s (i=%d j=%d k=%d)\n", moving_path, moving.nx, moving.ny, moving.nz, fixed_path, fixed.nx,
-           fixed.ny, fixed.nz);
+    if (!backward)
+        printf("Resampling: %s (i=%d j=%d k=%d) onto %s (i=%d j=%d k=%d)\n", moving_path, moving.nx, moving.ny, moving.nz, fixed_path, fixed.nx,
+               fixed.ny, fixed.nz);
     const size_t n_out = (size_t)fixed.nx * fixed.ny * fixed.nz;
     float *out = (float *)malloc(sizeof(float) * n_out);
     if (!out) {
@@ -258,13 +393,24 @@ int main(int argc, char **argv)
         free(field.disp);
         field = refined;
     }
+    if (backward) {
+        printf("Resampling: %s (i=%d j=%d k=%d) onto %s (i=%d j=%d k=%d)\n", fixed_path, fixed.nx, fixed.ny, fixed.nz, moving_path, moving.nx, moving.ny,
+               moving.nz);
+        if (reverse(device, fixed_path, moving_path, out_path, &fixed, &moving, t, fv, mv, field_path || intensity ? &field : NULL, interp, fill,
+                    jacobian) != 0)
+            return -1;
+        printf("\nDone.\n");
+        free(field.disp);
+        free(out);
+        nifti_min_free(&moving);
+        return 0;
+    }
     /* the first volume of a 4-D moving image */
     const int rc = field_path || intensity
                        ? sift3d_resample_field(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map, fv, mv,
                                                &field, interp, fill, &ms, err, sizeof err)
                        : sift3d_resample_affine(device, moving.data, moving.nx, moving.ny, moving.nz, out, fixed.nx, fixed.ny, fixed.nz, map,
                                                 interp, fill, &ms, err, sizeof err);
-    free(field.disp);
     if (rc != SIFT3D_OK) {
         printf("Error: could not resample: %s\n", err);
         return -1;
@@ -273,6 +419,9 @@ int main(int argc, char **argv)
         printf("Error: could not write output file: %s\n", out_path);
         return -1;
     }
+    if (jacobian && write_jacobian(device, out_path, fixed_path, fixed.nx, fixed.ny, fixed.nz, map, fv, mv, field_path || intensity ? &field : NULL) != 0)
+        return -1;
+    free(field.disp);
     printf("\nDone.\n");
     free(out);
     nifti_min_free(&moving);

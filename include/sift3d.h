@@ -880,6 +880,82 @@ int64_t sift3d_blockmatch_samples(const uint32_t *words, int64_t nx, int64_t ny,
 /* sift3d_field_folds for a 4 x 4 T: nodes where det (L + grad v) <= 0, L the inverse of T's linear part */
 int64_t sift3d_blockmatch_folds(const float moving_to_fixed[16], const sift3d_field *f, double *max_disp);
 
+/* ---- the reverse direction: the inverse field and the Jacobian determinant map (featResample -r, -j; beyond the reference) ---
+ * DESIGN.md section 7h states the contract; tests/invert_oracle.c restates it.  M is the forward 4 x 4 (moving key -> fixed
+ * key), phi(y) = inv(M) y + v(y) the forward map (v read through the sift3d_field_eval contract, 0 outside its grid and for a
+ * NULL field).  M' is inv(M) as a reader gets it back from its .trans.txt (sift3d_affine_invert, sift3d_write_matrix,
+ * sift3d_read_similarity).  The inverse field u lives on a node grid in MOVING key space, its values in FIXED key units:
+ * psi(z) = inv(M') z + u(z) solves phi(psi(z)) = z, so (M', u) is an ordinary .trans.txt + .field.nii pair with the roles of
+ * the two images swapped.  With P = inv(M'), Q = inv(M) (sift3d_affine_invert_d) and A the linear part of M, per node z (its
+ * float position widened to double), everything in double unless said:
+ *   b_r = ((P[r][0] z0 + P[r][1] z1) + P[r][2] z2) + P[r][3];  u = 0;  k = 0
+ *   loop:  y = b + u;  v = sift3d_field_eval at (float)y
+ *          r_c = ((((Q[c][0] y0 + Q[c][1] y1) + Q[c][2] y2) + Q[c][3]) + (double)v_c) - z_c;  rr = (r0 r0 + r1 r1) + r2 r2
+ *          rr <= (double)tol (double)tol: converged, stop.  k == max_iter: not converged, stop (u stays).
+ *          u_c = u_c - ((A[c][0] r0 + A[c][1] r1) + A[c][2] r2);  k = k + 1
+ *          a component of u outside [-SIFT3D_FIELD_MAX_DISP, SIFT3D_FIELD_MAX_DISP] or NaN: u = 0, diverged, stop.
+ * The node's value is (float)u, its status word k | state << 16 and its residual the last rr. */
+#define SIFT3D_INVERT_CONVERGED 0u
+#define SIFT3D_INVERT_NOT_CONVERGED 1u
+#define SIFT3D_INVERT_DIVERGED 2u
+#define SIFT3D_INVERT_STEPS(w) ((w) & 0xffffu)
+#define SIFT3D_INVERT_STATE(w) ((w) >> 16)
+#define SIFT3D_INVERT_MAX_ITER 65535
+
+typedef struct {
+    float spacing;     /* h of the inverse grid: 4 key units (featResample passes the forward field's) */
+    float radius;      /* R: the grid reaches R past the moving volume's box: 20 */
+    int32_t max_iter;  /* 30; 1 .. SIFT3D_INVERT_MAX_ITER */
+    float tol;         /* 1e-3 key units; >= 0 (0: every node with a nonzero residual runs to max_iter) */
+    int64_t max_nodes; /* 2^26: larger grids are refused */
+} sift3d_invert_params;
+void sift3d_invert_defaults(sift3d_invert_params *p);
+
+typedef struct {
+    int64_t nodes, converged, not_converged, diverged;
+    int32_t max_steps;                  /* the most steps any node used */
+    double rms_residual, max_residual;  /* of |r| over the converged nodes, summed in node order */
+    double max_disp;                    /* largest |u| over the nodes */
+    int64_t folds;                      /* sift3d_blockmatch_folds(M', u) */
+    double kernel_ms;                   /* device time of field_invert_kernel */
+} sift3d_invert_report;
+
+/* The inverse grid: sift3d_field_size (p's spacing, radius, max_nodes) over the key positions of the moving volume's eight
+ * corner voxels, as sift3d_blockmatch_grid does for the fixed volume.  p NULL: defaults.  Fills n, origin, spacing. */
+int sift3d_invert_grid(int64_t nx, int64_t ny, int64_t nz, const float moving_vox2key[16], const sift3d_invert_params *p, sift3d_field *f);
+/* field_invert_kernel alone on the GPU over the grid in `grid` (n, origin, spacing; its disp is not used): u (3 N floats,
+ * component-major), status (N words) and res2 (N doubles, may be NULL) are host arrays.  forward NULL: v = 0.  SIFT3D_ERR_ARG with
+ * text: a singular matrix or a last row other than 0 0 0 1, max_iter or tol out of range, a grid with an axis outside
+ * 1 .. 2^24 or more than max_nodes nodes, a forward field sift3d_resample_field would refuse. */
+int sift3d_invert_nodes(int device, const float m[16], const float m_inv[16], const sift3d_field *forward, const sift3d_invert_params *p,
+                        const sift3d_field *grid, float *u, uint32_t *status, double *res2, double *kernel_ms, char *err, int64_t err_len);
+/* The stage: sift3d_invert_nodes over out's grid (the caller sets out->n, origin and spacing, from sift3d_invert_grid) into
+ * out->disp, and the report.  out->capacity < 3 N or no out->disp: SIFT3D_ERR_CAPACITY, the grid left filled in.  Nodes that did
+ * not converge keep their last iterate, diverged nodes get 0; both are counted, neither is an error.  rep may be NULL. */
+int sift3d_invert_field(int device, const float m[16], const float m_inv[16], const sift3d_field *forward, const sift3d_invert_params *p,
+                        sift3d_field *out, sift3d_invert_report *rep, char *err, int64_t err_len);
+/* The Jacobian determinant of a warp on its output grid (jacobian_map_kernel): with q(p) the output voxel -> source voxel map
+ * sift3d_resample_field applies for (map, out_vox2key, src_vox2key, field) -- its position arithmetic, for any p -- per voxel p
+ *   D[r][a] = (q_r(p + e_a) - q_r(p - e_a)) * 0.5f in float;  det D in double in sift3d_blockmatch_folds' order;
+ *   J(p) = (float)(det D * factor),  factor = det lin(src_vox2key) / det lin(out_vox2key) in double (sift3d_jacobian_factor).
+ * That is det grad phi in key units: the physical volume ratio under -w, the voxel-count ratio with voxel keys.  J <= 0 is a
+ * fold; a NaN node gives NaN.  field NULL: the affine map alone.  out: ox oy oz floats (host).  form 0: six evaluations of q per
+ * voxel; 1: the workgroup's brick and a one-voxel halo evaluated once into LDS; -1: the default.  Same
+ * numbers from both.  Extents as sift3d_resample_field's output. */
+int sift3d_jacobian_map(int device, int64_t ox, int64_t oy, int64_t oz, const float map[12], const float out_vox2key[16],
+                        const float src_vox2key[16], const sift3d_field *field, float *out, int form, double *kernel_ms, char *err,
+                        int64_t err_len);
+/* Host helpers (also in libsift3d_host.so).
+ * The inverse of an affine 4 x 4 (last row 0 0 0 1): the adjugate of the 3 x 3 part over its determinant, then
+ * t'_r = -((o[r][0] t0 + o[r][1] t1) + o[r][2] t2), in double; sift3d_affine_invert rounds to float once.  0, or -1 for a last
+ * row other than 0 0 0 1 or a singular or non-finite matrix. */
+int sift3d_affine_invert_d(const float m[16], double out[16]);
+int sift3d_affine_invert(const float m[16], float out[16]);
+/* m in the .trans.txt layout (%f, tabs, the last row as 0.0 0.0 0.0 1.0), so that sift3d_read_similarity reads it back */
+int sift3d_write_matrix(const char *path, const float m[16]);
+/* det lin(src_vox2key) / det lin(out_vox2key) in double (NULL: identity); 0, or -1 where one of them is 0 or not finite */
+int sift3d_jacobian_factor(const float out_vox2key[16], const float src_vox2key[16], double *factor);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
