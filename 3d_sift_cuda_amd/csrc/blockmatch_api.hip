@@ -10,16 +10,13 @@
 #include <cstring>
 #include <vector>
 
-#include "device_call.h"
+#include "field_call.h"
 
 hipError_t sift3d_launch_bm_quantize(hipStream_t s, const float *src, int64_t n, double lo, double hi, short *dst);
 hipError_t sift3d_launch_block_match(hipStream_t s, const short *qf, const short *qw, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
                                      int64_t stride, const int64_t n[3], int b, int r, int generic, unsigned *out);
 hipError_t sift3d_launch_block_match_ncc(hipStream_t s, const short *qf, const short *qw, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
                                          int64_t stride, const int64_t n[3], int b, int r, int generic, unsigned *out);
-hipError_t sift3d_launch_field_warp(hipStream_t s, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
-                                    int64_t oz, const float *map, const float *c, const float *k, const float o[3], float h, const int64_t n[3],
-                                    const float4 *nodes, int nearest, float fill);
 
 #define BM_MAX_EXTENT ((1ll << 27) - 1)
 #define BM_MAX_NODES (1ll << 27)
@@ -99,36 +96,6 @@ extern "C" int sift3d_block_match_ncc(int device, const float *f, const float *w
     return block_match(SIFT3D_BLOCKMATCH_NCC, device, f, w, nx, ny, nz, first, stride, count, b, r, generic, out, kernel_ms, err, err_len);
 }
 
-static int64_t nodes_of(const sift3d_field &f) { return f.n[0] * f.n[1] * f.n[2]; }
-
-static double rms_of(const std::vector<double> &r)
-{
-    double s = 0;
-    for (double x : r) s += x * x;
-    return r.empty() ? 0.0 : std::sqrt(s / (double)r.size());
-}
-
-/* e_i = |v_i - v(y_i)| in double (section 7e's residual) */
-static void residuals(const sift3d_field &f, const float *y, const float *v, size_t n, std::vector<double> &e)
-{
-    std::vector<float> fit(3 * std::max<size_t>(n, 1));
-    sift3d_field_eval(&f, y, (int64_t)n, fit.data());
-    e.resize(n);
-    for (size_t i = 0; i < n; i++) {
-        const double dx = (double)v[3 * i] - (double)fit[3 * i], dy = (double)v[3 * i + 1] - (double)fit[3 * i + 1],
-                     dz = (double)v[3 * i + 2] - (double)fit[3 * i + 2];
-        e[i] = std::sqrt((dx * dx + dy * dy) + dz * dz);
-    }
-}
-
-static bool field_ok(const sift3d_field *f)
-{
-    if (!f->disp || !(f->spacing > 0) || !std::isfinite(f->spacing)) return false;
-    for (int k = 0; k < 3; k++)
-        if (f->n[k] < 2 || f->n[k] > (1 << 24)) return false;
-    return f->n[0] * f->n[1] <= (1ll << 40) / f->n[2] && f->capacity >= 3 * nodes_of(*f);
-}
-
 extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fixed, int64_t fx, int64_t fy, int64_t fz, const float *moving,
                                                     int64_t mx, int64_t my, int64_t mz, const float fixed_vox2key[16],
                                                     const float moving_vox2key[16], const float moving_to_fixed[16], const sift3d_field *in,
@@ -145,9 +112,9 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
     if (pp) p = *pp;
     else sift3d_blockmatch_defaults(&p);
     if (!fixed || !moving || !moving_to_fixed || !out) return call_fail(err, err_len, SIFT3D_ERR_ARG, "null pointer");
-    if (mx < 1 || my < 1 || mz < 1 || mx > (1 << 24) || my > (1 << 24) || mz > (1 << 24))
-        return call_fail(err, err_len, SIFT3D_ERR_ARG, "source extents must be 1 .. 2^24");
-    if (in && !field_ok(in)) return call_fail(err, err_len, SIFT3D_ERR_ARG, "the input field needs 2 .. 2^24 nodes per axis, a positive spacing and its values");
+    const char *why = check_source_extents(mx, my, mz);
+    if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%s", why);
+    if (in && check_field(*in) != nullptr) return call_fail(err, err_len, SIFT3D_ERR_ARG, "the input field needs 2 .. 2^24 nodes per axis, a positive spacing and its values");
     int64_t first[3], count[3];
     sift3d_field grid;
     memset(&grid, 0, sizeof grid);
@@ -159,7 +126,7 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
                          "or an output grid of more than max_nodes = %lld nodes", (long long)p.max_nodes);
     if (sift3d_blockmatch_lattice(fx, fy, fz, &p, first, count) != 0)
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the block and search window (%d voxels) is wider than the volume", 2 * (p.block + p.search) + 1);
-    const char *why = check_search(fx, fy, fz, first, p.stride, count, p.block, p.search);
+    why = check_search(fx, fy, fz, first, p.stride, count, p.block, p.search);
     if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%s", why);
     const int64_t NL = count[0] * count[1] * count[2], NG = nodes_of(grid);
     if (NL > p.max_nodes) return call_fail(err, err_len, SIFT3D_ERR_ARG, "the lattice has more than max_nodes = %lld nodes", (long long)p.max_nodes);
@@ -180,7 +147,7 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
     memset(&rp, 0, sizeof rp);
     /* the current field: the input's grid and values, or zero on the output grid */
     sift3d_field cur = in ? *in : grid;
-    std::vector<float> cur_disp((size_t)(3 * nodes_of(cur)), 0.0f), disp1((size_t)(3 * NG));
+    std::vector<float> cur_disp((size_t)(3 * nodes_of(cur)), 0.0f);
     if (in) std::copy(in->disp, in->disp + 3 * nodes_of(cur), cur_disp.begin());
     cur.disp = cur_disp.data();
     cur.capacity = (int64_t)cur_disp.size();
@@ -216,14 +183,11 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
         DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, (int64_t)nf, (double)rp.lo, (double)rp.hi, d_qf));
         DEVCHK(dc, dc.to_device(d_m, moving, nm));
         std::vector<uint32_t> words((size_t)NL * SIFT3D_BLOCKMATCH_WORDS);
-        std::vector<float> y((size_t)(3 * NL)), v((size_t)(3 * NL)), yk, vk;
-        std::vector<float4> nodes(max_nodes);
-        std::vector<double> e;
+        std::vector<float> y((size_t)(3 * NL)), v((size_t)(3 * NL));
+        std::vector<float4> nodes; /* send_nodes packs into it: it lives until the stream is synchronised */
         for (int round = 0; round < p.rounds; round++) {
             sift3d_blockmatch_round &r = rp.round[round];
-            const int64_t NC = nodes_of(cur);
-            for (int64_t i = 0; i < NC; i++) nodes[i] = make_float4(cur.disp[i], cur.disp[NC + i], cur.disp[2 * NC + i], 0.0f);
-            DEVCHK(dc, dc.to_device(d_nodes, nodes.data(), (size_t)NC));
+            DEVCHK(dc, send_nodes(dc, cur, nodes, d_nodes));
             DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
             DEVCHK(dc, sift3d_launch_field_warp(dc.s, d_m, mx, my, mz, d_w, fx, fy, fz, map, cterm, kterm, cur.origin, cur.spacing, cur.n, d_nodes, 0,
                                                 std::nanf("")));
@@ -251,34 +215,14 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
             for (int64_t i = 0; i < 3 * ns; i++)
                 if (std::isfinite(v[i]) && !(std::fabs(v[i]) <= SIFT3D_FIELD_MAX_DISP))
                     return call_fail(err, err_len, SIFT3D_ERR_ARG, "a sample's |v| exceeds SIFT3D_FIELD_MAX_DISP (128 key units)");
-            sift3d_field f1 = grid;
-            f1.disp = disp1.data();
-            f1.capacity = 3 * NG;
-            int rc = fit_on_grid(dc, y.data(), v.data(), ns, f1, p.radius, p.lambda, disp1.data(), &r.fit_ms[0]);
-            if (rc != SIFT3D_OK) return rc;
-            /* section 7e's trim: e_i <= max(min_tol, 3 x the lower median), then the second fit on the same grid */
-            residuals(f1, y.data(), v.data(), (size_t)ns, e);
-            r.rms_before = rms_of(e);
-            std::vector<double> srt(e);
-            const size_t lm = (srt.size() - 1) / 2;
-            std::nth_element(srt.begin(), srt.begin() + lm, srt.end());
-            const double thr = std::max((double)p.min_tol, 3.0 * srt[lm]);
-            yk.clear();
-            vk.clear();
-            for (int64_t k = 0; k < ns; k++)
-                if (e[k] <= thr) {
-                    yk.insert(yk.end(), y.begin() + 3 * k, y.begin() + 3 * k + 3);
-                    vk.insert(vk.end(), v.begin() + 3 * k, v.begin() + 3 * k + 3);
-                }
-            r.kept = (int64_t)(yk.size() / 3);
+            /* section 7e's two passes on the output grid; the current field's values are no longer needed */
             cur_disp.assign((size_t)(3 * NG), 0.0f);
             cur = grid;
             cur.disp = cur_disp.data();
             cur.capacity = 3 * NG;
-            rc = fit_on_grid(dc, yk.data(), vk.data(), r.kept, cur, p.radius, p.lambda, cur.disp, &r.fit_ms[1]);
+            const int rc = fit_trim_refit(dc, y.data(), v.data(), ns, grid, p.radius, p.lambda, p.min_tol, cur.disp, &r.kept, &r.rms_before,
+                                          &r.rms_after, r.fit_ms);
             if (rc != SIFT3D_OK) return rc;
-            residuals(cur, yk.data(), vk.data(), (size_t)r.kept, e);
-            r.rms_after = rms_of(e);
             r.folds = sift3d_blockmatch_folds(moving_to_fixed, &cur, &r.max_disp);
             rp.rounds = round + 1;
         }

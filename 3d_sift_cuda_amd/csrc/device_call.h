@@ -1,10 +1,11 @@
 /*
  * device_call.h -- what one call of a host-array entry point (sift3d_knn64, the alignment, resampling and guided re-matching
  * calls) holds on the device: a non-blocking stream, two timing events and its device buffers, released together when the
- * call returns, and the messages those entry points write into the caller's err.  Internal: nothing here is part of the C-ABI.
+ * call returns, the messages those entry points write into the caller's err, and the RMS their reports give.  Internal: nothing here is part of the C-ABI.
  */
 #ifndef SIFT3D_DEVICE_CALL_H
 #define SIFT3D_DEVICE_CALL_H
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <vector>
@@ -23,6 +24,14 @@ __attribute__((format(printf, 4, 5))) inline int call_fail(char *err, int64_t er
         va_end(ap);
     }
     return rc;
+}
+
+/* the root mean square of the residuals r, as the refinement reports give it; 0 for none */
+inline double rms_of(const std::vector<double> &r)
+{
+    double s = 0;
+    for (double x : r) s += x * x;
+    return r.empty() ? 0.0 : std::sqrt(s / (double)r.size());
 }
 
 struct device_call {
@@ -86,10 +95,6 @@ struct device_call {
         const int rc_ = (dc).check((call), #call);            \
         if (rc_ != SIFT3D_OK) return rc_;                     \
     } while (0)
-
-/* field_api.hip: one fit of the samples y, v (n x 3 floats, host) on the grid g into disp (3 N floats, host) */
-int fit_on_grid(device_call &dc, const float *y, const float *v, int64_t n, const sift3d_field &g, float R, float lambda, float *disp,
-                double *kernel_ms);
 
 #pragma GCC visibility pop
 #endif

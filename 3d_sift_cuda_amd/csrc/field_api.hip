@@ -9,21 +9,16 @@
 #include <cstring>
 #include <vector>
 
-#include "device_call.h"
+#include "field_call.h"
 #include "guided_accept.h"
 
 hipError_t sift3d_launch_field_fit(hipStream_t s, const float4 *ys, const float4 *vs, const int *start, const double co[3], double edge,
-                                   const long long cn[3], const float o[3], float h, const long long n[3], float rr, double lam24, float *out);
-hipError_t sift3d_launch_field_warp(hipStream_t s, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
-                                    int64_t oz, const float *map, const float *c, const float *k, const float o[3], float h, const int64_t n[3],
-                                    const float4 *nodes, int nearest, float fill);
+                                   const long long cn[3], const float o[3], float h, const int64_t n[3], float rr, double lam24, float *out);
 
 static bool finite6(const float *y, const float *v)
 {
     return std::isfinite(y[0]) && std::isfinite(y[1]) && std::isfinite(y[2]) && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
 }
-
-static int64_t nodes_of(const sift3d_field *f) { return f->n[0] * f->n[1] * f->n[2]; }
 
 /* NULL when every finite sample is within the bound, else the reason */
 static const char *check_samples(const float *v, int64_t n)
@@ -37,7 +32,7 @@ static const char *check_samples(const float *v, int64_t n)
  * binned into a uniform grid of cells of edge R (1 + 2^-10) over their bounding box, widened until an axis has at most 2^20
  * cells and the grid at most 2^24: a passing sample is less than R from the node on every axis (plus float rounding, which
  * the margin covers), so the 27 cells around the node's cell hold it.  Shared with blockmatch_api.hip (declared in
- * device_call.h). */
+ * field_call.h). */
 int fit_on_grid(device_call &dc, const float *y, const float *v, int64_t n, const sift3d_field &g, float R, float lambda, float *disp,
                        double *kernel_ms)
 {
@@ -81,7 +76,7 @@ int fit_on_grid(device_call &dc, const float *y, const float *v, int64_t n, cons
         ys[at] = make_float4(p[0], p[1], p[2], 0.0f);
         vs[at] = make_float4(q[0], q[1], q[2], 0.0f);
     }
-    const int64_t N = nodes_of(&g);
+    const int64_t N = nodes_of(g);
     float4 *d_y, *d_v;
     int *d_start;
     float *d_out;
@@ -93,9 +88,8 @@ int fit_on_grid(device_call &dc, const float *y, const float *v, int64_t n, cons
         return call_fail(dc.err, dc.err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", sizeof(float) * 3 * (size_t)N, dc.device);
     }
     const double co[3] = {mn[0], mn[1], mn[2]};
-    const long long gn[3] = {g.n[0], g.n[1], g.n[2]};
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
-    DEVCHK(dc, sift3d_launch_field_fit(dc.s, d_y, d_v, d_start, co, edge, cn, g.origin, g.spacing, gn, R * R, (double)lambda * 16777216.0, d_out));
+    DEVCHK(dc, sift3d_launch_field_fit(dc.s, d_y, d_v, d_start, co, edge, cn, g.origin, g.spacing, g.n, R * R, (double)lambda * 16777216.0, d_out));
     DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
     DEVCHK(dc, dc.download(disp, d_out, (size_t)N * 3));
     DEVCHK(dc, dc.sync());
@@ -129,32 +123,48 @@ extern "C" int sift3d_fit_field(int device, const float *y, const float *v, int6
     if (sift3d_field_size(y, n, &p, f) != SIFT3D_OK)
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the grid has more than max_nodes = %lld nodes or more than 2^24 along an axis",
                          (long long)p.max_nodes);
-    const int64_t N = nodes_of(f);
+    const int64_t N = nodes_of(*f);
     if (f->capacity < 3 * N || !f->disp) return call_fail(err, err_len, SIFT3D_ERR_CAPACITY, "the field needs %lld floats", (long long)(3 * N));
     device_call dc(err, err_len);
     DEVCHK(dc, dc.open(device));
     return fit_on_grid(dc, y, v, n, *f, p.radius, p.lambda, f->disp, kernel_ms);
 }
 
-/* e_i = |v_i - v(y_i)| in double */
-static void local_residuals(const sift3d_field &f, const std::vector<float> &y, const std::vector<float> &v, std::vector<double> &e)
+int fit_trim_refit(device_call &dc, const float *y, const float *v, int64_t n, const sift3d_field &g, float R, float lambda, float min_tol,
+                   float *out_disp, int64_t *kept, double *rms_before, double *rms_after, double fit_ms[2])
 {
-    const size_t n = y.size() / 3;
-    std::vector<float> fit(3 * std::max<size_t>(n, 1));
-    sift3d_field_eval(&f, y.data(), (int64_t)n, fit.data());
-    e.resize(n);
-    for (size_t i = 0; i < n; i++) {
-        const double dx = (double)v[3 * i] - (double)fit[3 * i], dy = (double)v[3 * i + 1] - (double)fit[3 * i + 1],
-                     dz = (double)v[3 * i + 2] - (double)fit[3 * i + 2];
-        e[i] = std::sqrt((dx * dx + dy * dy) + dz * dz);
+    /* pass 1 over all samples */
+    const int64_t N = nodes_of(g);
+    std::vector<float> disp1((size_t)N * 3);
+    sift3d_field f = g;
+    f.disp = disp1.data();
+    f.capacity = 3 * N;
+    int rc = fit_on_grid(dc, y, v, n, f, R, lambda, disp1.data(), &fit_ms[0]);
+    if (rc != SIFT3D_OK) return rc;
+    /* trim: e_i <= max(min_tol, 3 x the lower median), then pass 2 over the kept samples on the same grid */
+    std::vector<double> e;
+    residuals(f, y, v, (size_t)n, e);
+    *rms_before = rms_of(e);
+    double thr = (double)min_tol;
+    if (!e.empty()) {
+        std::vector<double> srt(e);
+        const size_t lm = (srt.size() - 1) / 2;
+        std::nth_element(srt.begin(), srt.begin() + lm, srt.end());
+        thr = std::max(thr, 3.0 * srt[lm]);
     }
-}
-
-static double rms_of(const std::vector<double> &r)
-{
-    double s = 0;
-    for (double x : r) s += x * x;
-    return r.empty() ? 0.0 : std::sqrt(s / (double)r.size());
+    std::vector<float> yk, vk;
+    for (int64_t k = 0; k < n; k++)
+        if (e[k] <= thr) {
+            yk.insert(yk.end(), y + 3 * k, y + 3 * k + 3);
+            vk.insert(vk.end(), v + 3 * k, v + 3 * k + 3);
+        }
+    *kept = (int64_t)(yk.size() / 3);
+    f.disp = out_disp;
+    rc = fit_on_grid(dc, yk.data(), vk.data(), *kept, f, R, lambda, out_disp, &fit_ms[1]);
+    if (rc != SIFT3D_OK) return rc;
+    residuals(f, yk.data(), vk.data(), (size_t)*kept, e);
+    *rms_after = rms_of(e);
+    return SIFT3D_OK;
 }
 
 extern "C" int sift3d_refine_field(int device, const sift3d_feature *fixed, int64_t n_fixed, const sift3d_feature *moving, int64_t n_moving,
@@ -198,63 +208,32 @@ extern "C" int sift3d_refine_field(int device, const sift3d_feature *fixed, int6
     if (sift3d_field_size(y.data(), (int64_t)na, &p, out) != SIFT3D_OK)
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the grid has more than max_nodes = %lld nodes or more than 2^24 along an axis",
                          (long long)p.max_nodes);
-    const int64_t N = nodes_of(out);
+    const int64_t N = nodes_of(*out);
     if (out->capacity < 3 * N || !out->disp) {
         if (rep) *rep = rp;
         return call_fail(err, err_len, SIFT3D_ERR_CAPACITY, "the field needs %lld floats", (long long)(3 * N));
     }
     device_call dc(err, err_len);
     DEVCHK(dc, dc.open(device));
-    /* pass 1 over the accepted samples */
-    sift3d_field f1 = *out;
-    std::vector<float> disp1((size_t)N * 3);
-    f1.disp = disp1.data();
-    f1.capacity = 3 * N;
-    int rc = fit_on_grid(dc, y.data(), v.data(), (int64_t)na, f1, p.radius, p.lambda, disp1.data(), &rp.fit_ms[0]);
+    int64_t kept;
+    const int rc = fit_trim_refit(dc, y.data(), v.data(), (int64_t)na, *out, p.radius, p.lambda, p.min_tol, out->disp, &kept, &rp.rms_before,
+                                  &rp.rms_after, rp.fit_ms);
     if (rc != SIFT3D_OK) return rc;
-    /* trim: e_i <= max(min_tol, 3 x the lower median), then pass 2 over the kept samples on the same grid */
-    std::vector<double> e;
-    local_residuals(f1, y, v, e);
-    rp.rms_before = rms_of(e);
-    double thr = (double)p.min_tol;
-    if (!e.empty()) {
-        std::vector<double> srt(e);
-        const size_t lm = (srt.size() - 1) / 2;
-        std::nth_element(srt.begin(), srt.begin() + lm, srt.end());
-        thr = std::max(thr, 3.0 * srt[lm]);
-    }
-    std::vector<float> yk, vk;
-    for (size_t k = 0; k < na; k++)
-        if (e[k] <= thr) {
-            yk.insert(yk.end(), y.begin() + 3 * k, y.begin() + 3 * k + 3);
-            vk.insert(vk.end(), v.begin() + 3 * k, v.begin() + 3 * k + 3);
-        }
-    rp.kept = (int32_t)(yk.size() / 3);
-    rc = fit_on_grid(dc, yk.data(), vk.data(), rp.kept, *out, p.radius, p.lambda, out->disp, &rp.fit_ms[1]);
-    if (rc != SIFT3D_OK) return rc;
-    local_residuals(*out, yk, vk, e);
-    rp.rms_after = rms_of(e);
+    rp.kept = (int32_t)kept;
     rp.folds = sift3d_field_folds(t, out, &rp.max_disp);
     if (rep) *rep = rp;
     return SIFT3D_OK;
 }
 
-/* NULL when the arguments are usable, else the reason: section 7c's shapes, and a node grid of 2 .. 2^24 nodes per axis with
- * a positive finite spacing and its values */
+/* NULL when the arguments are usable, else the reason: section 7c's shapes and check_field's rules */
 static const char *check_warp(const float *src, int64_t nx, int64_t ny, int64_t nz, const float *dst, int64_t ox, int64_t oy, int64_t oz,
                               const float *map, int interp, const sift3d_field *f)
 {
     if (!src || !dst || !map || !f) return "null pointer";
     if (interp != SIFT3D_INTERP_LINEAR && interp != SIFT3D_INTERP_NEAREST) return "interp must be SIFT3D_INTERP_LINEAR or SIFT3D_INTERP_NEAREST";
-    if (nx < 1 || ny < 1 || nz < 1 || nx > (1 << 24) || ny > (1 << 24) || nz > (1 << 24)) return "source extents must be 1 .. 2^24";
-    if (ox < 1 || oy < 1 || oz < 1 || ox >= (1ll << 31) || oy >= (1ll << 31) || oz >= (1ll << 31)) return "output extents must be 1 .. 2^31 - 1";
-    if (ox * oy > (1ll << 40) / oz) return "output larger than 2^40 voxels";
-    for (int k = 0; k < 3; k++)
-        if (f->n[k] < 2 || f->n[k] > (1 << 24)) return "the field needs 2 .. 2^24 nodes per axis";
-    if (!(f->spacing > 0) || !std::isfinite(f->spacing)) return "the field's spacing must be positive and finite";
-    if (f->n[0] * f->n[1] > (1ll << 40) / f->n[2]) return "the field has more than 2^40 nodes";
-    if (!f->disp || f->capacity < 3 * nodes_of(f)) return "the field's disp holds fewer than 3 n0 n1 n2 floats";
-    return nullptr;
+    const char *why = check_source_extents(nx, ny, nz);
+    if (!why) why = check_output_extents(ox, oy, oz);
+    return why ? why : check_field(*f);
 }
 
 extern "C" int sift3d_resample_field(int device, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
@@ -268,9 +247,8 @@ extern "C" int sift3d_resample_field(int device, const float *src, int64_t nx, i
     float c[12], k[9];
     if (sift3d_field_warp_terms(fixed_vox2key, moving_vox2key, c, k) != 0)
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "a vox2key's last row is not 0 0 0 1, or moving_vox2key is singular");
-    const int64_t N = nodes_of(field);
-    std::vector<float4> nodes((size_t)N);
-    for (int64_t i = 0; i < N; i++) nodes[i] = make_float4(field->disp[i], field->disp[N + i], field->disp[2 * N + i], 0.0f);
+    const int64_t N = nodes_of(*field);
+    std::vector<float4> nodes; /* send_nodes packs into it: it lives until the stream is synchronised */
     const size_t n_in = (size_t)(nx * ny * nz), n_out = (size_t)(ox * oy * oz);
     device_call dc(err, err_len);
     float *d_src, *d_dst;
@@ -282,7 +260,7 @@ extern "C" int sift3d_resample_field(int device, const float *src, int64_t nx, i
                          sizeof(float) * n_out, sizeof(float4) * (size_t)N, device);
     }
     DEVCHK(dc, dc.to_device(d_src, src, n_in));
-    DEVCHK(dc, dc.to_device(d_nodes, nodes.data(), (size_t)N));
+    DEVCHK(dc, send_nodes(dc, *field, nodes, d_nodes));
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
     DEVCHK(dc, sift3d_launch_field_warp(dc.s, d_src, nx, ny, nz, d_dst, ox, oy, oz, map, c, k, field->origin, field->spacing, field->n, d_nodes,
                                         interp == SIFT3D_INTERP_NEAREST, fill));

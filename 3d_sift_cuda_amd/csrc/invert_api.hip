@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "device_call.h"
+#include "field_call.h"
 
 hipError_t sift3d_launch_field_invert(hipStream_t s, const float4 *fwd, const float fo[3], float fh, const int64_t fn[3], const float go[3], float gh,
                                       const int64_t gn[3], const double p[12], const double q[12], const double a[9], double tol2, int max_iter,
@@ -17,26 +17,6 @@ hipError_t sift3d_launch_jacobian_map(hipStream_t s, float *dst, int64_t ox, int
 
 /* the form of jacobian_map_kernel that form = -1 selects */
 #define JACOBIAN_DEFAULT_FORM 1
-
-static int64_t nodes_of(const sift3d_field *f) { return f->n[0] * f->n[1] * f->n[2]; }
-
-/* NULL, or why a field cannot be gathered from: sift3d_resample_field's rules */
-static const char *check_field(const sift3d_field *f)
-{
-    for (int k = 0; k < 3; k++)
-        if (f->n[k] < 2 || f->n[k] > (1 << 24)) return "the field needs 2 .. 2^24 nodes per axis";
-    if (!(f->spacing > 0) || !std::isfinite(f->spacing)) return "the field's spacing must be positive and finite";
-    if (f->n[0] * f->n[1] > (1ll << 40) / f->n[2]) return "the field has more than 2^40 nodes";
-    if (!f->disp || f->capacity < 3 * nodes_of(f)) return "the field's disp holds fewer than 3 n0 n1 n2 floats";
-    return nullptr;
-}
-
-static void pack_nodes(const sift3d_field *f, std::vector<float4> &nodes)
-{
-    const int64_t N = nodes_of(f);
-    nodes.resize((size_t)N);
-    for (int64_t i = 0; i < N; i++) nodes[i] = make_float4(f->disp[i], f->disp[N + i], f->disp[2 * N + i], 0.0f);
-}
 
 extern "C" int sift3d_invert_nodes(int device, const float m[16], const float m_inv[16], const sift3d_field *forward, const sift3d_invert_params *pp,
                                    const sift3d_field *grid, float *u, uint32_t *status, double *res2, double *kernel_ms, char *err, int64_t err_len)
@@ -63,24 +43,24 @@ extern "C" int sift3d_invert_nodes(int device, const float m[16], const float m_
     if (total > (double)p.max_nodes)
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the inverse grid has more than max_nodes = %lld nodes", (long long)p.max_nodes);
     if (forward) {
-        const char *why = check_field(forward);
+        const char *why = check_field(*forward);
         if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%s", why);
     }
-    const size_t N = (size_t)nodes_of(grid);
-    std::vector<float4> nodes;
-    if (forward) pack_nodes(forward, nodes);
+    const size_t N = (size_t)nodes_of(*grid);
+    std::vector<float4> nodes; /* send_nodes packs into it: it lives until the stream is synchronised */
+    const size_t NF = forward ? (size_t)nodes_of(*forward) : 0;
     device_call dc(err, err_len);
     float4 *d_nodes = nullptr;
     float *d_u;
     unsigned *d_status;
     double *d_res;
     DEVCHK(dc, dc.open(device));
-    if ((forward && dc.alloc(&d_nodes, nodes.size()) != hipSuccess) || dc.alloc(&d_u, 3 * N) != hipSuccess || dc.alloc(&d_status, N) != hipSuccess ||
+    if ((forward && dc.alloc(&d_nodes, NF) != hipSuccess) || dc.alloc(&d_u, 3 * N) != hipSuccess || dc.alloc(&d_status, N) != hipSuccess ||
         dc.alloc(&d_res, N) != hipSuccess) {
         (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu bytes on device %d", sizeof(float4) * nodes.size(), 24 * N, device);
+        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu bytes on device %d", sizeof(float4) * NF, 24 * N, device);
     }
-    if (forward) DEVCHK(dc, dc.to_device(d_nodes, nodes.data(), nodes.size()));
+    if (forward) DEVCHK(dc, send_nodes(dc, *forward, nodes, d_nodes));
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
     DEVCHK(dc, sift3d_launch_field_invert(dc.s, d_nodes, forward ? forward->origin : nullptr, forward ? forward->spacing : 0.0f,
                                           forward ? forward->n : nullptr, grid->origin, grid->spacing, grid->n, P, Q, A, (double)p.tol * (double)p.tol,
@@ -106,7 +86,7 @@ extern "C" int sift3d_invert_field(int device, const float m[16], const float m_
         total *= (double)out->n[k];
     }
     if (total > (double)(1ll << 40)) return call_fail(err, err_len, SIFT3D_ERR_ARG, "the inverse grid has more than 2^40 nodes");
-    const int64_t N = nodes_of(out);
+    const int64_t N = nodes_of(*out);
     if (out->capacity < 3 * N || !out->disp) return call_fail(err, err_len, SIFT3D_ERR_CAPACITY, "the field needs %lld floats", (long long)(3 * N));
     sift3d_invert_report rp;
     memset(&rp, 0, sizeof rp);
@@ -142,30 +122,26 @@ extern "C" int sift3d_jacobian_map(int device, int64_t ox, int64_t oy, int64_t o
     if (kernel_ms) *kernel_ms = 0.0;
     if (!map || !out) return call_fail(err, err_len, SIFT3D_ERR_ARG, "null pointer");
     if (form < -1 || form > 1) return call_fail(err, err_len, SIFT3D_ERR_ARG, "form must be 0 (six evaluations), 1 (through LDS) or -1 (the default)");
-    if (ox < 1 || oy < 1 || oz < 1 || ox >= (1ll << 31) || oy >= (1ll << 31) || oz >= (1ll << 31))
-        return call_fail(err, err_len, SIFT3D_ERR_ARG, "output extents must be 1 .. 2^31 - 1");
-    if (ox * oy > (1ll << 40) / oz) return call_fail(err, err_len, SIFT3D_ERR_ARG, "output larger than 2^40 voxels");
-    if (field) {
-        const char *why = check_field(field);
-        if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%s", why);
-    }
+    const char *why = check_output_extents(ox, oy, oz);
+    if (!why && field) why = check_field(*field);
+    if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%s", why);
     float c[12], k[9];
     double factor;
     if (sift3d_field_warp_terms(out_vox2key, src_vox2key, c, k) != 0 || sift3d_jacobian_factor(out_vox2key, src_vox2key, &factor) != 0)
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "a vox2key's last row is not 0 0 0 1, or a vox2key is singular");
-    std::vector<float4> nodes;
-    if (field) pack_nodes(field, nodes);
+    std::vector<float4> nodes; /* send_nodes packs into it: it lives until the stream is synchronised */
+    const size_t NF = field ? (size_t)nodes_of(*field) : 0;
     const size_t n_out = (size_t)(ox * oy * oz);
     device_call dc(err, err_len);
     float *d_dst;
     float4 *d_nodes = nullptr;
     DEVCHK(dc, dc.open(device));
-    if (dc.alloc(&d_dst, n_out) != hipSuccess || (field && dc.alloc(&d_nodes, nodes.size()) != hipSuccess)) {
+    if (dc.alloc(&d_dst, n_out) != hipSuccess || (field && dc.alloc(&d_nodes, NF) != hipSuccess)) {
         (void)hipGetLastError();
         return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu bytes on device %d", sizeof(float) * n_out,
-                         sizeof(float4) * nodes.size(), device);
+                         sizeof(float4) * NF, device);
     }
-    if (field) DEVCHK(dc, dc.to_device(d_nodes, nodes.data(), nodes.size()));
+    if (field) DEVCHK(dc, send_nodes(dc, *field, nodes, d_nodes));
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
     DEVCHK(dc, sift3d_launch_jacobian_map(dc.s, d_dst, ox, oy, oz, map, c, k, field ? field->origin : nullptr, field ? field->spacing : 0.0f,
                                           field ? field->n : nullptr, d_nodes, factor, form < 0 ? JACOBIAN_DEFAULT_FORM : form));

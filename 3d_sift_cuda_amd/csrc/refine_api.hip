@@ -278,13 +278,6 @@ static double residual(const sift3d_similarity *t, const RecordSet &M, int32_t m
     return residual(t, p, F.x(f), F.y(f), F.z(f));
 }
 
-static double rms_of(const std::vector<double> &r)
-{
-    double s = 0;
-    for (double v : r) s += v * v;
-    return r.empty() ? 0.0 : std::sqrt(s / (double)r.size());
-}
-
 /* the fit over pairs (moving index, fixed index) */
 static int fit_pairs(const RecordSet &F, const RecordSet &M, const std::vector<int32_t> &pm, const std::vector<int32_t> &pf, sift3d_similarity *t)
 {

@@ -3,20 +3,17 @@
  * sift3d_resample_affine on host arrays and sift3d_resample_affine_dev on device buffers, on a context's stream.  The
  * kernel is in kernels_resample.hip; the map comes from sift3d_resample_map (align_host.c).
  */
-#include "device_call.h"
+#include "field_call.h"
 #include "pipeline.h"
 
-/* NULL when the arguments are usable, else the reason.  Source extents up to 2^24, so that n - 1 is exact in float and
- * the inside test can never admit a position past the last voxel; output extents up to 2^31 each, 2^40 voxels in all. */
+/* NULL when the arguments are usable, else the reason */
 static const char *check_args(const float *src, int64_t nx, int64_t ny, int64_t nz, const float *dst, int64_t ox, int64_t oy, int64_t oz,
                               const float *map, int interp)
 {
     if (!src || !dst || !map) return "null pointer";
     if (interp != SIFT3D_INTERP_LINEAR && interp != SIFT3D_INTERP_NEAREST) return "interp must be SIFT3D_INTERP_LINEAR or SIFT3D_INTERP_NEAREST";
-    if (nx < 1 || ny < 1 || nz < 1 || nx > (1 << 24) || ny > (1 << 24) || nz > (1 << 24)) return "source extents must be 1 .. 2^24";
-    if (ox < 1 || oy < 1 || oz < 1 || ox >= (1ll << 31) || oy >= (1ll << 31) || oz >= (1ll << 31)) return "output extents must be 1 .. 2^31 - 1";
-    if (ox * oy > (1ll << 40) / oz) return "output larger than 2^40 voxels";
-    return nullptr;
+    const char *why = check_source_extents(nx, ny, nz);
+    return why ? why : check_output_extents(ox, oy, oz);
 }
 
 extern "C" int sift3d_resample_affine(int device, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,

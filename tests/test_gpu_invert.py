@@ -168,6 +168,19 @@ def test_jacobian_kernel_256_cubed(built, io):
     assert (J > 0).all() and J.std() > 0.01
 
 
+@pytest.mark.parametrize("shape", [(11, 19, 37), (8, 16, 40)])
+def test_jacobian_no_field_equals_zero_field(built, shape):
+    """(nz, ny, nx) = 11 x 19 x 37 (rows cut in x: the scalar store) and 8 x 16 x 40 (whole float4 rows): the map without a field
+    has the bytes of the map through a zero field of two nodes per axis that covers part of the output, in both forms.  (The zero
+    field adds +0 to a position, which changes bits only where the position is exactly -0; the oblique map has no such voxel.)"""
+    A = built.resample_map(oblique())
+    zero = {"n": (2, 2, 2), "origin": np.zeros(3, np.float32), "spacing": np.float32(20.0), "disp": np.zeros((3, 2, 2, 2), np.float32)}
+    for form in (0, 1):
+        none = built.jacobian_map(shape, A, None, None, None, form=form)
+        got = built.jacobian_map(shape, A, None, None, zero, form=form)
+        assert got.shape == none.shape and (bits(got) == bits(none)).all(), (form, np.argwhere(bits(got) != bits(none))[:5])
+
+
 # ---- the stage ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("world", [False, True])
 def test_stage_equals_cpu_on_the_scenario(built, io, tmp_path, world):
