@@ -32,6 +32,7 @@ LIB_HIP = os.path.join(CSRC, "_build", "libsift3d_hip.so")
 LIB_HOST = os.path.join(CSRC, "_build", "libsift3d_host.so")
 FEATEXTRACT = os.path.join(CSRC, "_build", "featExtract")
 FEATRESAMPLE = os.path.join(CSRC, "_build", "featResample")
+FEATCOMPOSE = os.path.join(CSRC, "_build", "featCompose")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 6   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -180,6 +181,8 @@ def hip_lib():
     _sig(L.sift3d_invert_nodes, I, I, P, P, P, P, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_invert_field, I, I, P, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_jacobian_map, I, I, I64, I64, I64, P, P, P, P, P, I, P, C.c_char_p, I64)
+    _sig(L.sift3d_compose_nodes, I, I, P, P, P, P, P, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_compose_field, I, I, P, P, P, P, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -240,6 +243,11 @@ def host_lib():
     _sig(L.sift3d_affine_invert_d, I, P, P)
     _sig(L.sift3d_write_matrix, I, C.c_char_p, P)
     _sig(L.sift3d_jacobian_factor, I, P, P, P)
+    _sig(L.sift3d_compose_defaults, None, P)
+    _sig(L.sift3d_compose_matrix, I, P, P, P)
+    _sig(L.sift3d_compose_spacing, F, P, P, P)
+    _sig(L.sift3d_compose_grid, I, I64, I64, I64, P, P, P, P, P)
+    _sig(L.sift3d_compose_residual, I64, P, P, P, I64, P, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -1096,6 +1104,110 @@ def jacobian_map(out_shape, map, out_vox2key=None, src_vox2key=None, field=None,
     _call("sift3d_jacobian_map", int(device), ox, oy, oz, _map12(map).ctypes.data, _ptr(_m16(out_vox2key)), _ptr(_m16(src_vox2key)),
           C.byref(fs) if fs is not None else None, out.ctypes.data, int(form), C.byref(ms))
     return (out, ms.value) if return_ms else out
+
+
+# ---- composition: two alignments chained into one transform and field (featCompose), DESIGN.md section 7i --------------------
+COMPOSE_OUTSIDE1, COMPOSE_OUTSIDE2, COMPOSE_ZEROED = 1, 2, 4   # the bits of a status word of sift3d_compose_nodes
+
+
+class ComposeParams(C.Structure):
+    """sift3d_compose_params"""
+    _fields_ = [("spacing", C.c_float), ("radius", C.c_float), ("margin", C.c_int32), ("max_nodes", C.c_int64)]
+
+
+class ComposeReport(C.Structure):
+    """sift3d_compose_report"""
+    _fields_ = [("nodes", C.c_int64), ("outside1", C.c_int64), ("outside2", C.c_int64), ("zeroed", C.c_int64), ("max_disp", C.c_double),
+                ("folds", C.c_int64), ("residual_cells", C.c_int64), ("rms_residual", C.c_double), ("max_residual", C.c_double),
+                ("kernel_ms", C.c_double * 2)]
+
+
+def compose_params(**kw):
+    """sift3d_compose_defaults, then the given fields (spacing, radius, margin, max_nodes)."""
+    p = ComposeParams()
+    host_lib().sift3d_compose_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(ComposeParams._fields_):
+            raise ValueError("no composition parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def compose_matrix(m1, m2):
+    """sift3d_compose_matrix: M1 M2 in double, rounded to float32 once"""
+    out = np.zeros(16, np.float32)
+    if host_lib().sift3d_compose_matrix(_m16(m1).ctypes.data, _m16(m2).ctypes.data, out.ctypes.data) != 0:
+        raise Sift3DError("sift3d_compose_matrix: a last row is not 0 0 0 1 or an entry is not finite")
+    return out.reshape(4, 4)
+
+
+def _opt_field(field):
+    """(a byref of the sift3d_field of a field dict or None, what keeps it alive)"""
+    if field is None:
+        return None, None
+    fs, keep = _field_struct(field)
+    return C.byref(fs), (fs, keep)
+
+
+def compose_grid(shape, a_vox2key=None, field1=None, field2=None, **params):
+    """sift3d_compose_grid: the composite grid (dict n, origin, spacing) over image A of shape (nz, ny, nx)"""
+    nz, ny, nx = (int(d) for d in shape)
+    f = Field()
+    (f1, _k1), (f2, _k2) = _opt_field(field1), _opt_field(field2)
+    if host_lib().sift3d_compose_grid(nx, ny, nz, _ptr(_m16(a_vox2key)), C.byref(compose_params(**params)), f1, f2, C.byref(f)) != 0:
+        raise Sift3DError("sift3d_compose_grid: bad parameters or too many nodes")
+    return {"n": tuple(int(x) for x in f.n), "origin": np.array(f.origin, np.float32), "spacing": np.float32(f.spacing)}
+
+
+def compose_residual(n, status, res2, margin):
+    """sift3d_compose_residual: (cells, rms, max) of the cell values res2 over the grid of n = (n0, n1, n2) nodes"""
+    nn = (C.c_int64 * 3)(*[int(x) for x in n])
+    st, r2 = np.ascontiguousarray(status, np.uint32), np.ascontiguousarray(res2, np.float64)
+    if st.size != nn[0] * nn[1] * nn[2] or r2.size != (nn[0] - 1) * (nn[1] - 1) * (nn[2] - 1):
+        raise ValueError("status and res2 do not cover the grid")
+    rms, big = C.c_double(0.0), C.c_double(0.0)
+    cells = host_lib().sift3d_compose_residual(nn, st.ctypes.data, r2.ctypes.data, int(margin), C.byref(rms), C.byref(big))
+    return int(cells), rms.value, big.value
+
+
+def compose_nodes(m1, m2, mc, field1, field2, grid, residual=True, device=0, return_ms=False, **params):
+    """sift3d_compose_nodes: field_compose_kernel and (residual=True) compose_residual_kernel alone over grid (dict n, origin,
+    spacing).  m1, m2: 4 x 4; mc: the written composite matrix as read back; field1, field2: field dicts or None.  Returns
+    (w (3, n2, n1, n0) float32, status (n2, n1, n0) uint32, res2 (n2 - 1, n1 - 1, n0 - 1) float64 or None); return_ms=True appends
+    the two kernel times."""
+    n = tuple(int(x) for x in grid["n"])
+    N = max(n[0], 0) * max(n[1], 0) * max(n[2], 0)
+    cn = tuple(max(x - 1, 0) for x in n)
+    NC = cn[0] * cn[1] * cn[2]
+    w, status = np.zeros(3 * max(N, 1), np.float32), np.zeros(max(N, 1), np.uint32)
+    res2 = np.zeros(max(NC, 1), np.float64) if residual else None
+    (f1, _k1), (f2, _k2) = _opt_field(field1), _opt_field(field2)
+    g = _grid_struct(grid)
+    ms = (C.c_double * 2)()
+    _call("sift3d_compose_nodes", int(device), _m16(m1).ctypes.data, _m16(m2).ctypes.data, _m16(mc).ctypes.data, f1, f2,
+          C.byref(compose_params(**params)), C.byref(g), w.ctypes.data, status.ctypes.data, _ptr(res2), ms)
+    out = (w[:3 * N].reshape(3, n[2], n[1], n[0]), status[:N].reshape(n[2], n[1], n[0]),
+           res2[:NC].reshape(cn[2], cn[1], cn[0]) if residual else None)
+    return out + ((ms[0], ms[1]),) if return_ms else out
+
+
+def _compose_report_dict(r):
+    d = {name: getattr(r, name) for name, _ in ComposeReport._fields_ if name != "kernel_ms"}
+    d["kernel_ms"] = (float(r.kernel_ms[0]), float(r.kernel_ms[1]))
+    return d
+
+
+def compose_field(m1, m2, mc, field1, field2, grid, device=0, **params):
+    """sift3d_compose_field: the composite field on grid (from compose_grid) and its report.  Returns (field dict, report dict)."""
+    n = tuple(int(x) for x in grid["n"])
+    disp = np.zeros(3 * max(n[0] * n[1] * n[2], 1), np.float32)
+    out = _grid_struct(grid)
+    out.capacity, out.disp = disp.size, disp.ctypes.data
+    (f1, _k1), (f2, _k2) = _opt_field(field1), _opt_field(field2)
+    rep = ComposeReport()
+    _call("sift3d_compose_field", int(device), _m16(m1).ctypes.data, _m16(m2).ctypes.data, _m16(mc).ctypes.data, f1, f2,
+          C.byref(compose_params(**params)), C.byref(out), C.byref(rep))
+    return _field_dict(out, disp), _compose_report_dict(rep)
 
 
 def _map12(m):

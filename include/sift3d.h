@@ -956,6 +956,84 @@ int sift3d_write_matrix(const char *path, const float m[16]);
 /* det lin(src_vox2key) / det lin(out_vox2key) in double (NULL: identity); 0, or -1 where one of them is 0 or not finite */
 int sift3d_jacobian_factor(const float out_vox2key[16], const float src_vox2key[16], double *factor);
 
+/* ---- composition: two alignments chained into one transform and field (featCompose; beyond the reference) -------------------
+ * DESIGN.md section 7i states the contract; tests/compose_oracle.c restates it.  Pair 1 registers moving B to fixed A: M1 is its
+ * .trans.txt (B key -> A key), v1 an optional field on a grid in A key space with values in B key units, phi1(y) = inv(M1) y +
+ * v1(y), A key -> B key.  Pair 2 registers moving C to fixed B: M2 is C key -> B key, v2 an optional field on a grid in B key space
+ * with values in C key units, phi2(s) = inv(M2) s + v2(s).  The composite Phi = phi2 o phi1, A key -> C key, is the pair of "C
+ * moving, A fixed".  Its matrix is Mc = M1 M2 (sift3d_compose_matrix).  Mc' is Mc as a reader gets it back (sift3d_write_matrix,
+ * sift3d_read_similarity), and the composite field w(y) = Phi(y) - inv(Mc') y lives on a node grid in A key space with values in C
+ * key units, so the %f rounding of the matrix is absorbed by w and (Mc', w) is an ordinary .trans.txt + .field.nii pair.
+ * With P1 = inv(M1), P2 = inv(M2), Pc = inv(Mc') (sift3d_affine_invert_d), per node y (its float position origin + (float)index h,
+ * widened to double), everything in double unless said:
+ *   a_r = ((P1[r][0] y0 + P1[r][1] y1) + P1[r][2] y2) + P1[r][3]
+ *   v1  = field 1 at y: sift3d_field_eval's float arithmetic (g = (y - o) / h, inside where 0 <= g <= n - 1, floor, weights, the
+ *         upper index clamped, x then y then z, each step (1 - w) a + w b); 0 outside its grid and for no field
+ *   s_r = a_r + (double)v1_r
+ *   b_r = ((P2[r][0] s0 + P2[r][1] s1) + P2[r][2] s2) + P2[r][3]
+ *   v2  = field 2 at ((float)s0, (float)s1, (float)s2), same arithmetic; 0 outside and for no field
+ *   t_r = b_r + (double)v2_r
+ *   c_r = ((Pc[r][0] y0 + Pc[r][1] y1) + Pc[r][2] y2) + Pc[r][3]
+ *   w_r = t_r - c_r
+ * The node's value is (float)w.  Its status word: SIFT3D_COMPOSE_OUTSIDE1 where field 1 is given and y is outside its grid,
+ * SIFT3D_COMPOSE_OUTSIDE2 where field 2 is given and s is outside its grid, SIFT3D_COMPOSE_ZEROED where a component of w is not
+ * within +-SIFT3D_FIELD_MAX_DISP (NaN included): the node is then written as 0.  A NaN node of v1 or v2 zeroes exactly the
+ * composite nodes whose gather reads it, weight 0 included.
+ * The interpolation residual, per cell (n - 1 cells per axis): z = origin + ((float)index + 0.5f) h in float, widened; t(z) and
+ * c(z) as above; wt = the composite nodes just written, interpolated at z with the same float arithmetic;
+ * e_r = t_r - (c_r + (double)wt_r); the cell's value is the double (e0 e0 + e1 e1) + e2 e2. */
+#define SIFT3D_COMPOSE_OUTSIDE1 1u
+#define SIFT3D_COMPOSE_OUTSIDE2 2u
+#define SIFT3D_COMPOSE_ZEROED 4u
+
+typedef struct {
+    float spacing;     /* h of the composite grid; 0: field 1's spacing, else field 2's, else 4 key units */
+    float radius;      /* R: the grid reaches R past image A's box: 20 */
+    int32_t margin;    /* cells from the grid's border that the residual's figures leave out; -1: ceil(radius / the grid's spacing) */
+    int64_t max_nodes; /* 2^26: larger grids are refused */
+} sift3d_compose_params;
+void sift3d_compose_defaults(sift3d_compose_params *p);
+
+typedef struct {
+    int64_t nodes;                      /* of the composite grid */
+    int64_t outside1, outside2, zeroed; /* nodes with SIFT3D_COMPOSE_OUTSIDE1, _OUTSIDE2, _ZEROED set */
+    double max_disp;                    /* largest |w| over the nodes */
+    int64_t folds;                      /* sift3d_blockmatch_folds(Mc', w) */
+    int64_t residual_cells;             /* cells the residual's figures cover */
+    double rms_residual, max_residual;  /* of |e| over those cells, summed in index order (sift3d_compose_residual) */
+    double kernel_ms[2];                /* device time of field_compose_kernel and of compose_residual_kernel */
+} sift3d_compose_report;
+
+/* field_compose_kernel, and compose_residual_kernel where res2 is given, alone on the GPU over the grid in `grid` (n, origin,
+ * spacing; its disp is not used): w (3 N floats, component-major) and status (N words) are host arrays; res2 (may be NULL)
+ * receives the (n0 - 1)(n1 - 1)(n2 - 1) cell values, x fastest, and needs 2 nodes per axis.  mc: Mc' as read back.  field1, field2
+ * NULL: v = 0.  kernel_ms (may be NULL): the two device times.  p NULL: defaults; only max_nodes is read.  SIFT3D_ERR_ARG with
+ * text: a singular matrix or a last row other than 0 0 0 1, a grid with an axis outside 1 .. 2^24 (2 .. 2^24 with res2) or more
+ * than max_nodes nodes, a field sift3d_resample_field would refuse. */
+int sift3d_compose_nodes(int device, const float m1[16], const float m2[16], const float mc[16], const sift3d_field *field1,
+                         const sift3d_field *field2, const sift3d_compose_params *p, const sift3d_field *grid, float *w, uint32_t *status,
+                         double *res2, double kernel_ms[2], char *err, int64_t err_len);
+/* The stage: sift3d_compose_nodes with the residual over out's grid (the caller sets out->n, origin and spacing, from
+ * sift3d_compose_grid) into out->disp, and the report.  out->capacity < 3 N or no out->disp: SIFT3D_ERR_CAPACITY, the grid left
+ * filled in.  Zeroed nodes are counted, not an error.  rep may be NULL. */
+int sift3d_compose_field(int device, const float m1[16], const float m2[16], const float mc[16], const sift3d_field *field1,
+                         const sift3d_field *field2, const sift3d_compose_params *p, sift3d_field *out, sift3d_compose_report *rep, char *err,
+                         int64_t err_len);
+/* Host helpers (also in libsift3d_host.so).
+ * Mc = M1 M2: the floats widened to double, each entry ((a0 b0 + a1 b1) + a2 b2), plus a3 in the translation column, the last
+ * row 0 0 0 1, rounded to float once.  0, or -1 for a last row other than 0 0 0 1 or a non-finite entry. */
+int sift3d_compose_matrix(const float m1[16], const float m2[16], float out[16]);
+/* h of the composite grid: p->spacing where it is not 0 (p NULL: 0), else field 1's, else field 2's, else 4 */
+float sift3d_compose_spacing(const sift3d_compose_params *p, const sift3d_field *field1, const sift3d_field *field2);
+/* The composite grid: sift3d_blockmatch_grid's rule (sift3d_compose_spacing, p's radius and max_nodes) over image A's eight corner
+ * voxels.  p NULL: defaults.  Fills n, origin, spacing. */
+int sift3d_compose_grid(int64_t nx, int64_t ny, int64_t nz, const float a_vox2key[16], const sift3d_compose_params *p, const sift3d_field *field1,
+                        const sift3d_field *field2, sift3d_field *f);
+/* The residual's figures from the cell values res2 and the status words of a grid of n nodes: over the cells at least `margin`
+ * cells from the border on every axis (index margin .. n - 2 - margin) none of whose eight corner nodes is SIFT3D_COMPOSE_ZEROED,
+ * in index order: their count (returned), *rms = sqrt(sum / count) and *max = sqrt of the largest value; 0 for no cell. */
+int64_t sift3d_compose_residual(const int64_t n[3], const uint32_t *status, const double *res2, int64_t margin, double *rms, double *max);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
