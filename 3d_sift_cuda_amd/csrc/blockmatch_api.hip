@@ -18,6 +18,14 @@ hipError_t sift3d_launch_block_match(hipStream_t s, const short *qf, const short
 hipError_t sift3d_launch_block_match_ncc(hipStream_t s, const short *qf, const short *qw, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
                                          int64_t stride, const int64_t n[3], int b, int r, int generic, unsigned *out);
 
+/* the search kernel of a cost */
+static hipError_t launch_search(int metric, hipStream_t s, const short *qf, const short *qw, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
+                                int64_t stride, const int64_t n[3], int b, int r, int generic, unsigned *out)
+{
+    const auto launch = metric == SIFT3D_BLOCKMATCH_NCC ? sift3d_launch_block_match_ncc : sift3d_launch_block_match;
+    return launch(s, qf, qw, nx, ny, nz, first, stride, n, b, r, generic, out);
+}
+
 #define BM_MAX_EXTENT ((1ll << 27) - 1)
 #define BM_MAX_NODES (1ll << 27)
 
@@ -73,8 +81,7 @@ static int block_match(int metric, int device, const float *f, const float *w, i
     DEVCHK(dc, dc.to_device(d_v, w, nv));
     DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)wlo, (double)whi, d_qw));
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
-    if (metric == SIFT3D_BLOCKMATCH_NCC) DEVCHK(dc, sift3d_launch_block_match_ncc(dc.s, d_qf, d_qw, nx, ny, nz, first, stride, count, b, r, generic, d_out));
-    else DEVCHK(dc, sift3d_launch_block_match(dc.s, d_qf, d_qw, nx, ny, nz, first, stride, count, b, r, generic, d_out));
+    DEVCHK(dc, launch_search(metric, dc.s, d_qf, d_qw, nx, ny, nz, first, stride, count, b, r, generic, d_out));
     DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
     DEVCHK(dc, dc.download((unsigned *)out, d_out, N * SIFT3D_BLOCKMATCH_WORDS));
     DEVCHK(dc, dc.sync());
@@ -196,8 +203,7 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
             DEVCHK(dc, dc.elapsed_ms(&r.warp_ms));
             DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
             DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, (int64_t)nf, (double)wlo, (double)whi, d_qw));
-            if (ncc) DEVCHK(dc, sift3d_launch_block_match_ncc(dc.s, d_qf, d_qw, fx, fy, fz, first, p.stride, count, p.block, p.search, 0, d_words));
-            else DEVCHK(dc, sift3d_launch_block_match(dc.s, d_qf, d_qw, fx, fy, fz, first, p.stride, count, p.block, p.search, 0, d_words));
+            DEVCHK(dc, launch_search(metric, dc.s, d_qf, d_qw, fx, fy, fz, first, p.stride, count, p.block, p.search, 0, d_words));
             DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
             DEVCHK(dc, dc.download(words.data(), d_words, words.size()));
             DEVCHK(dc, dc.sync());

@@ -104,6 +104,22 @@ def test_kernel_256_cubed(built, bo):
     check(built, bo, F, W, first, 8, count, 4, 3)
 
 
+@pytest.mark.parametrize("b,r", [(6, 6), (1, 6), (2, 5)])
+def test_kernel_widest_search(built, bo, b, r):
+    """29 x 27 x 26 at stride 1 with the widest search the API admits: the key's nibbles reach s + r = 12 and its |s|^2 field 108.
+    At (6, 6) the lattice is 5 x 3 x 2 nodes, run once more from (10, 12, 12) so that some windows leave the volume.  One NaN,
+    +inf and -inf voxel in F and in W, not two: the 25^3 window covers nearly the whole volume, and with two of each the oracle
+    flags every node at (6, 6) for each of the seeds 1 .. 79."""
+    shape = (26, 27, 29)
+    F, W = pair("smooth", shape, 57, spoil=1)
+    first, count = lattice_numpy(shape, 1, b, r)
+    w = check(built, bo, F, W, first, 1, count, b, r, both=True)
+    assert (w[..., 3] == 0).any()
+    if (b, r) == (6, 6):
+        w = check(built, bo, F, W, (10, 12, 12), 1, count, b, r, both=True)
+        assert (w[..., 3] == 0).any() and (w[..., 3] != 0).any()
+
+
 def test_kernel_refusals(built):
     F = volume("smooth", (16, 16, 16), 1)
     for kw in (dict(block=0), dict(block=7), dict(search=0), dict(search=7), dict(stride=0), dict(count=(0, 1, 1))):
