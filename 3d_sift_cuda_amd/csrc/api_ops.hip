@@ -21,6 +21,12 @@
 #include "pipeline.h"
 
 /* ---- device-level building blocks -------------------------------------- */
+/* the knobs of the fused blur as its launch plan (blur_plan.h) reads them */
+static sift3d_blur_tuning blur_tuning(const sift3d_ctx *c)
+{
+    return {c->tune[SIFT3D_TUNE_FUSED_CHUNKS], c->tune[SIFT3D_TUNE_FUSED_ROWS], c->tune[SIFT3D_TUNE_FUSED_TILE], c->tune[SIFT3D_TUNE_FUSED_ORDER], c->tune[SIFT3D_TUNE_FUSED_STAGGER]};
+}
+
 /* out = blur(in); if dog != NULL also dog = in - out.  out may be NULL when only the DoG is wanted.  Uses T[0], T[1].
  * sub (optional): the next octave's level 0, the 2 x 2 x 2 mean of out as a dense (X / 2) x (Y / 2) x (Z / 2) volume; written
  * only where the fused launch can carry it, *sub_done says whether -- the caller launches the subsample itself if not. */
@@ -40,16 +46,10 @@ int blur_dev(sift3d_ctx *c, const float *in, float *out, float *dog, int64_t X, 
     }
     if (n / 2 > SIFT3D_FAST_MAX_R)
         HIPCHK(c, hipMemcpyAsync(c->d_taps, taps, sizeof(float) * n, hipMemcpyHostToDevice, ws));
-    /* One fused launch per level where the volume fills the chip (it marches along z with few, fat workgroups);
-     * coarse octaves keep the three-pass path.  SIFT3D_TUNE_BLUR_FUSED: 0 never / 2 always (tests, A/B timing). */
-    const int fmode = c->tune[SIFT3D_TUNE_BLUR_FUSED];
-    const sift3d_blur_tuning bt = {c->tune[SIFT3D_TUNE_FUSED_CHUNKS], c->tune[SIFT3D_TUNE_FUSED_ROWS], c->tune[SIFT3D_TUNE_FUSED_TILE], c->tune[SIFT3D_TUNE_FUSED_ORDER], c->tune[SIFT3D_TUNE_FUSED_STAGGER]};
-    /* measured standalone (tools/bench_blur_ab.sh 128 / 64): below 2^22 voxels the one launch still beats the three for 7 and
-     * 9 taps (0.020 / 0.026 against 0.042 / 0.043 ms at 128^3), ties at 11-13 and loses at 17 */
-    if (fmode == 2 || (fmode == 1 && (N >= (double)(1 << 22) || (N >= (double)(1 << 18) && n <= 9)))) {
+    if (blur_takes_fused(c->tune[SIFT3D_TUNE_BLUR_FUSED], n, N)) {
         stage_scope sc(c, SIFT3D_STAGE_BLUR_FUSED, (dog && out ? 12.0 : 8.0) * N, n, (int64_t)N, ws);
         int with_sub = 0;
-        hipError_t e = sift3d_launch_blur_fused(ws, in, out, dog, X, Y, Z, taps, n, &bt, 0, -1, c->tune[SIFT3D_TUNE_FUSED_SUB] ? sub : nullptr, &with_sub);
+        hipError_t e = sift3d_launch_blur_fused(ws, in, out, dog, X, Y, Z, taps, n, blur_tuning(c), 0, -1, c->tune[SIFT3D_TUNE_FUSED_SUB] ? sub : nullptr, &with_sub);
         if (e == hipSuccess) {
             if (with_sub) {
                 sc.add_bytes(0.5 * N); /* one float stored per eight voxels */
@@ -123,8 +123,7 @@ int fence_out(sift3d_ctx *c)
 bool blur_window_supported(int64_t X, int64_t Y, float sigma, float min_value)
 {
     float taps[SIFT3D_MAX_TAPS];
-    const int n = sift3d_gauss_taps(sigma, min_value, taps);
-    return n >= 3 && n <= 2 * SIFT3D_FAST_MAX_R + 1 && X % 4 == 0 && X * Y < (1ll << 29);
+    return blur_shape_inside(sift3d_gauss_taps(sigma, min_value, taps), X, Y);
 }
 
 int blur_window_dev(sift3d_ctx *c, const float *in, float *out, float *dog, int64_t X, int64_t Y, int64_t Z, int64_t zo0, int64_t zo1,
@@ -133,10 +132,9 @@ int blur_window_dev(sift3d_ctx *c, const float *in, float *out, float *dog, int6
     float taps[SIFT3D_MAX_TAPS];
     const int n = sift3d_gauss_taps(sigma, min_value, taps);
     if (n < 3 || zo0 < 0 || zo1 > Z || zo1 <= zo0) return set_err(c, SIFT3D_ERR_ARG, "bad blur window [%lld, %lld) of %lld planes", (long long)zo0, (long long)zo1, (long long)Z);
-    const sift3d_blur_tuning bt = {c->tune[SIFT3D_TUNE_FUSED_CHUNKS], c->tune[SIFT3D_TUNE_FUSED_ROWS], c->tune[SIFT3D_TUNE_FUSED_TILE], c->tune[SIFT3D_TUNE_FUSED_ORDER], c->tune[SIFT3D_TUNE_FUSED_STAGGER]};
     const double N = (double)X * Y * (double)(zo1 - zo0);
     stage_scope sc(c, SIFT3D_STAGE_BLUR_FUSED, (dog && out ? 12.0 : 8.0) * N, n, (int64_t)N);
-    hipError_t e = sift3d_launch_blur_fused(c->stream, in, out, dog, X, Y, Z, taps, n, &bt, zo0, zo1);
+    hipError_t e = sift3d_launch_blur_fused(c->stream, in, out, dog, X, Y, Z, taps, n, blur_tuning(c), zo0, zo1);
     if (e == hipErrorNotSupported) {
         sc.cancel();
         return set_err(c, SIFT3D_ERR_ARG, "this shape or filter has no windowed blur (sift3d_blur_window_supported)");

@@ -37,6 +37,8 @@
  * kernel below until round 3; DESIGN.md section 4 keeps its measurements.
  */
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "sift3d_internal.h"
 
@@ -549,139 +551,32 @@ __global__ __launch_bounds__(1024 / BR, (fb_ring_cfg<R, BR, PF, TXv, TYv>::WAVES
     }
 }
 
-/* chunks along z: enough workgroups to fill every CU's resident slots while the 2R lead-in planes stay cheap */
-static int fused_chunks(int R, int64_t Z, long long tiles, int resident, int forced)
-{
-    if (forced >= 1) return forced;
-    /* time ~ rounds of resident workgroups x planes marched per workgroup */
-    const double slots = 256.0 * resident;
-    int best = 1;
-    double best_cost = 0;
-    for (int n = 1; n <= 256; n++) {
-        const int64_t zlen = (Z + n - 1) / n;
-        if (n > 1 && zlen < 4 * R) break;
-        const double wgs = (double)tiles * (double)((Z + zlen - 1) / zlen);
-        const double cost = (wgs <= slots ? 1.0 : wgs / slots) * (double)(zlen + 2 * R);
-        if (n == 1 || cost < best_cost) {
-            best = n;
-            best_cost = cost;
-        }
-    }
-    return best;
-}
+/* ---- the launch: which form runs is blur_plan.h's decision; this is the table of forms and the one way into it ---- */
+static_assert(BLUR_PLAN_MAX_R == SIFT3D_FAST_MAX_R, "the plan and the kernel's tap array cover the same filters");
 
-/* Returns false when the shape is outside the kernel (32-bit buffer offsets: a chunk with its lead-in planes must stay
- * below 4 GiB -- a volume whose planes are that large gets more z chunks, and only a plane pair beyond 4 GiB has none) */
-template <int R, int BR, bool HAS_OUT, bool HAS_DOG, int PF, int TXv = FB_TX, int TYv = 32, bool HAS_SUB = false, bool STG = false>
-static bool launch_ring_t(hipStream_t s, const float *in, float *out, float *dog, int64_t X, int64_t Y, int64_t Z, int64_t zo0, int64_t zo1,
-                          const fb_taps2 &t, int forced_chunks, float *sub = nullptr, int order = 0)
-{
-    using C = fb_ring_cfg<R, BR, PF, TXv, TYv>;
-    static int resident = 0; /* workgroups of this instantiation one CU holds (LDS, registers) */
-    if (resident == 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, blur_fused_ring_kernel<R, BR, HAS_OUT, HAS_DOG, PF, TXv, TYv, HAS_SUB, STG>, C::NT, 0) != hipSuccess || n < 1) n = 1;
-        resident = n;
-    }
-    const int64_t plane_bytes = X * Y * 4;
-    const int64_t max_planes = (int64_t)0xFFFFFFF0ll / plane_bytes - 2 * R - 2; /* planes per chunk the offsets can address */
-    if (max_planes < 1) return false;
-    const int tiles_x = (int)((X + C::TX - 1) / C::TX), tiles_y = (int)((Y + C::TY - 1) / C::TY);
-    const long long tiles = (long long)tiles_x * tiles_y;
-    const int64_t Zo = zo1 - zo0; /* planes to produce */
-    int n = fused_chunks(R, Zo, tiles, resident, forced_chunks);
-    if ((Zo + n - 1) / n > max_planes) n = (int)((Zo + max_planes - 1) / max_planes);
-    int zlen = (int)((Zo + n - 1) / n);
-    if (HAS_SUB && (zlen & 1)) zlen++; /* a pair of planes never straddles two chunks (the window starts at plane 0) */
-    const int nch = (int)((Zo + zlen - 1) / zlen);
-    const long long total = tiles * nch;
-    const long long per = (total + 7) / 8;
-    /* the column-strip order needs counts that divide: 8 | tiles_x, or tiles_x | 8 with the (y, chunk) list of a column cut
-     * evenly over the 8 / tiles_x XCDs that share it; everything else keeps the order of rounds 1 - 4 */
-    if (order == 0) order = 1; /* by measurement: see DESIGN.md section 4 (round 5) */
-    if (order == 3) {
-        const long long M = (long long)tiles_y * nch;
-        const bool ok = tiles_x >= 8 ? tiles_x % 8 == 0 : (8 % tiles_x == 0 && M % (8 / tiles_x) == 0);
-        if (!ok) order = 1;
-    }
-    hipLaunchKernelGGL((blur_fused_ring_kernel<R, BR, HAS_OUT, HAS_DOG, PF, TXv, TYv, HAS_SUB, STG>), dim3((unsigned)(8 * per)), dim3(C::NT), 0, s, in, out, dog, (int)X,
-                       (int)Y, (int)Z, (int)zo0, (int)zo1, zlen, tiles_x, tiles_y, total, order, t, sub);
-    return true;
-}
+typedef void (*fb_kernel_t)(const float *, float *, float *, int, int, int, int, int, int, int, int, long long, int, fb_taps2, float *);
+struct fb_entry {
+    blur_form form;
+    fb_kernel_t kernel;
+    int resident; /* workgroups of this form one CU holds (LDS, registers); 0 = not asked yet */
+};
 
-template <int R, int BR, int PF, int TXv = FB_TX, int TYv = 32, bool STG = false>
-static bool launch_ring_pf(hipStream_t s, const float *in, float *out, float *dog, int64_t X, int64_t Y, int64_t Z, int64_t zo0, int64_t zo1,
-                           const fb_taps2 &t, int chunks, int order)
+/* One entry per form that blur_form_exists: the key and the kernel's template arguments are the same constant f, and a
+ * candidate that no input can pick is never instantiated. */
+template <int I>
+static void fb_add(std::vector<fb_entry> &table)
 {
-    if (out && dog) return launch_ring_t<R, BR, true, true, PF, TXv, TYv, false, STG>(s, in, out, dog, X, Y, Z, zo0, zo1, t, chunks, nullptr, order);
-    if (out) return launch_ring_t<R, BR, true, false, PF, TXv, TYv, false, STG>(s, in, out, dog, X, Y, Z, zo0, zo1, t, chunks, nullptr, order);
-    return launch_ring_t<R, BR, false, true, PF, TXv, TYv, false, STG>(s, in, out, dog, X, Y, Z, zo0, zo1, t, chunks, nullptr, order);
+    constexpr blur_form f = blur_form_candidate(I);
+    if constexpr (blur_form_exists(f))
+        table.push_back({f, blur_fused_ring_kernel<f.R, f.rows, f.has_out, f.has_dog, f.pf, f.tx, f.ty, f.has_sub, f.stg>, 0});
 }
-
-/* The two mappings, by measurement at 512^3 and 256^3: two rows per thread, two planes of window
- * prefetch and one workgroup per CU up to 13 taps; one row per thread (1024 threads, 128 registers) with one plane for 15
- * and 17 taps, and for every filter below 2^22 voxels, where a volume has fewer tiles than the chip has CUs and sixteen
- * wavefronts per workgroup help.  tune->rows_per_thread forces one of the two (tests run both on every shape). */
-template <int R>
-static bool launch_ring(hipStream_t s, const float *in, float *out, float *dog, int64_t X, int64_t Y, int64_t Z, int64_t zo0, int64_t zo1,
-                        const fb_taps2 &t, const sift3d_blur_tuning *tune, float *sub, int *sub_done)
+template <int... I>
+static std::vector<fb_entry> fb_make_table(std::integer_sequence<int, I...>)
 {
-    const int forced = tune ? tune->rows_per_thread : 0;
-    const int br = forced == 1 || forced == 2 ? forced : ((R >= 7 || X * Y * (zo1 - zo0) < (1ll << 22)) ? 1 : 2);
-    const int chunks = tune ? tune->z_chunks : 0;
-    const int order = tune ? tune->order : 0;
-    /* the half-size volume beside the level (HAS_SUB): built for the one filter the pyramid asks it of -- level 3 is 11 taps
-     * in every octave (oracle: sigma_extra[3]) -- with both arrays stored, the whole volume produced and rows that halve into
-     * whole 16-byte vectors; anything else leaves *sub_done 0 and the caller launches the subsample itself */
-    /* the half-step stagger of the second half of the wavefronts with one copy of the march per (half, role) -- the kernel's STG:
-     * tune->stagger 0 = by measurement, 1 = off (the kernel of rounds 2 - 5), 2 = on; built for the two-rows-per-thread mapping
-     * (eight wavefronts, two per SIMD) and the filters the pyramid launches (7 - 13 taps).  By measurement at 512^3
-     * (profiles/r06_stagger_ab.txt; ms per launch off -> on): 11 taps + DoG + half-size volume 0.357 - 0.363 -> 0.346 - 0.354, 13 taps
-     * + DoG 0.365 - 0.373 -> 0.352 - 0.367, 9 taps + DoG equal (0.300 - 0.307 / 0.297 - 0.305), the two level-only launches 2 - 3 %
-     * SLOWER (7 taps 0.201 - 0.203 -> 0.205 - 0.212, 9 taps 0.217 - 0.225 -> 0.220 - 0.228): on from 11 taps up. */
-    const int stg_knob = tune ? tune->stagger : 0;
-    const bool stg = R >= 3 && R <= 6 && (stg_knob == 2 || (stg_knob == 0 && R >= 5));
-    if constexpr (R == 5)
-        if (sub && br == 2 && out && dog && zo0 == 0 && zo1 == Z && X % 8 == 0 && Z >= 2 && Y >= 2) {
-            /* 128 x 16 under the stagger (round 6, profiles/r06_stagger_ab.txt section 8: 0.354 -> 0.340 - 0.344 ms at 512^3; without the
-             * stagger the two tiles measured equal in round 4); SIFT3D_TUNE_FUSED_TILE forces either */
-            const int tile5 = tune ? tune->tile : 0;
-            const bool wide5 = (tile5 == 2 || (tile5 == 0 && stg)) && X >= 128;
-#define FB_SUB(TXv, TYv)                                                                                                         \
-    (stg ? launch_ring_t<5, 2, true, true, 2, TXv, TYv, true, true>(s, in, out, dog, X, Y, Z, zo0, zo1, t, chunks, sub, order)        \
-         : launch_ring_t<5, 2, true, true, 2, TXv, TYv, true, false>(s, in, out, dog, X, Y, Z, zo0, zo1, t, chunks, sub, order))
-            const bool ok = wide5 ? FB_SUB(128, 16) : FB_SUB(FB_TX, 32);
-#undef FB_SUB
-            if (ok && sub_done) *sub_done = 1;
-            return ok;
-        }
-    if (br == 1) return launch_ring_pf<R, 1, 1>(s, in, out, dog, X, Y, Z, zo0, zo1, t, chunks, order);
-    /* tile shape of the two-rows-per-thread mapping: tune->tile 0 = by measurement (below), 1 = 64 x 32, 2 = 128 x 16 */
-    /* by measurement at 512^3 (profiles/r04_tile_ab.txt, dense random data, ms per launch 64 x 32 -> 128 x 16): 7 taps level only
-     * 0.217 -> 0.201 - 0.207, 9 taps level + DoG 0.333 - 0.337 -> 0.318 - 0.323, 7 taps level + DoG 0.329 - 0.331 -> 0.321 - 0.326; no
-     * gain at 11 taps (0.356 - 0.358 both) and a loss where the taller y halo meets more arithmetic or three planes of prefetch:
-     * 13 taps 0.364 - 0.368 -> 0.370 - 0.375, 9 taps level only 0.216 - 0.220 -> 0.225 - 0.234 */
-    const int tile = tune ? tune->tile : 0;
-    const bool both = out && dog;
-    const bool wide = tile == 2 || (tile == 0 && ((R == 3) || (R == 4 && both)));
-#define FB_PF(PFv, TXv, TYv)                                                                                                     \
-    (stg ? launch_ring_pf<R, 2, PFv, TXv, TYv, (R >= 3 && R <= 6)>(s, in, out, dog, X, Y, Z, zo0, zo1, t, chunks, order)           \
-         : launch_ring_pf<R, 2, PFv, TXv, TYv, false>(s, in, out, dog, X, Y, Z, zo0, zo1, t, chunks, order))
-    if constexpr (R <= 6)
-        if (wide && X >= 128) {
-            if constexpr (R <= 4)
-                if (!(out && dog)) return FB_PF(3, 128, 16);
-            return FB_PF(2, 128, 16);
-        }
-    /* three planes of window prefetch where the registers are there and only one array is stored (7 and 9 taps, level
-     * only: 0.213 / 0.224 ms at 512^3 against 0.225 - 0.232 / 0.233 - 0.237 with two; with the DoG store beside it three planes
-     * change nothing: 0.324 / 0.338 against 0.328 / 0.334 - 0.342; four planes, level only: 0.225 / 0.220, no better than three;
-     * round 6, under the stagger, whose role copies leave the registers for it: 11 / 13 taps with three planes 0.351 - 0.354 /
-     * 0.362 - 0.369 against 0.346 - 0.351 / 0.352 - 0.359 with two; ONE plane: 0.43 / 0.44) */
-    if constexpr (R <= 4)
-        if (!(out && dog)) return FB_PF(3, FB_TX, 32);
-    return FB_PF(2, FB_TX, 32);
-#undef FB_PF
+    std::vector<fb_entry> table;
+    const int each[] = {(fb_add<I>(table), 0)...};
+    (void)each;
+    return table;
 }
 
 /* Returns hipErrorNotSupported when the shape is outside this kernel (the caller then runs the three-pass path): rows
@@ -691,29 +586,35 @@ static bool launch_ring(hipStream_t s, const float *in, float *out, float *dog, 
  * is read as far as the filter reaches.  sub (optional): where the 2 x 2 x 2 mean of the produced level goes, a dense
  * (X / 2) x (Y / 2) x (Z / 2) volume; *sub_done says whether this launch wrote it (see HAS_SUB above). */
 hipError_t sift3d_launch_blur_fused(hipStream_t s, const float *in, float *out, float *dog, int64_t X, int64_t Y, int64_t Z,
-                                    const float *taps, int ntaps, const sift3d_blur_tuning *tune, int64_t zo0, int64_t zo1, float *sub,
+                                    const float *taps, int ntaps, const sift3d_blur_tuning &tune, int64_t zo0, int64_t zo1, float *sub,
                                     int *sub_done)
 {
+    static std::vector<fb_entry> table = fb_make_table(std::make_integer_sequence<int, BLUR_FORM_CANDIDATES>{});
     const int R = ntaps / 2;
     if (sub_done) *sub_done = 0;
     if (zo1 < 0) zo1 = Z; /* the default window: the whole volume */
-    if (R < 1 || R > SIFT3D_FAST_MAX_R || ntaps != 2 * R + 1 || X % 4 != 0 || X * Y >= (1ll << 29) || (!out && !dog)) return hipErrorNotSupported;
+    if (!blur_shape_inside(ntaps, X, Y) || (!out && !dog)) return hipErrorNotSupported;
     if (zo0 < 0 || zo1 > Z || zo1 <= zo0) return hipErrorInvalidValue;
     for (int j = 0; j < R; j++)
         if (__builtin_bit_cast(unsigned, taps[j]) != __builtin_bit_cast(unsigned, taps[2 * R - j])) return hipErrorNotSupported;
     fb_taps2 t;
     for (int i = 0; i < 2 * SIFT3D_FAST_MAX_R + 1; i++) t.f[i] = v2f(i < ntaps ? taps[i] : 0.0f);
-    bool ok = false;
-    switch (R) {
-    case 1: ok = launch_ring<1>(s, in, out, dog, X, Y, Z, zo0, zo1, t, tune, sub, sub_done); break;
-    case 2: ok = launch_ring<2>(s, in, out, dog, X, Y, Z, zo0, zo1, t, tune, sub, sub_done); break;
-    case 3: ok = launch_ring<3>(s, in, out, dog, X, Y, Z, zo0, zo1, t, tune, sub, sub_done); break;
-    case 4: ok = launch_ring<4>(s, in, out, dog, X, Y, Z, zo0, zo1, t, tune, sub, sub_done); break;
-    case 5: ok = launch_ring<5>(s, in, out, dog, X, Y, Z, zo0, zo1, t, tune, sub, sub_done); break;
-    case 6: ok = launch_ring<6>(s, in, out, dog, X, Y, Z, zo0, zo1, t, tune, sub, sub_done); break;
-    case 7: ok = launch_ring<7>(s, in, out, dog, X, Y, Z, zo0, zo1, t, tune, sub, sub_done); break;
-    default: ok = launch_ring<8>(s, in, out, dog, X, Y, Z, zo0, zo1, t, tune, sub, sub_done); break;
+
+    const blur_form f = blur_choose_form(R, out != nullptr, dog != nullptr, X, Y, Z, zo0, zo1, sub != nullptr, tune);
+    fb_entry *e = nullptr;
+    for (fb_entry &c : table)
+        if (c.form == f) e = &c;
+    if (!e) return hipErrorInvalidDeviceFunction; /* a form the plan picks and the table lacks: an error, never the three-pass path */
+    const int threads = 1024 / f.rows;
+    if (e->resident == 0) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, e->kernel, threads, 0) != hipSuccess || n < 1) n = 1;
+        e->resident = n;
     }
-    if (!ok) return hipErrorNotSupported;
+    blur_chunking c;
+    if (!blur_plan_chunks(f, X, Y, zo0, zo1, e->resident, tune, &c)) return hipErrorNotSupported;
+    hipLaunchKernelGGL(e->kernel, dim3((unsigned)(8 * ((c.total + 7) / 8))), dim3(threads), 0, s, in, out, dog, (int)X, (int)Y, (int)Z, (int)zo0,
+                       (int)zo1, c.zlen, c.tiles_x, c.tiles_y, c.total, c.order, t, f.has_sub ? sub : nullptr);
+    if (f.has_sub && sub_done) *sub_done = 1;
     return hipGetLastError();
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blur_plan.h"
 #include "sift3d.h"
 #include "sift3d_dev.h" /* the self-test and, in DEV builds, the development hooks: declared apart from the boundary */
 
@@ -65,17 +66,10 @@ hipError_t sift3d_launch_blur_y(hipStream_t s, const float *in, float *out, int6
 /* prev/dog may be NULL (no DoG epilogue) */
 hipError_t sift3d_launch_blur_z(hipStream_t s, const float *in, float *out, const float *prev, float *dog, int64_t X,
                                 int64_t Y, int64_t Z, const float *taps, int ntaps, const float *d_taps);
-/* all three passes and the DoG in one kernel; hipErrorNotSupported when the shape is outside it.  tune (may be NULL):
- * what sift3d_set_tuning forces -- 0 = the launcher's own choice */
-struct sift3d_blur_tuning {
-    int z_chunks;        /* SIFT3D_TUNE_FUSED_CHUNKS */
-    int rows_per_thread; /* SIFT3D_TUNE_FUSED_ROWS: 2 = 512 threads, two planes of prefetch; 1 = 1024 threads, one plane */
-    int tile;            /* SIFT3D_TUNE_FUSED_TILE: 1 = 64 x 32, 2 = 128 x 16 (two-rows-per-thread mapping, up to 13 taps) */
-    int order;           /* SIFT3D_TUNE_FUSED_ORDER: which workgroup takes which tile (0 = by measurement, 1 .. 3: see the kernel) */
-    int stagger;         /* SIFT3D_TUNE_FUSED_STAGGER: the second half of a workgroup's wavefronts half a step behind the first (0 = by measurement, 1 = off, 2 = on) */
-};
+/* all three passes and the DoG in one kernel; hipErrorNotSupported when the shape is outside it.  tune: what
+ * sift3d_set_tuning forces (blur_plan.h, which decides the form of the kernel that runs) */
 hipError_t sift3d_launch_blur_fused(hipStream_t s, const float *in, float *out, float *dog, int64_t X, int64_t Y, int64_t Z,
-                                    const float *taps, int ntaps, const sift3d_blur_tuning *tune, int64_t zo0 = 0, int64_t zo1 = -1,
+                                    const float *taps, int ntaps, const sift3d_blur_tuning &tune, int64_t zo0 = 0, int64_t zo1 = -1,
                                     float *sub = nullptr, int *sub_done = nullptr);
 hipError_t sift3d_launch_dog(hipStream_t s, const float *a, const float *b, float *out, int64_t n);
 hipError_t sift3d_launch_subsample(hipStream_t s, const float *in, int64_t X, int64_t Xl, int64_t Y, int64_t Z, float *out,

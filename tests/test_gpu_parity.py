@@ -26,7 +26,7 @@ def vol_of(built, dims, seed):
 
 SHAPES = [(17, 13, 11), (32, 32, 32), (64, 48, 40), (33, 21, 19), (130, 6, 9), (5, 70, 7), (256, 8, 8), (300, 20, 12)]
 SIGMAS = [0.5, 0.95, 1.2262736558914185, 1.5198684930801392, 1.5450079441070557, 1.9465880393981934,
-          2.452547311782837, 3.0900158882141113]
+          2.452547311782837, 3.0900158882141113, 2.75]   # 3, 5, 7, 9, 9, 11, 13, 17 and (appended: the indices are used) 15 taps
 
 
 @pytest.mark.parametrize("dims", SHAPES)
