@@ -1037,7 +1037,11 @@ static void o3_trace_near_ties(const float *g, const o3_feature *ft, int primary
 /* R/src_common/MultiScale.cpp:2722-3037 determineCanonicalOrientation3D.
  * ori_out receives up to max_ori 3x3 matrices (rows P1, P2, P3); the feature's
  * patch is zeroed as a side effect, as there (:2883). */
-int o3_canonical_orientations(o3_feature *ft, float *ori_out, int max_ori)
+static int canonical_orientations(o3_feature *ft, float *ori_out, int max_ori, int32_t *diag);
+int o3_canonical_orientations(o3_feature *ft, float *ori_out, int max_ori) { return canonical_orientations(ft, ori_out, max_ori, 0); }
+
+/* diag (optional): the O3_DIAG_WORDS words of o3_describe_level for this keypoint; words [1], [2], [4] and [5] are filled here */
+static int canonical_orientations(o3_feature *ft, float *ori_out, int max_ori, int32_t *diag)
 {
     float dx[PV], dy[PV], dz[PV];
     float t0[PV], t2[PV];
@@ -1071,6 +1075,10 @@ int o3_canonical_orientations(o3_feature *ft, float *ori_out, int max_ori)
     int npk = patch_peaks(t2, pk);
     if (o3_trace_peaks()) o3_trace_near_ties(t2, ft, -1);
     o3_sort_high_low(pk, npk);
+    if (diag) {
+        diag[1] = npk;
+        diag[2] = npk > 1 && memcmp(&pk[0].value, &pk[1].value, sizeof(float)) == 0;
+    }
 
     for (int i = 0; i < npk && i < PD && i < max_ori; i++) {
         float *oc = &ori_data[i * 3];
@@ -1086,7 +1094,9 @@ int o3_canonical_orientations(o3_feature *ft, float *ori_out, int max_ori)
             fprintf(stderr, "o3 peak-trace: kp (%.3f, %.3f, %.3f) primary %d: value %.9g / max %.9g = %.9f -> %s\n", ft->x, ft->y,
                     ft->z, i, pk[i].value, pk[0].value, (double)pk[i].value / (double)pk[0].value,
                     pk[i].value < 0.8 * pk[0].value ? "rejected" : "kept");
+        if (diag) diag[5] += (pk[i].value < 0.8f * pk[0].value) != (pk[i].value < 0.8 * pk[0].value);
         if (pk[i].value < 0.8 * pk[0].value) break;
+        if (diag) diag[4]++;
         float p1[3], p2[3], p3[3];
         p1[0] = ori_data[i * 3]; p1[1] = ori_data[i * 3 + 1]; p1[2] = ori_data[i * 3 + 2];
         memset(t0, 0, sizeof(t0));
@@ -1292,10 +1302,12 @@ static void fv_push(featvec *fv, const o3_feature *f)
 }
 
 /* R/src_common/MultiScale.cpp:1705-1862 generateFeature3D.  Returns 1 if the
- * keypoint survived (bounds + eigen test), else 0. */
-static int generate_feature(o3_feature *ft, const float *img, int64_t X, int64_t Y, int64_t Z, featvec *fv, float eig_thres)
+ * keypoint survived (bounds + eigen test), else 0.  diag (optional, O3_DIAG_WORDS ints): what became of it. */
+static int generate_feature(o3_feature *ft, const float *img, int64_t X, int64_t Y, int64_t Z, featvec *fv, float eig_thres,
+                            int32_t *diag)
 {
     float patch[PV];
+    if (diag) memset(diag, 0, sizeof(int32_t) * O3_DIAG_WORDS);
     memset(ft->ori, 0, sizeof(ft->ori));
     ft->ori[0][0] = 1; ft->ori[1][1] = 1; ft->ori[2][2] = 1;
     if (o3_sample_patch(ft, img, X, Y, Z, patch) != 0) return 0;
@@ -1307,13 +1319,18 @@ static int generate_feature(o3_feature *ft, const float *img, int64_t X, int64_t
     float esp = es * es * es;
     if (esp < eig_thres * ep || eig_thres < 0) {
     } else {
+        if (diag) diag[0] = 1;
         return 0;
     }
     ft->info &= ~O3_INFO_REORIENT;
     fv_push(fv, ft);
 
     float oris[30 * 9];
-    int nori = o3_canonical_orientations(ft, oris, 30);
+    int nori = canonical_orientations(ft, oris, 30, diag);
+    if (diag) {
+        diag[0] = 2;
+        diag[3] = nori;
+    }
     for (int io = 0; io < nori; io++) {
         const float *o = oris + 9 * io;
         for (int i = 0; i < 3; i++)
@@ -1330,7 +1347,7 @@ static int generate_feature(o3_feature *ft, const float *img, int64_t X, int64_t
 static int64_t generate_features(o3_feature *ft, const o3_extremum *mins, const float *minH, const float *minL, int64_t nmin,
                                  const o3_extremum *maxs, const float *maxH, const float *maxL, int64_t nmax,
                                  const float *C, float sH, float sC, float sL, const float *img, int64_t X, int64_t Y,
-                                 int64_t Z, featvec *fv, float eig_thres)
+                                 int64_t Z, featvec *fv, float eig_thres, int32_t *diag)
 {
     int64_t kept = 0;
 #ifdef _OPENMP
@@ -1357,7 +1374,7 @@ static int64_t generate_features(o3_feature *ft, const o3_extremum *mins, const 
                 f->x += 0.5f; f->y += 0.5f; f->z += 0.5f;
                 if (pass == 0) f->info &= ~O3_INFO_MIN0MAX1;
                 else f->info |= O3_INFO_MIN0MAX1;
-                kept += generate_feature(f, img, X, Y, Z, &lv[q], eig_thres);
+                kept += generate_feature(f, img, X, Y, Z, &lv[q], eig_thres, diag ? diag + O3_DIAG_WORDS * q : 0);
             }
             free(f);
         }
@@ -1393,7 +1410,7 @@ static int64_t generate_features(o3_feature *ft, const o3_extremum *mins, const 
             ft->x += 0.5f; ft->y += 0.5f; ft->z += 0.5f;
             if (pass == 0) ft->info &= ~O3_INFO_MIN0MAX1;
             else ft->info |= O3_INFO_MIN0MAX1;
-            kept += generate_feature(ft, img, X, Y, Z, fv, eig_thres);
+            kept += generate_feature(ft, img, X, Y, Z, fv, eig_thres, diag ? diag + O3_DIAG_WORDS * (pass * nmin + i) : 0);
         }
     }
     return kept;
@@ -1424,6 +1441,19 @@ static void cand_push(pyr_sink *s, int oct, int lvl, int is_max, const o3_extrem
     c->octave = oct; c->level = lvl; c->is_max = is_max;
     c->x = e->x; c->y = e->y; c->z = e->z;
     c->value = e->value; c->h_value = h; c->l_value = l;
+}
+
+/* octave -> image space, MultiScale.cpp:531-543 */
+static void to_image_space(featvec *fv, int64_t first, float fac)
+{
+    const float add = 0;
+    for (int64_t i = first; i < fv->n; i++) {
+        o3_feature *f = &fv->v[i];
+        f->scale *= fac;
+        f->x = f->x * fac + add;
+        f->y = f->y * fac + add;
+        f->z = f->z * fac + add;
+    }
 }
 
 static int run_pyramid(const float *vol, int64_t X, int64_t Y, int64_t Z, float init_scale, float eig_thres, pyr_sink *sink,
@@ -1507,7 +1537,7 @@ static int run_pyramid(const float *vol, int64_t X, int64_t Y, int64_t Z, float 
                         t0 = now_s();
                         sink->st.n_keypoints +=
                             generate_features(ft, mins, minH, minL, nmin, maxs, maxH, maxL, nmax, D[j - 2], sig[j - 3],
-                                              sig[j - 2], sig[j - 1], L[j - 2], X, Y, Z, sink->fv, eig_thres);
+                                              sig[j - 2], sig[j - 1], L[j - 2], X, Y, Z, sink->fv, eig_thres, 0);
                         sink->st.t_features += now_s() - t0;
                     }
                 }
@@ -1527,17 +1557,7 @@ static int run_pyramid(const float *vol, int64_t X, int64_t Y, int64_t Z, float 
             sigma *= factor;
             sig[j] = sigma;
         }
-        /* octave -> image space, MultiScale.cpp:531-543 */
-        if (sink->fv) {
-            float fac = fscale, add = 0;
-            for (int64_t i = first; i < sink->fv->n; i++) {
-                o3_feature *f = &sink->fv->v[i];
-                f->scale *= fac;
-                f->x = f->x * fac + add;
-                f->y = f->y * fac + add;
-                f->z = f->z * fac + add;
-            }
-        }
+        if (sink->fv) to_image_space(sink->fv, first, fscale);
         fscale *= 2.0f;
         X /= 2; Y /= 2; Z /= 2;
         memcpy(L[0], half, sizeof(float) * (size_t)(X * Y * Z));
@@ -1592,16 +1612,9 @@ int o3_octave_levels(const float *g0, int64_t X, int64_t Y, int64_t Z, float *G,
     return 1;
 }
 
-/* featExtract.cpp:474-505 descriptor loop + size factor */
-int o3_extract(const float *vol, int64_t X, int64_t Y, int64_t Z, float init_scale, int desc_mode, float eig_thres,
-               float size_factor, o3_record **out, int64_t *n_out, o3_stats *stats)
+/* featExtract.cpp:474-505 descriptor loop + size factor: fs[0..n) -> r[0..n) */
+static void describe_features(o3_feature *fs, int64_t n, int desc_mode, float size_factor, o3_record *r)
 {
-    o3_feature *fs = 0;
-    int64_t n = 0;
-    o3_stats st;
-    o3_pyramid_features(vol, X, Y, Z, init_scale, eig_thres, &fs, &n, &st);
-    o3_record *r = (o3_record *)malloc(sizeof(o3_record) * (size_t)(n ? n : 1));
-    double t0 = now_s();
 #ifdef _OPENMP
 #pragma omp parallel for schedule(dynamic, 64)
 #endif
@@ -1618,11 +1631,58 @@ int o3_extract(const float *vol, int64_t X, int64_t Y, int64_t Z, float init_sca
         r[i].info = f->info;
         memcpy(r[i].desc, f->pc, sizeof(float) * O3_DESC_LEN);
     }
+}
+
+int o3_extract(const float *vol, int64_t X, int64_t Y, int64_t Z, float init_scale, int desc_mode, float eig_thres,
+               float size_factor, o3_record **out, int64_t *n_out, o3_stats *stats)
+{
+    o3_feature *fs = 0;
+    int64_t n = 0;
+    o3_stats st;
+    o3_pyramid_features(vol, X, Y, Z, init_scale, eig_thres, &fs, &n, &st);
+    o3_record *r = (o3_record *)malloc(sizeof(o3_record) * (size_t)(n ? n : 1));
+    double t0 = now_s();
+    describe_features(fs, n, desc_mode, size_factor, r);
     st.t_desc = now_s() - t0;
     free(fs);
     *out = r;
     *n_out = n;
     if (stats) *stats = st;
+    return 1;
+}
+
+/* The per-keypoint stage of ONE level on caller-given buffers: what run_pyramid does with a level's validated extrema
+ * (generate_features, then octave -> image space) followed by o3_extract's descriptor loop.  cand: the level's extrema in the
+ * reference's order -- minima, then maxima, raster order within each (octave / level of the entries are not read).  Returns 1,
+ * or 0 when the list is not in that order. */
+int o3_describe_level(const float *img, const float *dogc, int64_t X, int64_t Y, int64_t Z, float sigma_h, float sigma_c,
+                      float sigma_l, float octave_factor, const o3_candidate *cand, int64_t n_cand, float eig_thres,
+                      int desc_mode, float size_factor, o3_record **out, int64_t *n_out, int32_t *diag)
+{
+    int64_t nmin = 0;
+    while (nmin < n_cand && !cand[nmin].is_max) nmin++;
+    for (int64_t i = nmin; i < n_cand; i++)
+        if (!cand[i].is_max) return 0;
+    o3_extremum *e = (o3_extremum *)malloc(sizeof(o3_extremum) * (size_t)(n_cand ? n_cand : 1));
+    float *h = (float *)malloc(sizeof(float) * (size_t)(2 * n_cand + 1)), *l = h + n_cand;
+    for (int64_t i = 0; i < n_cand; i++) {
+        e[i].x = cand[i].x; e[i].y = cand[i].y; e[i].z = cand[i].z; e[i].value = cand[i].value;
+        h[i] = cand[i].h_value;
+        l[i] = cand[i].l_value;
+    }
+    o3_feature *ft = (o3_feature *)calloc(1, sizeof(o3_feature));
+    featvec fv = {0, 0, 0};
+    generate_features(ft, e, h, l, nmin, e + nmin, h + nmin, l + nmin, n_cand - nmin, dogc, sigma_h, sigma_c, sigma_l, img, X, Y, Z,
+                      &fv, eig_thres, diag);
+    to_image_space(&fv, 0, octave_factor);
+    o3_record *r = (o3_record *)malloc(sizeof(o3_record) * (size_t)(fv.n ? fv.n : 1));
+    describe_features(fv.v, fv.n, desc_mode, size_factor, r);
+    free(fv.v);
+    free(ft);
+    free(h);
+    free(e);
+    *out = r;
+    *n_out = fv.n;
     return 1;
 }
 

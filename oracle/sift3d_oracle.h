@@ -152,6 +152,17 @@ typedef struct {
 } o3_candidate;
 int o3_pyramid_candidates(const float *vol, int64_t X, int64_t Y, int64_t Z, float initial_image_scale,
                           o3_candidate **out, int64_t *n_out);
+/* The stage-level twin of the product's sift3d_describe_dev for one level: the per-keypoint stage (generateFeatures3D_efficient,
+ * octave -> image space, descriptor loop, size factor) on caller-given buffers -- the level's Gaussian image and its DoG, both
+ * dense X*Y*Z -- and a caller-given list of validated extrema in the reference's order: minima, then maxima, raster order within
+ * each.  Returns malloc'ed records in *out (o3_free).  diag (optional): O3_DIAG_WORDS ints per candidate --
+ * [0] 0 = rejected by the bounds test, 1 = by the eigen test, 2 = kept; [1] primary orientation-histogram peaks found;
+ * [2] 1 when the two strongest of them hold the same bits; [3] frames returned (records of the keypoint - 1); [4] primaries
+ * that passed the 0.8 threshold; [5] primaries for which that threshold, taken in float instead of double, decides otherwise. */
+#define O3_DIAG_WORDS 6
+int o3_describe_level(const float *img, const float *dogc, int64_t X, int64_t Y, int64_t Z, float sigma_h, float sigma_c,
+                      float sigma_l, float octave_factor, const o3_candidate *cand, int64_t n_cand, float eig_thres,
+                      int desc_mode, float size_factor, o3_record **out, int64_t *n_out, int32_t *diag);
 /* one octave's Gaussians/DoGs for tests: G has 6 levels, D has 5 levels, each X*Y*Z */
 int o3_octave_levels(const float *g0, int64_t X, int64_t Y, int64_t Z, float *G, float *D);
 void o3_free(void *p);

@@ -76,6 +76,7 @@ class Oracle:
         sig("o3_pyramid_features", I, P, I64, I64, I64, F, F, P, P, P)
         sig("o3_pyramid_candidates", I, P, I64, I64, I64, F, P, P)
         sig("o3_octave_levels", I, P, I64, I64, I64, P, P)
+        sig("o3_describe_level", I, P, P, I64, I64, I64, F, F, F, F, P, I64, F, I, F, P, P, P)
         sig("o3_free", None, P)
         sig("o3_write_key", I, C.c_char_p, P, I64, F, I, P)
         sig("o3_knn64", I, P, I64, P, I64, I, P, P)
@@ -169,6 +170,22 @@ class Oracle:
         G = np.empty((6, nz, ny, nx), np.float32); D = np.empty((5, nz, ny, nx), np.float32)
         self.L.o3_octave_levels(g0.ctypes.data, nx, ny, nz, G.ctypes.data, D.ctypes.data)
         return G, D
+
+    def describe_level(self, img, dogc, sigmas, cand, octave_factor=1.0, eig_thres=140.0, desc_mode=0, size_factor=1.0, diag=False):
+        """o3_describe_level: the per-keypoint stage of one level on given buffers.  cand: CAND array, minima then maxima, raster
+        order within each.  Returns the records, and with diag=True also (len(cand), 6) int32: fate (0 bounds, 1 eigen test,
+        2 kept), primary peaks, top two primaries bit-equal, frames, primaries past the 0.8 threshold, primaries a float threshold
+        would decide otherwise."""
+        img, dogc = self._f(img), self._f(dogc); nz, ny, nx = dogc.shape
+        assert img.shape == dogc.shape
+        cand = np.ascontiguousarray(cand, CAND)
+        dg = np.zeros((len(cand), 6), np.int32)
+        out, n = C.c_void_p(), C.c_int64(0)
+        assert self.L.o3_describe_level(img.ctypes.data, dogc.ctypes.data, nx, ny, nz, float(sigmas[0]), float(sigmas[1]), float(sigmas[2]),
+                                        float(octave_factor), cand.ctypes.data, len(cand), float(eig_thres), int(desc_mode),
+                                        float(size_factor), C.byref(out), C.byref(n), dg.ctypes.data if diag else None) == 1
+        recs = self._take(out, n.value, REC)
+        return (recs, dg) if diag else recs
 
     def knn64(self, db, queries, k):
         """Brute-force nearest neighbours: (idx, dist2), each (n_q, k), ascending by (distance, index)."""
