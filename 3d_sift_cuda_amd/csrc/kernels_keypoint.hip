@@ -18,6 +18,7 @@
 #include <cstddef>
 #include <type_traits>
 
+#include "desc_bins.h"
 #include "sift3d_internal.h"
 
 #define PD SIFT3D_PATCH_DIM
@@ -27,21 +28,8 @@
 /* scalar helpers (each mirrors one reference routine)                     */
 /* ---------------------------------------------------------------------- */
 
-/* _fioDetermineInterpCoord, R/src_common/FeatureIO.cpp:757-782 */
-__device__ __forceinline__ void interp_coord(float fX, float fMin, float fMax, int &ix, float &w)
-{
-    if (fX < fMin + 0.5f) {
-        ix = (int)fMin;
-        w = 1.0f;
-    } else if (fX >= fMax - 0.5f) {
-        ix = (int)(fMax - 2);
-        w = 0.0f;
-    } else {
-        float mh = fX - 0.5f;
-        ix = (int)floorf(mh);
-        w = 1.0f - (mh - ((float)ix));
-    }
-}
+/* interp_coord (_fioDetermineInterpCoord, R/src_common/FeatureIO.cpp:757-782) is desc_bins.h's: the descriptor's weights are
+ * built from it at compile time */
 
 /* fioGetPixelTrilinearInterp, R/src_common/FeatureIO.cpp:812-850 */
 /* (x,y,z) are coordinates in the whole octave volume (Z = its slice count); img holds Zl slices
@@ -1057,11 +1045,14 @@ __constant__ unsigned char c_brief_y[192] = {
     3,5,4,2,3,6,4,5,6,3,3,5,1,3,1,6,7,4,1,4,3,5,2,4,2,1,2,5,4,5,2,3,3,3,3,4,2,6,3,4,3,3,3,6,1,2,5,4,2,4,1,4,6,7,3,6,2,4,3,6,5,6,4,0,
     6,6,5,1,4,7,2,1,5,3,4,2,2,7,3,3,6,4,2,4,1,9,7,7,5,2,7,1,7,5,5,1,5,4,1,3,3,4,0,5,1,6,3,5,3,2,3,3,7,2,5,1,1,0,4,1,3,1,0,3,1,6,5,9};
 
-struct kpB_sift { /* SIFT-rank: per interior voxel gradient magnitude + orientation octant, bucketed by octant */
-    float mag[NINT + 3];
-    unsigned short order[NINT + 3]; /* interior voxels sorted by (octant, raster); packed x | y<<4 | z<<8 */
-    unsigned char bin[NINT + 3];
-    int start[9];
+struct kpB_sift { /* SIFT-rank: per interior voxel gradient magnitude + orientation octant, laid out by desc_bins_entry */
+    float mag[DESC_BINS_LEN];
+    unsigned char bin[DESC_BINS_LEN + 1];
+    /* Not used.  It keeps a record's LDS where the octant lists had it, so that 15 workgroups share a CU and not the 17 the two
+     * arrays above would admit: with 17 waiting for the sampling tokens the sampling phase is 0.14 ms slower at 512^3 and the
+     * whole step 0.23 ms (docs/experiments.md section 13) */
+    int hold[379];
+    int all; /* a magnitude of +Inf: the chains take all 729 voxels (desc_bins.h) */
 };
 struct kpB_brief { /* BRIEF family: blur output (the middle pass goes back into the patch) */
     float t1[PV + 1];
@@ -1075,8 +1066,11 @@ struct kpB_smem {
     } u;
     float sc[16];
     float taps[8];
-    float wtab[2][PD + 1];
 };
+
+static_assert(sizeof(kpB_smem<true>) > 160 * 1024 / 16 && sizeof(kpB_smem<true>) <= 160 * 1024 / 15 && sizeof(kpB_smem<false>) > 160 * 1024 / 16 &&
+                  sizeof(kpB_smem<false>) <= 160 * 1024 / 15,
+              "15 records per CU by LDS (160 KB)");
 
 template <bool SIFT>
 __global__ __launch_bounds__(DESC_NT) void descriptor_kernel(sift3d_kp_params p, const sift3d_dkp *__restrict__ kps,
@@ -1089,6 +1083,9 @@ __global__ __launch_bounds__(DESC_NT) void descriptor_kernel(sift3d_kp_params p,
     if (r >= nrec) return;
     const int lane = threadIdx.x;
     if (lane < 5) sm.taps[lane] = taps5.f[lane];
+    if constexpr (SIFT) {
+        if (lane == 5) sm.u.v.all = 0; /* raised by the gradient pre-pass, behind the barriers of the normalisation */
+    }
     const sift3d_dkp *kp = kps + rec_kp[r];
     const int fr = rec_frame[r]; /* -1: the un-reoriented record */
     float ori[9];
@@ -1099,7 +1096,7 @@ __global__ __launch_bounds__(DESC_NT) void descriptor_kernel(sift3d_kp_params p,
     }
     const sift3d_level lv = p.levels[kp->lvl];
 #ifdef SIFT3D_DEV /* timing ablation (tools/desc_ablate.py): every record samples one cache-resident region */
-    if (p.debug_stop >= 21 && p.debug_stop <= 26) { /* development aid: every record samples one cache-resident region (22: and runs to the end, 23/24/25: stops where 12/13/14 do, 26: after the bin chains) */
+    if (p.debug_stop >= 21 && p.debug_stop <= 26) { /* development aid: every record samples one cache-resident region (22: and runs to the end, 23/24: stops where 12/13 do, 26: after the bin chains) */
         wave_sample_patch<DESC_NT>(sm.patch, lv.img, lv.X, lv.XP, lv.Y, lv.Z, lv.Zl, lv.z_off, 20.0f, 20.0f, 20.0f, 3.0f, ori);
         if (p.debug_stop == 21) return;
     } else
@@ -1174,80 +1171,19 @@ __global__ __launch_bounds__(DESC_NT) void descriptor_kernel(sift3d_kp_params p,
                     }
                 }
             }
-            sm.u.v.mag[q] = mg;
-            sm.u.v.bin[q] = (unsigned char)best;
-        }
-        if (lane < PD) {
-            /* spatial coordinate of patch index c in the 2-bin grid (MultiScale.cpp:641-671), then the
-             * trilinear weight of bin 0 (wtab[0]) and bin 1 (wtab[1]) along that axis */
-            const float binsz = PD / (float)2;
-            const int c = lane;
-            float v = (int)(c / binsz) + 0.5f;
-            if ((int)((c + 0) / binsz) != (int)((c + 1) / binsz)) {
-                float p0 = ((c + 0) / binsz);
-                float p1 = ((c + 1) / binsz);
-                v = (p0 + p1) / 2.0f;
-            }
-            float w;
-            int i0;
-            interp_coord(v, 0, 2.0f, i0, w);
-            sm.wtab[0][c] = w;
-            sm.wtab[1][c] = 1.0f - w;
+            const int en = desc_bins_entry(x, y, z);
+            sm.u.v.mag[en] = mg;
+            sm.u.v.bin[en] = (unsigned char)best;
+            if (desc_bins_needs_all(mg)) sm.u.v.all = 1;
         }
         __syncthreads();
 #ifdef SIFT3D_DEV
         if (p.debug_stop == 13 || p.debug_stop == 24) return;
 #endif
-        /* bucket the interior voxels by octant, keeping raster order inside a bucket (wavefront 0, ballots) */
         if (w0) {
-            int cnt[8];
-#pragma unroll
-            for (int o = 0; o < 8; o++) cnt[o] = 0;
-            for (int base = 0; base < NINT; base += 64) {
-                const int q = base + lane;
-                const int b = q < NINT ? sm.u.v.bin[q] : 8;
-#pragma unroll
-                for (int o = 0; o < 8; o++) cnt[o] += __popcll(__ballot(b == o));
-            }
-            int run[8];
-            int acc0 = 0;
-#pragma unroll
-            for (int o = 0; o < 8; o++) {
-                run[o] = acc0;
-                if (lane == 0) sm.u.v.start[o] = acc0;
-                acc0 += cnt[o];
-            }
-            if (lane == 0) sm.u.v.start[8] = acc0;
-            for (int base = 0; base < NINT; base += 64) {
-                const int q = base + lane;
-                const int b = q < NINT ? sm.u.v.bin[q] : 8;
-#pragma unroll
-                for (int o = 0; o < 8; o++) {
-                    const unsigned long long m = __ballot(b == o);
-                    if (b == o) {
-                        const int x = q % 9 + 1, y = (q / 9) % 9 + 1, z = q / 81 + 1;
-                        sm.u.v.order[run[o] + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)(x | (y << 4) | (z << 8));
-                    }
-                    run[o] += __popcll(m);
-                }
-            }
-        }
-        __syncthreads();
-#ifdef SIFT3D_DEV
-        if (p.debug_stop == 14 || p.debug_stop == 25) return;
-#endif
-        if (w0) {
-            /* lane = ((z*2+y)*2+x)*8 + orientation: one sequential chain per bin over its octant's voxels */
-            const int o = lane & 7, bx = (lane >> 3) & 1, by = (lane >> 4) & 1, bz = (lane >> 5) & 1;
-            const float *wxs = sm.wtab[bx], *wys = sm.wtab[by], *wzs = sm.wtab[bz];
-            const int k0 = sm.u.v.start[o], k1 = sm.u.v.start[o + 1];
-            float acc = 0;
-            for (int kk = k0; kk < k1; kk++) {
-                const unsigned v = sm.u.v.order[kk];
-                const int x = v & 15, y = (v >> 4) & 15, z = v >> 8;
-                const float mg = sm.u.v.mag[((z - 1) * 9 + (y - 1)) * 9 + (x - 1)];
-                acc += mg * wxs[x] * wys[y] * wzs[z];
-            }
+            /* lane = ((z*2+y)*2+x)*8 + orientation: one sequential chain per bin, over the 5^3 box on which the bin's weights are
+             * not zero (desc_bins.h says why that is the reference's sum over the whole octant, bit for bit) */
+            const float acc = sm.u.v.all ? desc_bins_walk_all(sm.u.v.mag, sm.u.v.bin, lane) : desc_bins_walk(sm.u.v.mag, sm.u.v.bin, lane);
 #ifdef SIFT3D_DEV
             if (p.debug_stop == 26) return;
 #endif

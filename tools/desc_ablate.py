@@ -12,7 +12,7 @@ n = int(os.environ.get("ABL_N", "256"))
 ctx = pkg.Context(n, n, n)
 ctx.set_volume(pkg.synth_blobs(n, n, n))
 ctx.set_tuning(pkg.TUNE_KP_CHUNKS, 1)
-for stop in [int(v) for v in os.environ.get("ABL_STOPS", "21,11,12,13,14,0").split(",")]:
+for stop in [int(v) for v in os.environ.get("ABL_STOPS", "21,11,12,13,0").split(",")]:
     L.sift3d_dev_set_stop(ctx.handle, stop)
     ctx.extract(); ctx.enable_timing(1); ctx.extract()
     log = ctx.launch_log(); sel = log[log["stage"] == 6]
