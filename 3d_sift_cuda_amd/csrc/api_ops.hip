@@ -5,7 +5,8 @@
  * change): api_context.hip (contexts, buffers, tuning, stream), api_timing.hip (event pairs, the launch log), api_ops.hip
  * (the blur dispatcher, the operator-level entry points, the candidate lists), api_pipeline.hip (volume upload, the
  * per-keypoint stage, run_pipeline, sift3d_extract / sift3d_detect), api_slab.hip (the building blocks a Z-slab driver calls).
- * What they share is pipeline.h.  R/ = /root/reference/3dsift_cleanup-softVote_App_Weight_SoftMax/
+ * What they share is pipeline.h.  The kernels behind the blur dispatcher are in kernels_volume.hip and kernels_blur_fused.hip
+ * (launch plan: blur_plan.h), those behind the candidate lists in kernels_extrema.hip (launch plan: extrema_plan.h).  R/ = /root/reference/3dsift_cleanup-softVote_App_Weight_SoftMax/
  */
 #include <algorithm>
 #include <chrono>
@@ -319,7 +320,6 @@ int cand_reset(sift3d_ctx *c, hipStream_t on)
     if (!on) on = c->stream;
     c->jobs.clear();
     c->cand_split_at = 0;
-    c->cand_group = 0;
     HIPCHK(c, hipMemsetAsync(c->d_count, 0, sizeof(unsigned long long) * 8, on));
     /* every extrema pass of the run gets its own counter set: one memset here instead of one per pass */
     HIPCHK(c, hipMemsetAsync(c->surv_counts, 0, sizeof(unsigned long long) * SIFT3D_SURV_COUNTERS * SIFT3D_SURV_SETS, on));
@@ -330,19 +330,18 @@ int cand_reset(sift3d_ctx *c, hipStream_t on)
     return SIFT3D_OK;
 }
 
-/* where the extrema launches queued now append: the whole list, or the part of it the current group owns (split tail) */
-int cand_append(sift3d_ctx *c, const level_job &j, bool record)
+int cand_append(sift3d_ctx *c, const level_job &j, const cand_where &w, bool record)
 {
     c->count_queued = false;
     if (record) c->jobs.push_back(j);
-    hipStream_t st = c->cand_stream ? c->cand_stream : c->stream;
+    hipStream_t st = w.stream ? w.stream : c->stream;
     stage_scope sc(c, SIFT3D_STAGE_EXTREMA, 4.0 * (double)j.X * j.Y * j.Z, 0, j.X * j.Y * j.Z, st);
     /* own-level extrema are ~0.3 % of the voxels on blob fields (7 % on white noise): the list of a level is
      * sized at 1/surv_div of its voxels; an overflow is flagged on the device and handled in cand_finalize */
     int64_t cover = j.X * j.Y * j.Z / c->surv_div + 64 * 1024; /* split evenly over 64 segments */
     if (cover > c->surv_cap) cover = c->surv_cap;
     sift3d_survivor *surv = c->surv;
-    if (c->surv_sel > 0) { /* a pass on the second extrema stream: that stream's own list, grown on demand */
+    if (w.list > 0) { /* a pass on the second extrema stream: that stream's own list, grown on demand */
         if (c->surv2_cap < cover) {
             HIPCHK(c, hipStreamSynchronize(st));
             hipFree(c->surv2);
@@ -364,7 +363,7 @@ int cand_append(sift3d_ctx *c, const level_job &j, bool record)
         lz.next_g = j.next_g;
         if (j.next_g) {
             /* the second list holds a subset of the own-level list: the same capacity always suffices */
-            const int li = c->surv_sel > 0 ? 1 : 0;
+            const int li = w.list > 0 ? 1 : 0;
             if (c->list2_cap[li] < cover) {
                 HIPCHK(c, hipStreamSynchronize(st)); /* an earlier pass may still be reading the list */
                 hipFree(c->list2[li]);
@@ -381,23 +380,31 @@ int cand_append(sift3d_ctx *c, const level_job &j, bool record)
             if (!fresh) HIPCHK(c, hipMemsetAsync(lz.list2_count, 0, sizeof(unsigned long long) * SIFT3D_LIST2_COUNTERS, st));
         }
     }
-    const cand_target tg = cand_target_of(c);
-    HIPCHK(c, sift3d_launch_extrema(st, j.dp, j.dc, j.dn, j.X, j.Xl ? j.Xl : j.X, j.Y, j.Z, j.z_lo, j.z_hi, j.lvl_id, tg.keys,
-                                    tg.vals, tg.count, tg.cap, surv, counters, c->d_count + 2, cover, !fresh,
-                                    lazy ? &lz : nullptr, c->strict_extrema));
+    HIPCHK(c, sift3d_launch_extrema(st, {j.dp, j.dc, j.dn, j.X, j.Xl ? j.Xl : j.X, j.Y, j.Z, j.z_lo, j.z_hi, j.lvl_id, cand_target_of(c, w.group),
+                                         surv, counters, c->d_count + 2, cover, !fresh, lazy ? &lz : nullptr, c->strict_extrema}));
+    return SIFT3D_OK;
+}
+
+int cand_append_octave_small(sift3d_ctx *c, const level_job jobs[3], const float *const D[5], int64_t XP, int64_t X, int64_t Y, int64_t Z,
+                             const cand_where &w)
+{
+    hipStream_t st = w.stream ? w.stream : c->stream;
+    stage_scope sc(c, SIFT3D_STAGE_EXTREMA, 12.0 * (double)XP * Y * Z, 0, XP * Y * Z, st);
+    HIPCHK(c, sift3d_launch_extrema_octave_small(st, D, XP, X, Y, Z, jobs[0].lvl_id, cand_target_of(c, w.group)));
+    c->count_queued = false;
+    for (int l = 0; l < 3; l++) c->jobs.push_back(jobs[l]);
     return SIFT3D_OK;
 }
 
 int cand_replay(sift3d_ctx *c)
 {
     c->cand_split_at = 0; /* a replay fills one list, whatever the first attempt did */
-    c->cand_group = 0;
     HIPCHK(c, hipMemsetAsync(c->d_count, 0, sizeof(unsigned long long) * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->surv_counts, 0, sizeof(unsigned long long) * SIFT3D_SURV_COUNTERS * SIFT3D_SURV_SETS, c->stream));
     HIPCHK(c, hipMemsetAsync(c->list2_counts, 0, sizeof(unsigned long long) * SIFT3D_LIST2_COUNTERS * SIFT3D_SURV_SETS, c->stream));
     c->surv_set = 0;
     for (const level_job &j : c->jobs) {
-        int rc = cand_append(c, j, false);
+        int rc = cand_append(c, j, cand_where(), false);
         if (rc) return rc;
     }
     return SIFT3D_OK;
@@ -480,7 +487,7 @@ extern "C" int sift3d_extrema(sift3d_ctx *c, const float *d_prev, const float *d
     c->strict_extrema = sift3d_volume_needs_strict(d_cur, nx * ny * nz);
     int64_t cnt = 0;
     rc = cand_reset(c);
-    if (!rc) rc = cand_append(c, {c->D[0], c->D[1], d_next ? c->D[2] : nullptr, nx, ny, nz, 0, (int)nz, 0}, true);
+    if (!rc) rc = cand_append(c, {c->D[0], c->D[1], d_next ? c->D[2] : nullptr, nx, ny, nz, 0, (int)nz, 0}, cand_where(), true);
     if (!rc) rc = cand_finalize(c, &cnt);
     if (rc) return rc;
     std::vector<unsigned long long> keys((size_t)cnt);

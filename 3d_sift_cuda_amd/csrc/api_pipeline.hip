@@ -842,30 +842,18 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
             HIPCHK(c, hipStreamWaitEvent(exs, ev, 0));
             if (which == 1) used_second = true;
         }
-        c->cand_stream = exs;
-        c->cand_group = o >= 2 ? 1 : 0; /* only looked at while the list is split */
-        c->surv_sel = (exs != c->stream && which == 1) ? 1 : 0;
+        const cand_where where = {exs, (exs != c->stream && which == 1) ? 1 : 0, o >= 2 ? 1 : 0};
         const float *L[5], *D[5];
         octave_buffers(d, L, D);
         if (ru.lazy) D[0] = D[4] = nullptr;
         if (ru.tiny_done) D[4] = ru.d4tiny;
         level_job jobs[3];
         octave_jobs(jobs, L, D, d.XP, d.X, d.Y, d.Z, 0, (int)d.Z, (int)o * 3, next_taps, next_ntaps);
-        int rc_ = SIFT3D_OK;
         /* an octave one workgroup built whole (at most 4 096 voxels, every DoG level stored): its three detection levels in one
          * launch; the per-level jobs are recorded all the same, for a replay after a list overflow */
-        if (ru.tiny_done) {
-            stage_scope sc(c, SIFT3D_STAGE_EXTREMA, 12.0 * (double)d.XP * d.Y * d.Z, 0, d.XP * d.Y * d.Z, exs);
-            const cand_target tg = cand_target_of(c);
-            HIPCHK(c, sift3d_launch_extrema_octave_small(exs, D, d.XP, d.X, d.Y, d.Z, (int)o * 3, tg.keys, tg.vals, tg.count, tg.cap));
-            c->count_queued = false;
-            for (const level_job &jb : jobs) c->jobs.push_back(jb);
-        } else {
-            for (int l = 0; l < 3 && !rc_; l++) rc_ = cand_append(c, jobs[l], true);
-        }
-        c->cand_stream = nullptr;
-        c->cand_group = 0;
-        c->surv_sel = 0;
+        if (ru.tiny_done) return cand_append_octave_small(c, jobs, D, d.XP, d.X, d.Y, d.Z, where);
+        int rc_ = SIFT3D_OK;
+        for (int l = 0; l < 3 && !rc_; l++) rc_ = cand_append(c, jobs[l], where, true);
         return rc_;
     };
     for (size_t o = 0; o < oct.size(); o++) {

@@ -40,7 +40,7 @@ extern "C" int sift3d_extrema_append_dev(sift3d_ctx *c, const float *d_prev, con
     HIPCHK(c, hipSetDevice(c->device));
     int rc = fence_in(c);
     if (rc) return rc;
-    rc = cand_append(c, {d_prev, d_cur, d_next, nx, ny, nz_local, (int)z_lo, (int)z_hi, level_id}, true);
+    rc = cand_append(c, {d_prev, d_cur, d_next, nx, ny, nz_local, (int)z_lo, (int)z_hi, level_id}, cand_where(), true);
     if (rc) return rc;
     return fence_out(c); /* the caller may reuse the buffers once the pass has read them */
 }
@@ -73,7 +73,7 @@ extern "C" int sift3d_extrema_append_lazy_dev(sift3d_ctx *c, const float *d_prev
         for (int q = 0; q < ntaps; q++) jb.next_taps[q] = taps[q];
         jb.next_g = g_next;
     }
-    rc = cand_append(c, jb, true);
+    rc = cand_append(c, jb, cand_where(), true);
     if (rc) return rc;
     return fence_out(c);
 }

@@ -72,13 +72,6 @@ static inline octave_sigmas sigma_schedule(float initial_image_scale)
     return s;
 }
 
-/* shapes (row pitch, rows, slices held) the extrema passes can take D_0 and D_4 in unstored form for (level_job's prev_b /
- * next_g); the pitch is always a multiple of 4 on one device, a slab's rows are its logical rows */
-static inline bool lazy_shape_ok(int64_t nx, int64_t ny, int64_t nz_local)
-{
-    return nx % 4 == 0 && nx >= 8 && ny >= 3 && nz_local >= 3 && nx * ny < (1ll << 29);
-}
-
 /* The three detection levels of an octave as extrema jobs.  L and D: the octave's Gaussian levels 0..4 and DoG levels 0..4
  * as the buffers hold them (pitch XP, logical row length Xl, 0: XP; Zl slices, of which [z_lo, z_hi) are detected; first_id:
  * the level id of the first).  A null D[0] is not stored: the level below D_1 is L_0 - L_1.  A null D[4] is not stored either:
@@ -121,13 +114,11 @@ struct sift3d_ctx {
     int device;
     hipStream_t stream;
     hipStream_t ex_stream;     /* extrema detection of an octave, overlapped with the blurs of the coarser octaves */
-    hipStream_t cand_stream;   /* where cand_append launches: stream, or ex_stream inside run_pipeline */
     hipStream_t ex_stream2;    /* extrema of the octaves after the first */
     hipEvent_t ev_ex2[2];      /* levels of such an octave complete / its extrema launches complete */
     hipEvent_t ev_reset;       /* the counters of the extrema passes have been cleared (on ex_stream) */
     sift3d_survivor *surv2;    /* own-level list of that stream (the passes of one stream share a list, one after the other) */
     int64_t surv2_cap;
-    int surv_sel;              /* which list cand_append uses: 0 = surv, 1 = surv2 */
     hipStream_t kp_stream;     /* descriptor launches of the chunked per-keypoint stage, beside the keypoint kernel of the next chunk */
     hipEvent_t ev_kpc[SIFT3D_KP_MAX_CHUNKS]; /* chunk i's keypoint kernel, scan and record map are complete */
     hipEvent_t ev_desc;        /* the descriptor launches on kp_stream are complete */
@@ -155,10 +146,9 @@ struct sift3d_ctx {
                                   * mark, [3] keypoints, [4] validated extrema of the second group (split tail) */
     int64_t cand_split_at;       /* 0: one list in keys_a / vals_a; n > 0: entries [0, n) take the first group's extrema (counter [0]), [n, cand_cap)
                                   * the second group's (counter [4]) -- run_pipeline's split tail */
-    int cand_group;              /* the group cand_append's launches append to */
     sift3d_survivor *surv;
     sift3d_survivor2 *list2[2];      /* extrema that passed the level below, waiting for the lazily evaluated level above: one list
-                                      * per extrema stream (surv_sel) */
+                                      * per extrema stream (cand_where::list) */
     int64_t list2_cap[2];
     unsigned long long *list2_counts; /* one length word per extrema pass (SIFT3D_SURV_SETS), zeroed with surv_counts */
     unsigned long long *surv_counts; /* segment counters of the own-level list: SIFT3D_SURV_SETS sets */
@@ -268,7 +258,17 @@ int blur_window_dev(sift3d_ctx *c, const float *in, float *out, float *dog, int6
                     float min_value);
 /* the candidate lists of a run: reset, one detection level appended, the count requested, awaited (+ sort) */
 int cand_reset(sift3d_ctx *c, hipStream_t on = nullptr);
-int cand_append(sift3d_ctx *c, const level_job &j, bool record);
+/* where an extrema pass runs and appends.  The default: the main stream, the first own-level list, the whole candidate list. */
+struct cand_where {
+    hipStream_t stream = nullptr; /* NULL: the context's main stream */
+    int list = 0;                 /* own-level list and second list: 0 = surv / list2[0], 1 = surv2 / list2[1] (one pair per extrema stream) */
+    int group = 0;                /* only looked at while the candidate list is split (cand_split_at): 0 = its first part, 1 = its second */
+};
+int cand_append(sift3d_ctx *c, const level_job &j, const cand_where &w, bool record);
+/* the three detection levels of an octave of at most SIFT3D_TINY_VOX voxels (all five DoG levels D stored; rows of pitch XP, X
+ * of them logical) in one launch; jobs: the same three levels as cand_append would take them, recorded for a replay */
+int cand_append_octave_small(sift3d_ctx *c, const level_job jobs[3], const float *const D[5], int64_t XP, int64_t X, int64_t Y, int64_t Z,
+                             const cand_where &w);
 int cand_count_queue(sift3d_ctx *c);
 int cand_finalize(sift3d_ctx *c, int64_t *count_out);
 /* the per-keypoint stage in three phases, so that a driver with several contexts can queue it on all of them before it
@@ -345,17 +345,11 @@ struct stage_scope {
     }
 };
 
-/* where the extrema passes of the current group append (the whole list, or its first / second part: SIFT3D_TUNE_SPLIT_TAIL) */
-struct cand_target {
-    unsigned long long *keys;
-    sift3d_cval *vals;
-    unsigned long long *count;
-    int64_t cap;
-};
-static inline cand_target cand_target_of(const sift3d_ctx *c)
+/* where the extrema passes of a group append (the whole list, or its first / second part: SIFT3D_TUNE_SPLIT_TAIL) */
+static inline cand_target cand_target_of(const sift3d_ctx *c, int group)
 {
     if (c->cand_split_at <= 0) return {c->keys_a, c->vals_a, c->d_count, c->cand_cap};
-    if (c->cand_group == 0) return {c->keys_a, c->vals_a, c->d_count, c->cand_split_at};
+    if (group == 0) return {c->keys_a, c->vals_a, c->d_count, c->cand_split_at};
     return {c->keys_a + c->cand_split_at, c->vals_a + c->cand_split_at, c->d_count + 4, c->cand_cap - c->cand_split_at};
 }
 

@@ -1,6 +1,6 @@
 /*
- * sift3d_internal.h -- declarations shared by the HIP translation units of
- * libsift3d_hip.so (kernel launchers and the context).  Not installed.
+ * sift3d_internal.h -- declarations shared by the HIP translation units of libsift3d_hip.so (kernel launchers and the
+ * context).  Not installed.  The launch decisions of the fused blur and of the extrema passes: blur_plan.h, extrema_plan.h.
  */
 #ifndef SIFT3D_INTERNAL_H
 #define SIFT3D_INTERNAL_H
@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "blur_plan.h"
+#include "extrema_plan.h"
 #include "sift3d.h"
 #include "sift3d_dev.h" /* the self-test and, in DEV builds, the development hooks: declared apart from the boundary */
 
@@ -20,6 +21,23 @@
 struct sift3d_taps {
     float f[2 * SIFT3D_FAST_MAX_R + 1];
 };
+
+/* a row taken as 16-byte vectors (VEC = 4) or element by element (VEC = 1): the whole-volume kernels */
+typedef float v4f __attribute__((ext_vector_type(4)));
+template <int VEC>
+struct vecT;
+template <> struct vecT<4> { typedef v4f type; };
+template <> struct vecT<1> { typedef float type; };
+template <int VEC>
+__device__ __forceinline__ typename vecT<VEC>::type vload(const float *p)
+{
+    return *reinterpret_cast<const typename vecT<VEC>::type *>(p);
+}
+template <int VEC>
+__device__ __forceinline__ void vstore(float *p, typename vecT<VEC>::type v)
+{
+    *reinterpret_cast<typename vecT<VEC>::type *>(p) = v;
+}
 
 /* Candidates are kept as (key, value) pairs so that one device radix sort puts them in the
  * reference's order: key = level id << 40 | is_max << 39 | linear voxel index, with
@@ -58,7 +76,7 @@ struct sift3d_level {
     int pad;
 };
 
-/* ---- kernel launchers (kernels_volume.hip) ---- */
+/* ---- kernel launchers (kernels_volume.hip; the fused blur: kernels_blur_fused.hip) ---- */
 hipError_t sift3d_launch_blur_x(hipStream_t s, const float *in, float *out, int64_t X, int64_t Y, int64_t Z,
                                 const float *taps, int ntaps, const float *d_taps);
 hipError_t sift3d_launch_blur_y(hipStream_t s, const float *in, float *out, int64_t X, int64_t Y, int64_t Z,
@@ -92,26 +110,44 @@ hipError_t sift3d_launch_tiny_octave(hipStream_t s, const float *L0, const sift3
                                      int64_t Z, const sift3d_octave_taps &t);
 hipError_t sift3d_launch_double_size(hipStream_t s, const float *in, int64_t X, int64_t Y, int64_t Z, float *out);
 hipError_t sift3d_launch_halve_size(hipStream_t s, const float *in, int64_t X, int64_t Y, int64_t Z, float *out);
-/* X: row pitch, Xl: logical row length (Xl == X for a dense volume) */
+/* ---- extrema passes (kernels_extrema.hip; every launch decision: extrema_plan.h) ---- */
 /* Neighbour levels that are not stored as DoG volumes (NULL or all-zero: both neighbours are the stored dprev / dnext).
  * prev_b: the level below is dprev - prev_b, two Gaussian levels.  next_g: the level above is next_g - blur(next_g, taps),
  * and blur(next_g) is evaluated only at the 27 voxels around each extremum that passed everything else (dnext is ignored;
- * ntaps <= 2 * SIFT3D_FAST_MAX_R + 1, rows of whole 16-byte vectors). */
+ * the shapes and filters this takes: lazy_shape_ok and extrema_lazy_status, extrema_plan.h). */
 struct sift3d_extrema_lazy {
     const float *prev_b;
     const float *next_g;
     float taps[2 * SIFT3D_FAST_MAX_R + 1];
     int ntaps;
-    sift3d_survivor2 *list2;         /* 64 segments of list2_cap / 64 entries, one per slab of z, like the own-level list */
+    sift3d_survivor2 *list2;         /* EX_SEGS segments of list2_cap / EX_SEGS entries, one per slab of z, like the own-level list */
     unsigned long long *list2_count; /* SIFT3D_LIST2_COUNTERS words, zeroed by the caller */
     int64_t list2_cap;               /* at least surv_cap of the same call */
 };
-hipError_t sift3d_launch_extrema(hipStream_t s, const float *dprev, const float *dcur, const float *dnext, int64_t X,
-                                 int64_t Xl, int64_t Y, int64_t Z, int z_lo, int z_hi, int lvl_id, unsigned long long *keys,
-                                 sift3d_cval *vals, unsigned long long *count, int64_t cap, sift3d_survivor *surv,
-                                 unsigned long long *surv_count /* SIFT3D_SURV_COUNTERS words */,
-                                 unsigned long long *surv_overflow, int64_t surv_cap, bool zero_counters,
-                                 const sift3d_extrema_lazy *lazy = nullptr, bool strict = false);
+static_assert(EX_LAZY_NTAPS == 2 * SIFT3D_FAST_MAX_R + 1, "the third phase is built for the widest filter of the templated kernels");
+/* where validated extrema are appended: (key, value) pairs, their count on the device, the room there is */
+struct cand_target {
+    unsigned long long *keys;
+    sift3d_cval *vals;
+    unsigned long long *count; /* on the device */
+    int64_t cap;
+};
+/* one extrema pass: a detection level, where its extrema go, and the own-level list between the first and the second phase */
+struct sift3d_extrema_pass {
+    const float *dprev, *dcur, *dnext; /* dnext may be NULL: no level above */
+    int64_t X, Xl, Y, Z;               /* X: row pitch, Xl: logical row length (Xl == X for a dense volume) */
+    int z_lo, z_hi, lvl_id;            /* planes searched: the interior ones of [z_lo, z_hi) */
+    cand_target out;
+    sift3d_survivor *surv;             /* NULL: no list, every voxel takes all three tests in one launch */
+    unsigned long long *surv_count;    /* SIFT3D_SURV_COUNTERS words */
+    unsigned long long *surv_overflow; /* raised to the length a list cut short would have needed */
+    int64_t surv_cap;
+    bool zero_counters;                /* clear surv_count first (the pipeline hands every level its own, already zeroed, set instead) */
+    const sift3d_extrema_lazy *lazy;   /* or NULL */
+    bool strict;                       /* the first phase compares element by element (sift3d_volume_needs_strict) */
+};
+/* hipErrorNotSupported / hipErrorInvalidValue: what the plan refuses, with nothing queued */
+hipError_t sift3d_launch_extrema(hipStream_t s, const sift3d_extrema_pass &p);
 /* Volumes the max / min form of the first extrema pass would get wrong: a NaN anywhere (v_max_f32 / v_min_f32 return the
  * other operand, so "c > max of 26" would hold beside a NaN neighbour where the reference's element-wise "every neighbour < c"
  * fails), an infinity, or a magnitude above FLT_MAX / 4 (the blur, DoG and subsample can overflow it to an infinity, and
@@ -120,11 +156,10 @@ hipError_t sift3d_launch_scan_strict(hipStream_t s, const float *v, int64_t n, u
 bool sift3d_volume_needs_strict(const float *v, int64_t n); /* the same test on host memory */
 /* the three detection levels of an octave of at most SIFT3D_TINY_VOX voxels (d[0..4]: its five stored DoG levels) in one launch */
 hipError_t sift3d_launch_extrema_octave_small(hipStream_t s, const float *const d[5], int64_t X, int64_t Xl, int64_t Y, int64_t Z,
-                                              int lvl_id0, unsigned long long *keys, sift3d_cval *vals, unsigned long long *count,
-                                              int64_t cap);
+                                              int lvl_id0, const cand_target &out);
 #define SIFT3D_SURV_SETS 96 /* one counter set per extrema pass of a pipeline run, zeroed together */
-#define SIFT3D_SURV_COUNTERS (64 * 32)
-#define SIFT3D_LIST2_COUNTERS 64
+#define SIFT3D_SURV_COUNTERS (EX_SEGS * EX_SEG_STRIDE)
+#define SIFT3D_LIST2_COUNTERS EX_SEGS
 
 /* ---- per-keypoint stage (kernels_keypoint.hip) ---- */
 struct sift3d_kp_params {

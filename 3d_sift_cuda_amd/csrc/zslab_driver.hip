@@ -717,19 +717,14 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
             ZR_HIP(hipSetDevice(q.dev));
             ZR_HIP(hipEventRecord(q.c->ev_oct[0], q.c->stream));
             ZR_HIP(hipStreamWaitEvent(q.c->ex_stream, q.c->ev_oct[0], 0));
-            q.c->cand_stream = q.c->ex_stream;
             /* (lazy: D_0 and D_4 are NULL, the jobs take L_0 - L_1 and L_4 - blur(L_4) for them) */
             level_job jobs[3];
             octave_jobs(jobs, q.L, q.D, X, 0, Y, q.e1 - q.e0, (int)(q.z0 - q.e0), (int)(q.z1 - q.e0), o * 3, taps5, ntaps5);
             for (int l = 0; l < 3; l++) {
-                const int rc_ = cand_append(q.c, jobs[l], true);
-                if (rc_ != SIFT3D_OK) {
-                    q.c->cand_stream = nullptr;
-                    ZR_FAIL(rc_, "rank %d: %s", r, sift3d_last_error(q.c));
-                }
+                const int rc_ = cand_append(q.c, jobs[l], {q.c->ex_stream}, true);
+                if (rc_ != SIFT3D_OK) ZR_FAIL(rc_, "rank %d: %s", r, sift3d_last_error(q.c));
             }
             octave_level_rows(&q.levels[(size_t)o * 3], q.L, q.D, X, X, Y, zo, q.e1 - q.e0, q.e0, sigmas, fscale);
-            q.c->cand_stream = nullptr;
             if (q.lo || q.hi) ZR_HIP(hipStreamWaitEvent(q.c->stream, q.ev_patch, 0)); /* before the subsample reads L3 beyond +- 8: the first deferred step only */
             if (more && sharded && o + 1 < K) {
                 int64_t n0, n1;
@@ -973,7 +968,6 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
         hipSetDevice(q.dev);
         hipStreamSynchronize(q.c->stream);
         hipStreamSynchronize(q.c->ex_stream);
-        q.c->cand_stream = nullptr;
         hipStreamSynchronize(q.copy_stream);
         hipStreamSynchronize(q.halo_stream);
     }
