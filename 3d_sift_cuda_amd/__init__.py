@@ -33,6 +33,7 @@ LIB_HOST = os.path.join(CSRC, "_build", "libsift3d_host.so")
 FEATEXTRACT = os.path.join(CSRC, "_build", "featExtract")
 FEATRESAMPLE = os.path.join(CSRC, "_build", "featResample")
 FEATCOMPOSE = os.path.join(CSRC, "_build", "featCompose")
+FEATFUSE = os.path.join(CSRC, "_build", "featFuse")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 6   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -183,6 +184,9 @@ def hip_lib():
     _sig(L.sift3d_jacobian_map, I, I, I64, I64, I64, P, P, P, P, P, I, P, C.c_char_p, I64)
     _sig(L.sift3d_compose_nodes, I, I, P, P, P, P, P, P, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_compose_field, I, I, P, P, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_fuse_weights, I, I, P, P, I64, I64, I64, C.c_int32, C.c_int32, P, C.c_int32, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_fuse_vote, I, I, C.c_int32, P, P, I64, C.c_int32, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_fuse_labels, I, I, P, I64, I64, I64, P, C.c_int32, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -248,6 +252,10 @@ def host_lib():
     _sig(L.sift3d_compose_spacing, F, P, P, P)
     _sig(L.sift3d_compose_grid, I, I64, I64, I64, P, P, P, P, P)
     _sig(L.sift3d_compose_residual, I64, P, P, P, I64, P, P)
+    _sig(L.sift3d_fuse_defaults, None, P)
+    _sig(L.sift3d_fuse_similarity, C.c_uint32, C.c_int32, I64, I64, I64, I64, I64, I64)
+    _sig(L.sift3d_fuse_check_labels, I64, P, I64)
+    _sig(L.sift3d_label_overlap, I64, P, P, I64, P, P, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -1208,6 +1216,128 @@ def compose_field(m1, m2, mc, field1, field2, grid, device=0, **params):
     _call("sift3d_compose_field", int(device), _m16(m1).ctypes.data, _m16(m2).ctypes.data, _m16(mc).ctypes.data, f1, f2,
           C.byref(compose_params(**params)), C.byref(out), C.byref(rep))
     return _field_dict(out, disp), _compose_report_dict(rep)
+
+
+# ---- multi-atlas label fusion by locally weighted voting (featFuse), DESIGN.md section 7j ----------------------------------
+FUSE_MAX_ATLASES, FUSE_U_ONE, FUSE_FALLBACK, FUSE_NONE = 32, 32768, 0x40000000, 0x80000000
+
+
+class FuseParams(C.Structure):
+    """sift3d_fuse_params"""
+    _fields_ = [("block", C.c_int32), ("metric", C.c_int32), ("power", C.c_int32), ("fill", C.c_float), ("max_voxels", C.c_int64)]
+
+
+class FuseAtlas(C.Structure):
+    """sift3d_fuse_atlas"""
+    _fields_ = [("image", C.c_void_p), ("labels", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("vox2key", C.c_void_p),
+                ("moving_to_fixed", C.c_void_p), ("field", C.c_void_p)]
+
+
+class FuseAtlasReport(C.Structure):
+    """sift3d_fuse_atlas_report"""
+    _fields_ = [("voters", C.c_int64), ("support", C.c_int64), ("mean_u", C.c_double), ("empty_range", C.c_int32), ("reserved", C.c_int32),
+                ("warp_ms", C.c_double), ("weight_ms", C.c_double)]
+
+
+class FuseReport(C.Structure):
+    """sift3d_fuse_report"""
+    _fields_ = [("none", C.c_int64), ("fallback", C.c_int64), ("lo", C.c_float), ("hi", C.c_float), ("vote_ms", C.c_double),
+                ("atlas", FuseAtlasReport * FUSE_MAX_ATLASES)]
+
+
+def fuse_params(**kw):
+    """sift3d_fuse_defaults, then the given fields (block, metric ("ssd", "ncc" or a number), power, fill, max_voxels)."""
+    p = FuseParams()
+    host_lib().sift3d_fuse_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(FuseParams._fields_):
+            raise ValueError("no fusion parameter %s" % k)
+        setattr(p, k, BLOCKMATCH_METRICS.get(v, v) if k == "metric" else v)
+    return p
+
+
+def fuse_similarity(metric, n, sf, sff, sw, sww, sfw):
+    """sift3d_fuse_similarity: u (0 .. 32768) of a patch from its six sums"""
+    return int(host_lib().sift3d_fuse_similarity(int(BLOCKMATCH_METRICS.get(metric, metric)), int(n), int(sf), int(sff), int(sw), int(sww), int(sfw)))
+
+
+def label_overlap(a, b):
+    """sift3d_label_overlap of two float32 label volumes: (labels, count_a, count_b, count_both), the labels that occur in either
+    volume in ascending order and their three int64 counts; Dice = 2 count_both / (count_a + count_b).  Raises where a voxel is
+    neither non-finite nor an integer 0 .. 65535."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    if a.shape != b.shape:
+        raise ValueError("the label volumes differ in shape")
+    ca, cb, cc = (np.zeros(65536, np.int64) for _ in range(3))
+    if host_lib().sift3d_label_overlap(a.ctypes.data, b.ctypes.data, a.size, ca.ctypes.data, cb.ctypes.data, cc.ctypes.data) < 0:
+        raise Sift3DError("sift3d_label_overlap: a label is neither non-finite nor an integer 0 .. 65535")
+    present = np.nonzero((ca > 0) | (cb > 0))[0]
+    return present, ca[present], cb[present], cc[present]
+
+
+def fuse_weights(target, warped, block=2, metric="ssd", w_range=None, device=0, generic=False, return_ms=False):
+    """sift3d_fuse_weights: the similarity u of every voxel's patch, uint16 (nz, ny, nx).  target, warped: (nz, ny, nx) float32 on
+    one grid; w_range: (lo, hi) warped is quantised with (None: the target's range under "ssd", warped's own under "ncc");
+    generic: the kernel's form for any block.  return_ms=True returns (u, kernel_ms)."""
+    t, w = _f32(target), _f32(warped)
+    if t.shape != w.shape:
+        raise ValueError("target and warped differ in shape")
+    nz, ny, nx = t.shape
+    u = np.zeros(t.shape, np.uint16)
+    wr = None if w_range is None else (C.c_float * 2)(float(w_range[0]), float(w_range[1]))
+    ms = C.c_double(0.0)
+    _call("sift3d_fuse_weights", int(device), t.ctypes.data, w.ctypes.data, nx, ny, nz, int(block), int(BLOCKMATCH_METRICS.get(metric, metric)), wr,
+          int(generic), u.ctypes.data, C.byref(ms))
+    return (u, ms.value) if return_ms else u
+
+
+def fuse_vote(u, labels, power=2, device=0, return_ms=False):
+    """sift3d_fuse_vote: u: K arrays of uint16, labels: K arrays of float32 of the same shape (not finite: no vote).  Returns the
+    words, uint32 of that shape + (2,): label | voters << 16 | FUSE_FALLBACK | FUSE_NONE, and conf.  return_ms=True returns
+    (words, kernel_ms)."""
+    us = [np.ascontiguousarray(a, np.uint16) for a in u]
+    ls = [np.ascontiguousarray(a, np.float32) for a in labels]
+    if len(us) != len(ls) or any(a.shape != ls[0].shape for a in us + ls):
+        raise ValueError("u and labels differ in number or shape")
+    K, shape = len(us), (ls[0].shape if ls else (0,))
+    up, lp = (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in us]), (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in ls])
+    words = np.zeros(shape + (2,), np.uint32)
+    ms = C.c_double(0.0)
+    _call("sift3d_fuse_vote", int(device), K, up, lp, int(np.prod(shape)), int(power), words.ctypes.data, C.byref(ms))
+    return (words, ms.value) if return_ms else words
+
+
+def _fuse_report_dict(r, K):
+    return {"none": int(r.none), "fallback": int(r.fallback), "lo": np.float32(r.lo), "hi": np.float32(r.hi), "vote_ms": float(r.vote_ms),
+            "atlas": [{name: getattr(r.atlas[k], name) for name, _ in FuseAtlasReport._fields_ if name != "reserved"} for k in range(K)]}
+
+
+def fuse_labels(target, atlases, target_vox2key=None, device=0, **params):
+    """sift3d_fuse_labels: the stage.  target: (nz, ny, nx) float32; atlases: dicts with image and labels ((nz, ny, nx) float32 of one
+    shape), t (the moving -> fixed key transform, 4 x 4 or a match_keys-style dict) and optionally vox2key (4 x 4) and field (a
+    field dict); params: fields of fuse_params.  Returns (words uint32 (nz, ny, nx, 2), report dict)."""
+    t = _f32(target)
+    nz, ny, nx = t.shape
+    K = len(atlases)
+    arr = (FuseAtlas * max(K, 1))()
+    keep = []
+    for k, a in enumerate(atlases):
+        im, lb = _f32(a["image"]), _f32(a["labels"])
+        if im.shape != lb.shape:
+            raise ValueError("atlas %d: image and labels differ in shape" % k)
+        mv, tm = _m16(a.get("vox2key")), _m16(a["t"])
+        fs, disp = _field_struct(a["field"]) if a.get("field") is not None else (None, None)
+        keep.append((im, lb, mv, tm, fs, disp))
+        arr[k].image, arr[k].labels = im.ctypes.data, lb.ctypes.data
+        arr[k].nz, arr[k].ny, arr[k].nx = im.shape
+        arr[k].vox2key, arr[k].moving_to_fixed = _ptr(mv), tm.ctypes.data
+        arr[k].field = C.addressof(fs) if fs is not None else None
+    words = np.zeros((nz, ny, nx, 2), np.uint32)
+    rep = FuseReport()
+    p = fuse_params(**params)
+    _call("sift3d_fuse_labels", int(device), t.ctypes.data, nx, ny, nz, _ptr(_m16(target_vox2key)), K, arr, C.byref(p), words.ctypes.data,
+          C.byref(rep))
+    return words, _fuse_report_dict(rep, K)
 
 
 def _map12(m):

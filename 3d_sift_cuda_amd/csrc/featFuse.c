@@ -1,0 +1,290 @@
+/*
+ * featFuse.c -- the step after registration: the label maps of several atlases, each registered to a target image
+ * (featExtract, featMatchMultiple -a [-e -u], featResample -i), fused into a segmentation of the target by locally weighted
+ * voting (sift3d_fuse_labels).  Beyond the reference.
+ *
+ *   featFuse [options] <target image> <output labels> <atlas image> <atlas labels> <atlas.trans.txt> <atlas.field.nii|-> [...]
+ *
+ * The target is the fixed image and every atlas a moving one, exactly featResample's roles: <atlas.trans.txt> is what
+ * featMatchMultiple -a wrote for the atlas image against the target, <atlas.field.nii> the displacement field of -a -e -u or of
+ * featResample -i ("-": none).  Four arguments per atlas, 1 .. 32 atlases.  Atlas labels are integers 0 .. 65535; a non-finite
+ * voxel is unlabelled and does not vote.
+ * Writes <output labels> (float32, the target's geometry, -f's value where no atlas votes), <output labels>.conf.nii (the winning
+ * label's share of the vote, 0 .. 1) and <output labels>.fuse.txt (the parameters, the report, the voxels per label and, with -t,
+ * the Dice overlap per label with the truth and their mean over the labels either volume has).
+ */
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "nifti_min.h"
+#include "sift3d.h"
+
+static void print_options(void)
+{
+    printf("Volumetric multi-atlas label fusion by locally weighted voting v1.0\n");
+    printf("Usage: %s [options] <target image> <output labels> <atlas image> <atlas labels> <atlas.trans.txt> <atlas.field.nii|-> [...]\n",
+           "featFuse");
+    printf("  <target image>: nifti (.nii,.hdr,.nii.gz), the image to segment and the grid of the output.\n");
+    printf("  <output labels>: float32 nifti (.nii,.nii.gz); also written: <output labels>.conf.nii and <output labels>.fuse.txt.\n");
+    printf("  then four arguments per atlas, for 1 to %d atlases:\n", SIFT3D_FUSE_MAX_ATLASES);
+    printf("  <atlas image>: nifti, the atlas' intensities.\n");
+    printf("  <atlas labels>: nifti on the atlas image's grid: integers 0 .. 65535, NaN where unlabelled.\n");
+    printf("  <atlas.trans.txt>: the 4x4 transform featMatchMultiple -a wrote for the atlas image against the target.\n");
+    printf("  <atlas.field.nii|->: the atlas' displacement field (featMatchMultiple -a -e -u, featResample -i), or - for none.\n");
+    printf(" [options]\n");
+    printf("  -w         : the features were extracted with -w (world coordinates, NIFTI qto_xyz matrix).\n");
+    printf("  -ws        : the features were extracted with -ws (world coordinates, NIFTI sto_xyz matrix).\n");
+    printf("  -c         : weigh by the patches' normalised correlation: for atlases on other intensity scales (default: squared differences).\n");
+    printf("  -b<half>   : half-width of the patch, 1 .. %d (default 2: 5x5x5 voxels).\n", SIFT3D_BLOCKMATCH_MAX_B);
+    printf("  -p<0|1|2>  : power of the similarity in the vote; 0 is majority voting (default 2).\n");
+    printf("  -f<value>  : value of output voxels where no atlas votes (default 0).\n");
+    printf("  -t <truth> : label image on the target's grid: also write the Dice overlap per label to <output labels>.fuse.txt.\n");
+    printf("  -d[0-9]    : set device id to be used.\n");
+}
+
+/* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
+static void world_matrix(nifti_min_image *img, int world_mode, float m[16])
+{
+    float(*w)[4] = img->qto_xyz;
+    if (world_mode == 2) {
+        if (img->sform_code > 0) w = img->sto_xyz;
+        else printf("Error: sform_code <= 0, using qto_xyz instead of sto_xyz\n");
+    }
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) m[4 * r + c] = w[r][c];
+    m[12] = m[13] = m[14] = 0.0f;
+    m[15] = 1.0f;
+}
+
+static void image_vox2key(nifti_min_image *img, int world_mode, float v[16])
+{
+    const float vox[3] = {img->dx, img->dy, img->dz};
+    float w[16];
+    if (world_mode) world_matrix(img, world_mode, w);
+    sift3d_key_vox2key(vox, world_mode ? w : NULL, v);
+}
+
+static int bad_option(const char *what, const char *arg)
+{
+    printf("Error: %s: %s\n", what, arg);
+    print_options();
+    return -1;
+}
+
+/* <out>.fuse.txt */
+static int write_report(const char *out_path, int K, const sift3d_fuse_params *p, const sift3d_fuse_report *rep, int64_t n, const float *fused,
+                        const float *truth)
+{
+    int64_t *ca = (int64_t *)malloc(sizeof(int64_t) * 3 * 65536);
+    char *path = (char *)malloc(strlen(out_path) + 16);
+    if (!ca || !path) return -1;
+    int64_t *cb = ca + 65536, *cboth = cb + 65536;
+    sprintf(path, "%s.fuse.txt", out_path);
+    FILE *o = fopen(path, "w");
+    free(path);
+    if (!o) return -1;
+    fprintf(o, "# atlases %d block %d metric %s power %d fill %g\n", K, p->block, p->metric == SIFT3D_BLOCKMATCH_NCC ? "ncc" : "ssd", p->power,
+            (double)p->fill);
+    fprintf(o, "# target quantised over %g .. %g\n", (double)rep->lo, (double)rep->hi);
+    fprintf(o, "# voxels %lld none %lld fallback %lld\n", (long long)n, (long long)rep->none, (long long)rep->fallback);
+    fprintf(o, "# atlas voters support mean_u empty_range\n");
+    for (int k = 0; k < K; k++)
+        fprintf(o, "%d\t%lld\t%lld\t%.6f\t%d\n", k + 1, (long long)rep->atlas[k].voters, (long long)rep->atlas[k].support, rep->atlas[k].mean_u,
+                rep->atlas[k].empty_range);
+    /* fused: NaN where no atlas votes, so those voxels have no label here */
+    if (sift3d_label_overlap(fused, truth ? truth : fused, n, ca, cb, cboth) < 0) {
+        fclose(o);
+        free(ca);
+        return -2;
+    }
+    fprintf(o, "# label voxels\n");
+    for (int l = 0; l < 65536; l++)
+        if (ca[l] > 0) fprintf(o, "%d\t%lld\n", l, (long long)ca[l]);
+    if (truth) {
+        double sum = 0;
+        int64_t present = 0;
+        fprintf(o, "# label fused truth both dice\n");
+        for (int l = 0; l < 65536; l++)
+            if (ca[l] > 0 || cb[l] > 0) {
+                const double dice = (double)(2 * cboth[l]) / (double)(ca[l] + cb[l]);
+                fprintf(o, "%d\t%lld\t%lld\t%lld\t%.6f\n", l, (long long)ca[l], (long long)cb[l], (long long)cboth[l], dice);
+                sum += dice;
+                present++;
+            }
+        fprintf(o, "# mean dice %.6f over %lld labels\n", present > 0 ? sum / (double)present : 0.0, (long long)present);
+    }
+    free(ca);
+    return fclose(o);
+}
+
+int main(int argc, char **argv)
+{
+    int device = 0, world_mode = 0;
+    const char *truth_path = NULL;
+    sift3d_fuse_params p;
+    sift3d_fuse_defaults(&p);
+    int arg = 1;
+    while (arg < argc && argv[arg][0] == '-' && argv[arg][1] != 0) {
+        char *end = NULL;
+        switch (argv[arg][1]) {
+        case 'w':
+        case 'W':
+            world_mode = 1;
+            if (argv[arg][2] == 's' || argv[arg][2] == 'S') world_mode = 2;
+            break;
+        case 'c':
+            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            p.metric = SIFT3D_BLOCKMATCH_NCC;
+            break;
+        case 'b': {
+            const long v = strtol(argv[arg] + 2, &end, 10);
+            if (end == argv[arg] + 2 || *end != 0 || v < 1 || v > SIFT3D_BLOCKMATCH_MAX_B) return bad_option("bad patch half-width", argv[arg]);
+            p.block = (int32_t)v;
+            break;
+        }
+        case 'p': {
+            const long v = strtol(argv[arg] + 2, &end, 10);
+            if (end == argv[arg] + 2 || *end != 0 || v < 0 || v > 2) return bad_option("bad power", argv[arg]);
+            p.power = (int32_t)v;
+            break;
+        }
+        case 'f':
+            p.fill = strtof(argv[arg] + 2, &end);
+            if (end == argv[arg] + 2 || *end != 0) return bad_option("bad fill value", argv[arg]);
+            break;
+        case 't':
+            if (argv[arg][2] != 0 || arg + 1 >= argc) return bad_option("-t needs a label image", argv[arg]);
+            truth_path = argv[++arg];
+            break;
+        case 'd':
+            if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count())
+                return bad_option("unknown device", argv[arg] + 2);
+            device = argv[arg][2] - '0';
+            break;
+        default:
+            return bad_option("unknown command line argument", argv[arg]);
+        }
+        arg++;
+    }
+    const int rest = argc - arg - 2;
+    if (rest < 4 || rest % 4 != 0 || rest / 4 > SIFT3D_FUSE_MAX_ATLASES) {
+        if (rest > 0 && rest % 4 != 0) printf("Error: every atlas takes four arguments: <atlas image> <atlas labels> <atlas.trans.txt> <atlas.field.nii|->\n");
+        else if (rest / 4 > SIFT3D_FUSE_MAX_ATLASES) printf("Error: more than %d atlases\n", SIFT3D_FUSE_MAX_ATLASES);
+        print_options();
+        return -1;
+    }
+    const int K = rest / 4;
+    const char *target_path = argv[arg], *out_path = argv[arg + 1];
+    char **group = argv + arg + 2;
+
+    nifti_min_image target, truth;
+    memset(&truth, 0, sizeof truth);
+    if (nifti_min_read(target_path, &target) != 0) {
+        printf("Error: could not read input file: %s\n", target_path);
+        return -1;
+    }
+    if (truth_path && (nifti_min_read(truth_path, &truth) != 0 || truth.nx != target.nx || truth.ny != target.ny || truth.nz != target.nz)) {
+        printf("Error: could not read input file, or it is not on the target's grid: %s\n", truth_path);
+        return -1;
+    }
+    float tv[16];
+    image_vox2key(&target, world_mode, tv);
+    const int64_t n = (int64_t)target.nx * target.ny * target.nz;
+
+    sift3d_fuse_atlas *atlas = (sift3d_fuse_atlas *)calloc((size_t)K, sizeof *atlas);
+    nifti_min_image *img = (nifti_min_image *)calloc((size_t)(2 * K), sizeof *img);
+    sift3d_field *field = (sift3d_field *)calloc((size_t)K, sizeof *field);
+    float *mats = (float *)calloc((size_t)K, sizeof(float) * 32);
+    if (!atlas || !img || !field || !mats) {
+        printf("Error: insufficient memory.\n");
+        return -1;
+    }
+    for (int k = 0; k < K; k++) {
+        const char *image_path = group[4 * k], *labels_path = group[4 * k + 1], *trans_path = group[4 * k + 2], *field_path = group[4 * k + 3];
+        nifti_min_image *im = &img[2 * k], *lb = &img[2 * k + 1];
+        float *mv = mats + 32 * k, *t = mv + 16;
+        if (nifti_min_read(image_path, im) != 0) {
+            printf("Error: could not read input file: %s\n", image_path);
+            return -1;
+        }
+        if (nifti_min_read(labels_path, lb) != 0 || lb->nx != im->nx || lb->ny != im->ny || lb->nz != im->nz) {
+            printf("Error: could not read input file, or it is not on the atlas image's grid: %s\n", labels_path);
+            return -1;
+        }
+        if (sift3d_read_similarity(trans_path, t) != 0) {
+            printf("Error: could not read transform file: %s\n", trans_path);
+            return -1;
+        }
+        image_vox2key(im, world_mode, mv);
+        if (strcmp(field_path, "-") != 0) {
+            int frc = sift3d_read_field(field_path, &field[k]);
+            if (frc == SIFT3D_ERR_CAPACITY) {
+                field[k].capacity = 3 * field[k].n[0] * field[k].n[1] * field[k].n[2];
+                field[k].disp = (float *)malloc(sizeof(float) * (size_t)field[k].capacity);
+                frc = field[k].disp ? sift3d_read_field(field_path, &field[k]) : SIFT3D_ERR_MEMORY;
+            }
+            if (frc != SIFT3D_OK) {
+                printf("Error: could not read displacement field file: %s\n", field_path);
+                return -1;
+            }
+            atlas[k].field = &field[k];
+        }
+        atlas[k].image = im->data;
+        atlas[k].labels = lb->data;
+        atlas[k].nx = im->nx;
+        atlas[k].ny = im->ny;
+        atlas[k].nz = im->nz;
+        atlas[k].vox2key = mv;
+        atlas[k].moving_to_fixed = t;
+    }
+    printf("Fusing: %d atlases onto %s (i=%d j=%d k=%d)\n", K, target_path, target.nx, target.ny, target.nz);
+    uint32_t *words = (uint32_t *)malloc(sizeof(uint32_t) * 2 * (size_t)n);
+    float *labels = (float *)malloc(sizeof(float) * (size_t)n), *conf = (float *)malloc(sizeof(float) * (size_t)n);
+    char *path = (char *)malloc(strlen(out_path) + 16);
+    if (!words || !labels || !conf || !path) {
+        printf("Error: could not fuse, insufficient memory.\n");
+        return -1;
+    }
+    char err[512] = "";
+    sift3d_fuse_report rep;
+    if (sift3d_fuse_labels(device, target.data, target.nx, target.ny, target.nz, tv, K, atlas, &p, words, &rep, err, sizeof err) != SIFT3D_OK) {
+        printf("Error: could not fuse: %s\n", err);
+        return -1;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        labels[i] = (words[2 * i] & SIFT3D_FUSE_NONE) ? p.fill : (float)(words[2 * i] & 0xffffu);
+        conf[i] = (float)words[2 * i + 1] / 65535.0f;
+    }
+    sprintf(path, "%s.conf.nii", out_path);
+    if (nifti_min_write_f32_geom(out_path, labels, target_path) != 0 || nifti_min_write_f32_geom(path, conf, target_path) != 0) {
+        printf("Error: could not write output file: %s\n", out_path);
+        return -1;
+    }
+    for (int64_t i = 0; i < n; i++)
+        if (words[2 * i] & SIFT3D_FUSE_NONE) labels[i] = NAN;
+    const int wrc = write_report(out_path, K, &p, &rep, n, labels, truth_path ? truth.data : NULL);
+    if (wrc != 0) {
+        if (wrc == -2) printf("Error: a voxel of the truth is neither non-finite nor an integer 0 .. 65535: %s\n", truth_path);
+        else printf("Error: could not write the report of: %s\n", out_path);
+        return -1;
+    }
+    printf("\nDone.\n");
+    for (int k = 0; k < K; k++) {
+        nifti_min_free(&img[2 * k]);
+        nifti_min_free(&img[2 * k + 1]);
+        free(field[k].disp);
+    }
+    free(path);
+    free(conf);
+    free(labels);
+    free(words);
+    free(mats);
+    free(field);
+    free(img);
+    free(atlas);
+    nifti_min_free(&target);
+    if (truth_path) nifti_min_free(&truth);
+    return 0;
+}

@@ -1,7 +1,8 @@
 /*
  * warp_device.h -- the arithmetic and the thread mappings that the warp family shares on gfx950 (MI355X): the image sampler,
  * the gather of a displacement field's nodes, the position of an output voxel under a map and a field, the brick of output
- * voxels and the brick of nodes.  Included by kernels_resample.hip, kernels_field.hip and kernels_invert.hip only; every
+ * voxels and the brick of nodes.  Included by kernels_resample.hip, kernels_field.hip, kernels_invert.hip and kernels_fuse.hip
+ * (which takes the brick of output voxels alone) only; every
  * function is __device__ __forceinline__, or a host inline that fills one of the structs or sizes a launch (marked "host"), so
  * each kernel keeps its own code.  tests/resample_oracle.c,
  * tests/field_oracle.c and tests/invert_oracle.c restate the arithmetic on the CPU, operation for operation.

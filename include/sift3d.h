@@ -1034,6 +1034,97 @@ int sift3d_compose_grid(int64_t nx, int64_t ny, int64_t nz, const float a_vox2ke
  * in index order: their count (returned), *rms = sqrt(sum / count) and *max = sqrt of the largest value; 0 for no cell. */
 int64_t sift3d_compose_residual(const int64_t n[3], const uint32_t *status, const double *res2, int64_t margin, double *rms, double *max);
 
+/* ---- multi-atlas label fusion by locally weighted voting (featFuse; beyond the reference) -----------------------------------
+ * DESIGN.md section 7j states the contract; tests/fuse_oracle.c restates it as a serial brute force.
+ *
+ * The target T (nx ny nz floats, x fastest, extents 1 .. 2^24) is the fixed image; each of K atlases (1 .. SIFT3D_FUSE_MAX_ATLASES)
+ * is a moving one with an intensity volume, a label volume of the same extents, its moving_to_fixed 4 x 4 and an optional field:
+ * featResample's roles.  Atlas label voxels are non-finite (unlabelled) or integers 0 .. 65535; anything else is SIFT3D_ERR_ARG.
+ * Warp: W_k = the atlas intensities through sift3d_resample_field's arithmetic (sift3d_resample_affine's without a field), linear,
+ * fill NaN; M_k = the atlas labels through the same map, nearest, fill NaN.
+ * Quantisation: section 7f's q (-1: not finite).  T with T's range (sift3d_blockmatch_range; an empty range refuses the call);
+ * W_k with T's range under SIFT3D_BLOCKMATCH_SSD and with the range of atlas k's own intensity volume under SIFT3D_BLOCKMATCH_NCC
+ * (an empty one gives that atlas u = 0 everywhere).
+ * Patch sums, per voxel x and atlas k, half-width b (1 .. SIFT3D_BLOCKMATCH_MAX_B): over the u in [-b, b]^3 with x + u inside the
+ * volume, qT(x + u) >= 0 and qW(x + u) >= 0: n = their count, Sf = sum qT, Sff = sum qT^2, Sw = sum qW, Sww = sum qW^2,
+ * Sfw = sum qT qW; each below 2^32.  Border patches are clipped, not flagged.
+ * Similarity u_k(x) in 0 .. 32768, 0 where n = 0 (sift3d_fuse_similarity):
+ *   SSD: D = Sff - 2 Sfw + Sww (int64, >= 0); u = (n 2^15) / (D + n), unsigned 64-bit division: one quantisation step^2 per voxel
+ *        regularises, D = 0 gives 32768.
+ *   NCC: A = n Sfw - Sf Sw, Vf = n Sff - Sf^2, Vw = n Sww - Sw^2; c = section 7g's cost (its sequence of double operations, n in
+ *        place of N); u = (2^31 - c) >> 16.
+ * Weight: w = 1 (power 0: majority voting), u (power 1) or u u <= 2^30 (power 2).
+ * Vote: atlas k votes at x iff M_k(x) is finite.  S(l) = sum of w_k over the voters with M_k(x) = l (uint64).  If power > 0 and every
+ * voter's w is 0, every voter weighs 1 and SIFT3D_FUSE_FALLBACK is set.  The fused label is the l of the largest S(l), ties to the
+ * smallest l; conf = (S(win) 65535) / sum over l of S(l), integer division.  No voter: label 0, conf 0, SIFT3D_FUSE_NONE.
+ * Two 32-bit words per voxel: [0] label in bits 0 - 15, the number of voters in bits 16 - 21, the two flags; [1] conf. */
+#define SIFT3D_FUSE_MAX_ATLASES 32
+#define SIFT3D_FUSE_U_ONE 32768
+#define SIFT3D_FUSE_FALLBACK 0x40000000u /* bit 30 */
+#define SIFT3D_FUSE_NONE 0x80000000u     /* bit 31 */
+
+typedef struct {
+    int32_t block;      /* b, the patch half-width: 2; 1 .. SIFT3D_BLOCKMATCH_MAX_B */
+    int32_t metric;     /* SIFT3D_BLOCKMATCH_SSD */
+    int32_t power;      /* 2; 0, 1 or 2 */
+    float fill;         /* 0: the value featFuse writes where no atlas votes (the words do not depend on it) */
+    int64_t max_voxels; /* 2^28: above max_voxels target voxels times atlases the stage is refused */
+} sift3d_fuse_params;
+void sift3d_fuse_defaults(sift3d_fuse_params *p);
+
+typedef struct {
+    const float *image, *labels;  /* nx ny nz floats each, x fastest */
+    int64_t nx, ny, nz;           /* 1 .. 2^24 */
+    const float *vox2key;         /* 16 floats; NULL: identity */
+    const float *moving_to_fixed; /* 16 floats: the atlas' .trans.txt */
+    const sift3d_field *field;    /* NULL: none */
+} sift3d_fuse_atlas;
+
+typedef struct {
+    int64_t voters;      /* voxels where the atlas votes */
+    int64_t support;     /* voxels where it votes for the fused label */
+    double mean_u;       /* (double)(sum of u over its voters) / voters; 0 for no voter or power 0 */
+    int32_t empty_range; /* 1: NCC and the atlas' intensities have no two distinct finite values */
+    int32_t reserved;
+    double warp_ms, weight_ms; /* device time: the atlas' uploads and its two warps; quantisation + fuse_weight_kernel */
+} sift3d_fuse_atlas_report;
+
+typedef struct {
+    int64_t none, fallback; /* voxels with SIFT3D_FUSE_NONE, with SIFT3D_FUSE_FALLBACK */
+    float lo, hi;           /* T's quantisation range */
+    double vote_ms;         /* device time: fuse_vote_kernel */
+    sift3d_fuse_atlas_report atlas[SIFT3D_FUSE_MAX_ATLASES];
+} sift3d_fuse_report;
+
+/* fuse_weight_kernel alone: T and W (already on T's grid) host arrays, u one uint16 per voxel.  w_range: lo, hi that W is quantised
+ * with; NULL: T's range under SSD, W's own under NCC.  A w_range without hi > lo gives u = 0 everywhere.  generic: 0 the kernel's
+ * form with b at compile time where one exists (b = 2), anything else its form for any b (same u).  SIFT3D_ERR_ARG with text: extents
+ * outside 1 .. 2^24, b outside 1 .. 6, an unknown metric, a T without two distinct finite values. */
+int sift3d_fuse_weights(int device, const float *t, const float *w, int64_t nx, int64_t ny, int64_t nz, int32_t b, int32_t metric,
+                        const float w_range[2], int32_t generic, uint16_t *u, double *kernel_ms, char *err, int64_t err_len);
+/* fuse_label_kernel and fuse_vote_kernel alone: u[k], labels[k]: n values each of atlas k (u <= 32768; labels as the atlas labels
+ * above, not finite: no vote); words: 2 n.  SIFT3D_ERR_ARG with text: K outside 1 .. 32, a power outside 0 .. 2, a u above 32768, a
+ * label that is neither non-finite nor an integer 0 .. 65535 (the text names the atlas and the first such voxel). */
+int sift3d_fuse_vote(int device, int32_t K, const uint16_t *const *u, const float *const *labels, int64_t n, int32_t power, uint32_t *words,
+                     double *kernel_ms, char *err, int64_t err_len);
+/* The stage.  T is quantised once and stays on the device; the atlases stream through one at a time (warp, quantise, weigh, warp the
+ * labels); the u and label planes stay for the vote, 4 bytes per voxel and atlas.  Power 0 launches no weight kernel and warps no
+ * intensities.  p NULL: defaults.  words: 2 nx ny nz; rep may be NULL.  SIFT3D_ERR_ARG with text: what the above refuse, a matrix
+ * that sift3d_resample_map refuses, a field that sift3d_resample_field refuses, nx ny nz K above max_voxels. */
+int sift3d_fuse_labels(int device, const float *target, int64_t nx, int64_t ny, int64_t nz, const float target_vox2key[16], int32_t K,
+                       const sift3d_fuse_atlas *atlases, const sift3d_fuse_params *p, uint32_t *words, sift3d_fuse_report *rep, char *err,
+                       int64_t err_len);
+
+/* Host helpers (also in libsift3d_host.so).
+ * u from the six sums under a metric, as stated above; 0 for n <= 0 or an unknown metric. */
+uint32_t sift3d_fuse_similarity(int32_t metric, int64_t n, int64_t sf, int64_t sff, int64_t sw, int64_t sww, int64_t sfw);
+/* The first voxel of a label volume that is neither non-finite nor an integer 0 .. 65535, or -1 for none */
+int64_t sift3d_fuse_check_labels(const float *labels, int64_t n);
+/* The overlap of two label volumes in exact counts: per label l, count_a[l] and count_b[l] voxels of that label (non-finite voxels
+ * have none) and count_both[l] where both have it; each array holds 65536 counts.  Dice(l) = 2 count_both / (count_a + count_b).
+ * Returns the number of labels that occur in either volume, or -1 where sift3d_fuse_check_labels refuses one of them. */
+int64_t sift3d_label_overlap(const float *a, const float *b, int64_t n, int64_t *count_a, int64_t *count_b, int64_t *count_both);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
