@@ -187,6 +187,8 @@ def hip_lib():
     _sig(L.sift3d_fuse_weights, I, I, P, P, I64, I64, I64, C.c_int32, C.c_int32, P, C.c_int32, P, P, C.c_char_p, I64)
     _sig(L.sift3d_fuse_vote, I, I, C.c_int32, P, P, I64, C.c_int32, P, P, C.c_char_p, I64)
     _sig(L.sift3d_fuse_labels, I, I, P, I64, I64, I64, P, C.c_int32, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_fuse_search, I, I, P, P, P, I64, I64, I64, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_fuse_labels_search, I, I, P, I64, I64, I64, P, C.c_int32, P, P, C.c_int32, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -255,6 +257,9 @@ def host_lib():
     _sig(L.sift3d_fuse_defaults, None, P)
     _sig(L.sift3d_fuse_similarity, C.c_uint32, C.c_int32, I64, I64, I64, I64, I64, I64)
     _sig(L.sift3d_fuse_check_labels, I64, P, I64)
+    _sig(L.sift3d_fuse_shift_code, C.c_uint16, C.c_int32, C.c_int32, C.c_int32, C.c_int32)
+    _sig(L.sift3d_fuse_shift_of, I, C.c_int32, C.c_uint32, P)
+    _sig(L.sift3d_fuse_shift_stats, I64, C.c_int32, P, I64, P, P)
     _sig(L.sift3d_label_overlap, I64, P, P, I64, P, P, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
@@ -1312,10 +1317,8 @@ def _fuse_report_dict(r, K):
             "atlas": [{name: getattr(r.atlas[k], name) for name, _ in FuseAtlasReport._fields_ if name != "reserved"} for k in range(K)]}
 
 
-def fuse_labels(target, atlases, target_vox2key=None, device=0, **params):
-    """sift3d_fuse_labels: the stage.  target: (nz, ny, nx) float32; atlases: dicts with image and labels ((nz, ny, nx) float32 of one
-    shape), t (the moving -> fixed key transform, 4 x 4 or a match_keys-style dict) and optionally vox2key (4 x 4) and field (a
-    field dict); params: fields of fuse_params.  Returns (words uint32 (nz, ny, nx, 2), report dict)."""
+def _fuse_stage(entry, target, atlases, target_vox2key, device, search, params):
+    """sift3d_fuse_labels or sift3d_fuse_labels_search (entry) on the arguments of fuse_labels"""
     t = _f32(target)
     nz, ny, nx = t.shape
     K = len(atlases)
@@ -1335,9 +1338,80 @@ def fuse_labels(target, atlases, target_vox2key=None, device=0, **params):
     words = np.zeros((nz, ny, nx, 2), np.uint32)
     rep = FuseReport()
     p = fuse_params(**params)
-    _call("sift3d_fuse_labels", int(device), t.ctypes.data, nx, ny, nz, _ptr(_m16(target_vox2key)), K, arr, C.byref(p), words.ctypes.data,
-          C.byref(rep))
-    return words, _fuse_report_dict(rep, K)
+    if entry == "sift3d_fuse_labels":
+        _call(entry, int(device), t.ctypes.data, nx, ny, nz, _ptr(_m16(target_vox2key)), K, arr, C.byref(p), words.ctypes.data, C.byref(rep))
+        return words, _fuse_report_dict(rep, K)
+    srep = FuseSearchReport()
+    _call(entry, int(device), t.ctypes.data, nx, ny, nz, _ptr(_m16(target_vox2key)), K, arr, C.byref(p), int(search), words.ctypes.data, C.byref(rep),
+          C.byref(srep))
+    out = _fuse_report_dict(rep, K)
+    out["search"] = {"radius": int(srep.radius),
+                     "atlas": [{name: getattr(srep.atlas[k], name) for name, _ in FuseSearchAtlasReport._fields_} for k in range(K)]}
+    return words, out
+
+
+def fuse_labels(target, atlases, target_vox2key=None, device=0, search=0, **params):
+    """sift3d_fuse_labels: the stage.  target: (nz, ny, nx) float32; atlases: dicts with image and labels ((nz, ny, nx) float32 of one
+    shape), t (the moving -> fixed key transform, 4 x 4 or a match_keys-style dict) and optionally vox2key (4 x 4) and field (a
+    field dict); params: fields of fuse_params.  Returns (words uint32 (nz, ny, nx, 2), report dict).  search = 1 .. 3:
+    sift3d_fuse_labels_search, every atlas votes from its best-matching patch within that radius, and the
+    report gains "search": the radius and per atlas moved, dist2_sum and search_ms."""
+    entry = "sift3d_fuse_labels" if search == 0 else "sift3d_fuse_labels_search"
+    return _fuse_stage(entry, target, atlases, target_vox2key, device, search, params)
+
+
+# ---- the local search of the label fusion (featFuse -s), DESIGN.md section 7k ----------------------------------------------
+FUSE_MAX_SEARCH, FUSE_NO_SHIFT = 3, 0xffff
+
+
+class FuseSearchAtlasReport(C.Structure):
+    """sift3d_fuse_search_atlas_report"""
+    _fields_ = [("moved", C.c_int64), ("dist2_sum", C.c_int64), ("search_ms", C.c_double)]
+
+
+class FuseSearchReport(C.Structure):
+    """sift3d_fuse_search_report"""
+    _fields_ = [("radius", C.c_int32), ("reserved", C.c_int32), ("atlas", FuseSearchAtlasReport * FUSE_MAX_ATLASES)]
+
+
+def fuse_shift_code(radius, t):
+    """sift3d_fuse_shift_code of the shift t = (tx, ty, tz); FUSE_NO_SHIFT where it is none under the radius"""
+    return int(host_lib().sift3d_fuse_shift_code(int(radius), int(t[0]), int(t[1]), int(t[2])))
+
+
+def fuse_shift_of(radius, code):
+    """sift3d_fuse_shift_of: (tx, ty, tz), or None for a code that is none under the radius"""
+    t = (C.c_int32 * 3)()
+    return None if host_lib().sift3d_fuse_shift_of(int(radius), int(code), t) != 0 else (t[0], t[1], t[2])
+
+
+def fuse_shift_stats(radius, shift):
+    """sift3d_fuse_shift_stats over an array of codes: (voters, moved, dist2_sum); raises for a code that is none under the radius"""
+    s = np.ascontiguousarray(shift, np.uint16)
+    moved, d2 = C.c_int64(0), C.c_int64(0)
+    voters = host_lib().sift3d_fuse_shift_stats(int(radius), s.ctypes.data, s.size, C.byref(moved), C.byref(d2))
+    if voters < 0:
+        raise Sift3DError("sift3d_fuse_shift_stats: a code is none under the radius %d" % radius)
+    return int(voters), int(moved.value), int(d2.value)
+
+
+def fuse_search(target, warped, labels=None, block=2, radius=1, metric="ssd", w_range=None, device=0, generic=False, return_ms=False):
+    """sift3d_fuse_search: per voxel the similarity u of warped's best-matching patch within the radius, the code of its shift and
+    the label picked there: (u uint16, shift uint16, picked float32 or None), each (nz, ny, nx).  target, warped and the optional
+    labels (warped labels, not finite: may not be picked): (nz, ny, nx) float32 on one grid; w_range and generic as for
+    fuse_weights.  return_ms=True appends kernel_ms."""
+    t, w = _f32(target), _f32(warped)
+    lb = None if labels is None else _f32(labels)
+    if t.shape != w.shape or (lb is not None and lb.shape != t.shape):
+        raise ValueError("target, warped and labels differ in shape")
+    nz, ny, nx = t.shape
+    u, shift = np.zeros(t.shape, np.uint16), np.zeros(t.shape, np.uint16)
+    picked = None if lb is None else np.zeros(t.shape, np.float32)
+    wr = None if w_range is None else (C.c_float * 2)(float(w_range[0]), float(w_range[1]))
+    ms = C.c_double(0.0)
+    _call("sift3d_fuse_search", int(device), t.ctypes.data, w.ctypes.data, _ptr(lb), nx, ny, nz, int(block), int(radius),
+          int(BLOCKMATCH_METRICS.get(metric, metric)), wr, int(generic), u.ctypes.data, shift.ctypes.data, _ptr(picked), C.byref(ms))
+    return (u, shift, picked, ms.value) if return_ms else (u, shift, picked)
 
 
 def _map12(m):

@@ -1,7 +1,8 @@
 /*
  * featFuse.c -- the step after registration: the label maps of several atlases, each registered to a target image
  * (featExtract, featMatchMultiple -a [-e -u], featResample -i), fused into a segmentation of the target by locally weighted
- * voting (sift3d_fuse_labels).  Beyond the reference.
+ * voting (sift3d_fuse_labels); with -s every atlas votes from its best-matching patch within a radius
+ * (sift3d_fuse_labels_search, section 7k).  Beyond the reference.
  *
  *   featFuse [options] <target image> <output labels> <atlas image> <atlas labels> <atlas.trans.txt> <atlas.field.nii|-> [...]
  *
@@ -11,7 +12,8 @@
  * voxel is unlabelled and does not vote.
  * Writes <output labels> (float32, the target's geometry, -f's value where no atlas votes), <output labels>.conf.nii (the winning
  * label's share of the vote, 0 .. 1) and <output labels>.fuse.txt (the parameters, the report, the voxels per label and, with -t,
- * the Dice overlap per label with the truth and their mean over the labels either volume has).
+ * the Dice overlap per label with the truth and their mean over the labels either volume has; with -s the radius and per atlas the
+ * voxels where it voted from another place and the mean squared distance of its votes).
  */
 #include <math.h>
 #include <stdio.h>
@@ -39,6 +41,8 @@ static void print_options(void)
     printf("  -c         : weigh by the patches' normalised correlation: for atlases on other intensity scales (default: squared differences).\n");
     printf("  -b<half>   : half-width of the patch, 1 .. %d (default 2: 5x5x5 voxels).\n", SIFT3D_BLOCKMATCH_MAX_B);
     printf("  -p<0|1|2>  : power of the similarity in the vote; 0 is majority voting (default 2).\n");
+    printf("  -s<radius> : every atlas votes with the label and the weight of its best-matching patch within <radius> voxels, 1 .. %d;\n", SIFT3D_FUSE_MAX_SEARCH);
+    printf("               half-width + radius at most %d, and not with -p0 (default: no search).\n", SIFT3D_BLOCKMATCH_MAX_B);
     printf("  -f<value>  : value of output voxels where no atlas votes (default 0).\n");
     printf("  -t <truth> : label image on the target's grid: also write the Dice overlap per label to <output labels>.fuse.txt.\n");
     printf("  -d[0-9]    : set device id to be used.\n");
@@ -74,8 +78,8 @@ static int bad_option(const char *what, const char *arg)
 }
 
 /* <out>.fuse.txt */
-static int write_report(const char *out_path, int K, const sift3d_fuse_params *p, const sift3d_fuse_report *rep, int64_t n, const float *fused,
-                        const float *truth)
+static int write_report(const char *out_path, int K, const sift3d_fuse_params *p, const sift3d_fuse_report *rep, const sift3d_fuse_search_report *srep,
+                        int64_t n, const float *fused, const float *truth)
 {
     int64_t *ca = (int64_t *)malloc(sizeof(int64_t) * 3 * 65536);
     char *path = (char *)malloc(strlen(out_path) + 16);
@@ -93,6 +97,12 @@ static int write_report(const char *out_path, int K, const sift3d_fuse_params *p
     for (int k = 0; k < K; k++)
         fprintf(o, "%d\t%lld\t%lld\t%.6f\t%d\n", k + 1, (long long)rep->atlas[k].voters, (long long)rep->atlas[k].support, rep->atlas[k].mean_u,
                 rep->atlas[k].empty_range);
+    if (srep) {
+        fprintf(o, "# search radius %d\n# atlas moved mean_dist2\n", srep->radius);
+        for (int k = 0; k < K; k++)
+            fprintf(o, "%d\t%lld\t%.6f\n", k + 1, (long long)srep->atlas[k].moved,
+                    rep->atlas[k].voters > 0 ? (double)srep->atlas[k].dist2_sum / (double)rep->atlas[k].voters : 0.0);
+    }
     /* fused: NaN where no atlas votes, so those voxels have no label here */
     if (sift3d_label_overlap(fused, truth ? truth : fused, n, ca, cb, cboth) < 0) {
         fclose(o);
@@ -122,6 +132,7 @@ static int write_report(const char *out_path, int K, const sift3d_fuse_params *p
 int main(int argc, char **argv)
 {
     int device = 0, world_mode = 0;
+    int32_t search = 0;
     const char *truth_path = NULL;
     sift3d_fuse_params p;
     sift3d_fuse_defaults(&p);
@@ -150,6 +161,12 @@ int main(int argc, char **argv)
             p.power = (int32_t)v;
             break;
         }
+        case 's': {
+            const long v = strtol(argv[arg] + 2, &end, 10);
+            if (end == argv[arg] + 2 || *end != 0 || v < 1 || v > SIFT3D_FUSE_MAX_SEARCH) return bad_option("bad search radius", argv[arg]);
+            search = (int32_t)v;
+            break;
+        }
         case 'f':
             p.fill = strtof(argv[arg] + 2, &end);
             if (end == argv[arg] + 2 || *end != 0) return bad_option("bad fill value", argv[arg]);
@@ -168,6 +185,8 @@ int main(int argc, char **argv)
         }
         arg++;
     }
+    if (search > 0 && p.power == 0) return bad_option("a search needs weights to search by", "-s with -p0");
+    if (search > 0 && p.block + search > SIFT3D_BLOCKMATCH_MAX_B) return bad_option("the patch half-width plus the search radius must not exceed 6", "-b with -s");
     const int rest = argc - arg - 2;
     if (rest < 4 || rest % 4 != 0 || rest / 4 > SIFT3D_FUSE_MAX_ATLASES) {
         if (rest > 0 && rest % 4 != 0) printf("Error: every atlas takes four arguments: <atlas image> <atlas labels> <atlas.trans.txt> <atlas.field.nii|->\n");
@@ -249,7 +268,11 @@ int main(int argc, char **argv)
     }
     char err[512] = "";
     sift3d_fuse_report rep;
-    if (sift3d_fuse_labels(device, target.data, target.nx, target.ny, target.nz, tv, K, atlas, &p, words, &rep, err, sizeof err) != SIFT3D_OK) {
+    sift3d_fuse_search_report srep;
+    const int frc = search > 0 ? sift3d_fuse_labels_search(device, target.data, target.nx, target.ny, target.nz, tv, K, atlas, &p, search, words, &rep, &srep, err,
+                                                           sizeof err)
+                               : sift3d_fuse_labels(device, target.data, target.nx, target.ny, target.nz, tv, K, atlas, &p, words, &rep, err, sizeof err);
+    if (frc != SIFT3D_OK) {
         printf("Error: could not fuse: %s\n", err);
         return -1;
     }
@@ -264,7 +287,7 @@ int main(int argc, char **argv)
     }
     for (int64_t i = 0; i < n; i++)
         if (words[2 * i] & SIFT3D_FUSE_NONE) labels[i] = NAN;
-    const int wrc = write_report(out_path, K, &p, &rep, n, labels, truth_path ? truth.data : NULL);
+    const int wrc = write_report(out_path, K, &p, &rep, search > 0 ? &srep : NULL, n, labels, truth_path ? truth.data : NULL);
     if (wrc != 0) {
         if (wrc == -2) printf("Error: a voxel of the truth is neither non-finite nor an integer 0 .. 65535: %s\n", truth_path);
         else printf("Error: could not write the report of: %s\n", out_path);

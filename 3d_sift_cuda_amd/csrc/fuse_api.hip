@@ -1,8 +1,9 @@
 /*
  * fuse_api.hip -- C-ABI of the label fusion (include/sift3d.h, "multi-atlas label fusion"):
- * sift3d_fuse_weights, sift3d_fuse_vote and sift3d_fuse_labels.  The kernels are in kernels_fuse.hip; the warps are section 7c's
+ * sift3d_fuse_weights, sift3d_fuse_vote and sift3d_fuse_labels, and section 7k's local search: sift3d_fuse_search and
+ * sift3d_fuse_labels_search.  The kernels are in kernels_fuse.hip and kernels_fuse_search.hip; the warps are section 7c's
  * and 7e's (kernels_resample.hip, kernels_field.hip), the quantisation section 7f's (kernels_blockmatch.hip); the defaults, the
- * label check and the report's counts are host arithmetic (fuse_host.c and below).
+ * label check, the shift codes and the reports' counts are host arithmetic (fuse_host.c and below).
  */
 #include <cmath>
 #include <cstring>
@@ -15,6 +16,8 @@ hipError_t sift3d_launch_fuse_weight(hipStream_t s, const short *qt, const short
                                      unsigned short *u);
 hipError_t sift3d_launch_fuse_label(hipStream_t s, const float *labels, int64_t n, int clear_u, unsigned short *lab, unsigned short *u);
 hipError_t sift3d_launch_fuse_vote(hipStream_t s, const unsigned short *u, const unsigned short *lab, int K, int64_t n, int power, unsigned *words);
+hipError_t sift3d_launch_fuse_search(hipStream_t s, const short *qt, const short *qw, const float *labels, int64_t nx, int64_t ny, int64_t nz, int b, int r,
+                                     int ncc, int generic, unsigned short *u, unsigned short *shift, float *picked);
 
 /* NULL, or why the weight kernel refuses these arguments */
 static const char *check_weights(int64_t nx, int64_t ny, int64_t nz, int b, int metric)
@@ -24,6 +27,14 @@ static const char *check_weights(int64_t nx, int64_t ny, int64_t nz, int b, int 
     if (nx * ny > (1ll << 38) / nz) return "volume larger than 2^38 voxels";
     if (b < 1 || b > SIFT3D_BLOCKMATCH_MAX_B) return "the patch half-width must be 1 .. 6";
     if (metric != SIFT3D_BLOCKMATCH_SSD && metric != SIFT3D_BLOCKMATCH_NCC) return "unknown metric: SIFT3D_BLOCKMATCH_SSD (0) or SIFT3D_BLOCKMATCH_NCC (1)";
+    return nullptr;
+}
+
+/* NULL, or why the search kernel refuses this radius with this half-width */
+static const char *check_search(int b, int r)
+{
+    if (r < 0 || r > SIFT3D_FUSE_MAX_SEARCH) return "the search radius must be 0 .. 3";
+    if (b + r > SIFT3D_BLOCKMATCH_MAX_B) return "the patch half-width plus the search radius must not exceed 6";
     return nullptr;
 }
 
@@ -83,6 +94,64 @@ static int check_labels(int k, const float *labels, int64_t n, char *err, int64_
                      (double)labels[bad], (long long)bad);
 }
 
+extern "C" int sift3d_fuse_search(int device, const float *t, const float *w, const float *labels, int64_t nx, int64_t ny, int64_t nz, int32_t b, int32_t r,
+                                  int32_t metric, const float w_range[2], int32_t generic, uint16_t *u, uint16_t *shift, float *picked, double *kernel_ms,
+                                  char *err, int64_t err_len)
+{
+    if (err && err_len > 0) err[0] = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (!t || !w || !u || !shift || (labels && !picked)) return call_fail(err, err_len, SIFT3D_ERR_ARG, "null pointer");
+    const char *why = check_weights(nx, ny, nz, b, metric);
+    if (!why) why = check_search(b, r);
+    if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%s", why);
+    const size_t nv = (size_t)(nx * ny * nz);
+    if (labels) {
+        const int rc = check_labels(0, labels, (int64_t)nv, err, err_len);
+        if (rc != SIFT3D_OK) return rc;
+    }
+    float lo, hi;
+    if (!sift3d_blockmatch_range(t, (int64_t)nv, &lo, &hi))
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "the target has no two distinct finite values: nothing to quantise");
+    float wlo = lo, whi = hi;
+    bool ranged = true;
+    if (w_range) {
+        wlo = w_range[0];
+        whi = w_range[1];
+        ranged = whi > wlo && std::isfinite(wlo) && std::isfinite(whi);
+    } else if (metric == SIFT3D_BLOCKMATCH_NCC) {
+        ranged = sift3d_blockmatch_range(w, (int64_t)nv, &wlo, &whi) != 0;
+    }
+    device_call dc(err, err_len);
+    float *d_v, *d_l = nullptr, *d_p = nullptr;
+    short *d_qt, *d_qw;
+    unsigned short *d_u, *d_s;
+    DEVCHK(dc, dc.open(device));
+    if (dc.alloc(&d_v, nv) != hipSuccess || dc.alloc(&d_qt, nv) != hipSuccess || dc.alloc(&d_qw, nv) != hipSuccess || dc.alloc(&d_u, nv) != hipSuccess ||
+        dc.alloc(&d_s, nv) != hipSuccess || (labels && (dc.alloc(&d_l, nv) != hipSuccess || dc.alloc(&d_p, nv) != hipSuccess))) {
+        (void)hipGetLastError();
+        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", (labels ? 20 : 12) * nv, device);
+    }
+    DEVCHK(dc, dc.to_device(d_v, t, nv));
+    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_qt));
+    if (ranged) {
+        DEVCHK(dc, dc.to_device(d_v, w, nv));
+        DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)wlo, (double)whi, d_qw));
+    } else {
+        /* no range to quantise W with: every voxel of it is invalid, every patch is empty, u = 0 and the shift 0 wins every tie */
+        DEVCHK(dc, hipMemsetAsync(d_qw, 0xff, sizeof(short) * nv, dc.s));
+    }
+    if (labels) DEVCHK(dc, dc.to_device(d_l, labels, nv));
+    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, sift3d_launch_fuse_search(dc.s, d_qt, d_qw, d_l, nx, ny, nz, b, r, metric == SIFT3D_BLOCKMATCH_NCC, generic, d_u, d_s, d_p));
+    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.download((unsigned short *)u, d_u, nv));
+    DEVCHK(dc, dc.download((unsigned short *)shift, d_s, nv));
+    if (labels) DEVCHK(dc, dc.download(picked, d_p, nv));
+    DEVCHK(dc, dc.sync());
+    DEVCHK(dc, dc.elapsed_ms(kernel_ms));
+    return SIFT3D_OK;
+}
+
 extern "C" int sift3d_fuse_vote(int device, int32_t K, const uint16_t *const *u, const float *const *labels, int64_t n, int32_t power, uint32_t *words,
                                 double *kernel_ms, char *err, int64_t err_len)
 {
@@ -124,12 +193,15 @@ extern "C" int sift3d_fuse_vote(int device, int32_t K, const uint16_t *const *u,
     return SIFT3D_OK;
 }
 
-extern "C" int sift3d_fuse_labels(int device, const float *target, int64_t nx, int64_t ny, int64_t nz, const float target_vox2key[16], int32_t K,
-                                  const sift3d_fuse_atlas *atlases, const sift3d_fuse_params *pp, uint32_t *words, sift3d_fuse_report *rep, char *err,
-                                  int64_t err_len)
+/* The stage.  search 0: section 7j, every atlas votes with the label and the weight it has at the voxel; 1 .. 3: section 7k, with
+ * those of its best candidate within that radius, and srep (may be NULL) says how far the atlases moved. */
+static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, int64_t nz, const float target_vox2key[16], int32_t K,
+                      const sift3d_fuse_atlas *atlases, const sift3d_fuse_params *pp, int32_t search, uint32_t *words, sift3d_fuse_report *rep,
+                      sift3d_fuse_search_report *srep, char *err, int64_t err_len)
 {
     if (err && err_len > 0) err[0] = 0;
     if (rep) memset(rep, 0, sizeof *rep);
+    if (srep) memset(srep, 0, sizeof *srep);
     sift3d_fuse_params p;
     if (pp) p = *pp;
     else sift3d_fuse_defaults(&p);
@@ -137,6 +209,8 @@ extern "C" int sift3d_fuse_labels(int device, const float *target, int64_t nx, i
     if (!target || !atlases || !words) return call_fail(err, err_len, SIFT3D_ERR_ARG, "null pointer");
     if (p.power < 0 || p.power > 2) return call_fail(err, err_len, SIFT3D_ERR_ARG, "the power must be 0, 1 or 2");
     const char *why = check_weights(nx, ny, nz, p.block, p.metric);
+    if (!why) why = check_search(p.block, search);
+    if (!why && search > 0 && p.power == 0) why = "a search needs weights to search by: the power must be 1 or 2";
     if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%s", why);
     const int64_t n = nx * ny * nz;
     if (p.max_voxels < 1 || n > p.max_voxels / K)
@@ -157,17 +231,26 @@ extern "C" int sift3d_fuse_labels(int device, const float *target, int64_t nx, i
         if (a.field) nodes_max = std::max(nodes_max, (size_t)nodes_of(*a.field));
     }
     sift3d_fuse_report rp;
+    sift3d_fuse_search_report sp;
     memset(&rp, 0, sizeof rp);
+    memset(&sp, 0, sizeof sp);
+    sp.radius = search;
     if (!sift3d_blockmatch_range(target, n, &rp.lo, &rp.hi))
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the target has no two distinct finite values: nothing to quantise");
     const size_t nv = (size_t)n;
     device_call dc(err, err_len);
-    float *d_w, *d_m;
+    float *d_w, *d_m, *d_pick = nullptr;
     short *d_qt, *d_qw;
-    unsigned short *d_u, *d_lab;
+    unsigned short *d_u, *d_lab, *d_shift = nullptr;
     unsigned *d_words;
     float4 *d_nodes;
+    std::vector<unsigned short> hs; /* one atlas' shift plane, for the search report */
     DEVCHK(dc, dc.open(device));
+    if (search > 0 && (dc.alloc(&d_pick, nv) != hipSuccess || dc.alloc(&d_shift, nv) != hipSuccess)) {
+        (void)hipGetLastError();
+        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", 6 * nv, device);
+    }
+    if (search > 0) hs.resize(nv);
     if (dc.alloc(&d_w, nv) != hipSuccess || dc.alloc(&d_m, nm_max) != hipSuccess || dc.alloc(&d_qt, nv) != hipSuccess || dc.alloc(&d_qw, nv) != hipSuccess ||
         dc.alloc(&d_u, nv * K) != hipSuccess || dc.alloc(&d_lab, nv * K) != hipSuccess || dc.alloc(&d_words, 2 * nv) != hipSuccess ||
         dc.alloc(&d_nodes, nodes_max) != hipSuccess) {
@@ -211,7 +294,7 @@ extern "C" int sift3d_fuse_labels(int device, const float *target, int64_t nx, i
             r.warp_ms += ms;
             DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
             DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, n, (double)wlo, (double)whi, d_qw));
-            DEVCHK(dc, sift3d_launch_fuse_weight(dc.s, d_qt, d_qw, nx, ny, nz, p.block, ncc, 0, d_u + nv * k));
+            if (search == 0) DEVCHK(dc, sift3d_launch_fuse_weight(dc.s, d_qt, d_qw, nx, ny, nz, p.block, ncc, 0, d_u + nv * k));
             DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
             DEVCHK(dc, dc.sync());
             DEVCHK(dc, dc.elapsed_ms(&r.weight_ms));
@@ -219,10 +302,24 @@ extern "C" int sift3d_fuse_labels(int device, const float *target, int64_t nx, i
         DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
         DEVCHK(dc, warp(a.labels, 1));
         DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
-        DEVCHK(dc, sift3d_launch_fuse_label(dc.s, d_w, n, !weigh, d_lab + nv * k, d_u + nv * k));
+        if (search == 0 || !weigh) DEVCHK(dc, sift3d_launch_fuse_label(dc.s, d_w, n, !weigh, d_lab + nv * k, d_u + nv * k));
         DEVCHK(dc, dc.sync());
         DEVCHK(dc, dc.elapsed_ms(&ms));
         r.warp_ms += ms;
+        if (search > 0 && weigh) {
+            /* d_w holds the warped labels: the search picks among them, and the picked ones go the way the labels went.  An atlas
+             * with an empty range has nothing to search by and has voted above as in section 7j: u = 0 and the shift 0. */
+            sift3d_fuse_search_atlas_report &sr = sp.atlas[k];
+            DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+            DEVCHK(dc, sift3d_launch_fuse_search(dc.s, d_qt, d_qw, d_w, nx, ny, nz, p.block, search, ncc, 0, d_u + nv * k, d_shift, d_pick));
+            DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+            DEVCHK(dc, sift3d_launch_fuse_label(dc.s, d_pick, n, 0, d_lab + nv * k, d_u + nv * k));
+            DEVCHK(dc, dc.download(hs.data(), d_shift, nv));
+            DEVCHK(dc, dc.sync());
+            DEVCHK(dc, dc.elapsed_ms(&sr.search_ms));
+            r.weight_ms += sr.search_ms;
+            sift3d_fuse_shift_stats(search, hs.data(), n, &sr.moved, &sr.dist2_sum);
+        }
     }
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
     DEVCHK(dc, sift3d_launch_fuse_vote(dc.s, d_u, d_lab, K, n, p.power, d_words));
@@ -251,5 +348,20 @@ extern "C" int sift3d_fuse_labels(int device, const float *target, int64_t nx, i
         r.mean_u = r.voters > 0 ? (double)sum / (double)r.voters : 0.0;
     }
     if (rep) *rep = rp;
+    if (srep) *srep = sp;
     return SIFT3D_OK;
+}
+
+extern "C" int sift3d_fuse_labels(int device, const float *target, int64_t nx, int64_t ny, int64_t nz, const float target_vox2key[16], int32_t K,
+                                  const sift3d_fuse_atlas *atlases, const sift3d_fuse_params *pp, uint32_t *words, sift3d_fuse_report *rep, char *err,
+                                  int64_t err_len)
+{
+    return fuse_stage(device, target, nx, ny, nz, target_vox2key, K, atlases, pp, 0, words, rep, nullptr, err, err_len);
+}
+
+extern "C" int sift3d_fuse_labels_search(int device, const float *target, int64_t nx, int64_t ny, int64_t nz, const float target_vox2key[16], int32_t K,
+                                         const sift3d_fuse_atlas *atlases, const sift3d_fuse_params *pp, int32_t search, uint32_t *words,
+                                         sift3d_fuse_report *rep, sift3d_fuse_search_report *srep, char *err, int64_t err_len)
+{
+    return fuse_stage(device, target, nx, ny, nz, target_vox2key, K, atlases, pp, search, words, rep, srep, err, err_len);
 }

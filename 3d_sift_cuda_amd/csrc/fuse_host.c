@@ -1,6 +1,7 @@
 /*
- * fuse_host.c -- host arithmetic of the label fusion: the default parameters, the similarity of a patch from
- * its six sums, the check of a label volume and the overlap of two.  Linked into libsift3d_hip.so (fuse_api.hip uses it) and into
+ * fuse_host.c -- host arithmetic of the label fusion (DESIGN.md sections 7j and 7k): the default parameters, the similarity of a patch
+ * from its six sums, the check of a label volume, the overlap of two, and the code of a search shift, its way back and the counts
+ * over a plane of codes.  Linked into libsift3d_hip.so (fuse_api.hip uses it) and into
  * libsift3d_host.so (no GPU needed).
  */
 #include <math.h>
@@ -58,4 +59,42 @@ int64_t sift3d_label_overlap(const float *a, const float *b, int64_t n, int64_t 
     int64_t present = 0;
     for (int l = 0; l < 65536; l++) present += count_a[l] > 0 || count_b[l] > 0;
     return present;
+}
+
+uint16_t sift3d_fuse_shift_code(int32_t r, int32_t tx, int32_t ty, int32_t tz)
+{
+    if (r < 0 || r > SIFT3D_FUSE_MAX_SEARCH || tx < -r || tx > r || ty < -r || ty > r || tz < -r || tz > r) return SIFT3D_FUSE_NO_SHIFT;
+    const int32_t s = 2 * r + 1;
+    return (uint16_t)(((tz + r) * s + (ty + r)) * s + (tx + r));
+}
+
+int sift3d_fuse_shift_of(int32_t r, uint32_t code, int32_t t[3])
+{
+    if (!t || r < 0 || r > SIFT3D_FUSE_MAX_SEARCH) return -1;
+    const uint32_t s = 2 * (uint32_t)r + 1;
+    if (code >= s * s * s) return -1;
+    t[0] = (int32_t)(code % s) - r;
+    t[1] = (int32_t)(code / s % s) - r;
+    t[2] = (int32_t)(code / (s * s)) - r;
+    return 0;
+}
+
+int64_t sift3d_fuse_shift_stats(int32_t r, const uint16_t *shift, int64_t n, int64_t *moved, int64_t *dist2_sum)
+{
+    int64_t voters = 0, mv = 0, d2 = 0;
+    if (moved) *moved = 0;
+    if (dist2_sum) *dist2_sum = 0;
+    if (!shift || n < 0 || r < 0 || r > SIFT3D_FUSE_MAX_SEARCH) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        int32_t t[3];
+        if (shift[i] == SIFT3D_FUSE_NO_SHIFT) continue;
+        if (sift3d_fuse_shift_of(r, shift[i], t) != 0) return -1;
+        const int64_t d = (int64_t)t[0] * t[0] + (int64_t)t[1] * t[1] + (int64_t)t[2] * t[2];
+        voters++;
+        mv += d > 0;
+        d2 += d;
+    }
+    if (moved) *moved = mv;
+    if (dist2_sum) *dist2_sum = d2;
+    return voters;
 }

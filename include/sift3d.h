@@ -1125,6 +1125,67 @@ int64_t sift3d_fuse_check_labels(const float *labels, int64_t n);
  * Returns the number of labels that occur in either volume, or -1 where sift3d_fuse_check_labels refuses one of them. */
 int64_t sift3d_label_overlap(const float *a, const float *b, int64_t n, int64_t *count_a, int64_t *count_b, int64_t *count_both);
 
+/* ---- the local search of the label fusion (featFuse -s; beyond the reference) ------------------------------------------------
+ * DESIGN.md section 7k states the contract; tests/fuse_search_oracle.c restates it as a serial brute force.
+ *
+ * Section 7j lets atlas k vote at voxel x with the label it carries at x.  With a search radius r (0 .. SIFT3D_FUSE_MAX_SEARCH,
+ * b + r <= SIFT3D_BLOCKMATCH_MAX_B) it votes with the label and the weight of its best-matching nearby patch.  Inputs as above: qT and
+ * qW_k on the target grid (-1: not finite), M_k the warped labels, the half-width b.
+ * Candidates at x: the shifts t in [-r, r]^3 where x + t lies inside the volume and M_k(x + t) is finite (without labels, as
+ * sift3d_fuse_search may be called: every shift inside the volume).
+ * Sums per candidate: over the v in [-b, b]^3 where x + v and x + t + v lie inside the volume, qT(x + v) >= 0 and
+ * qW(x + t + v) >= 0: the six integers above with qW taken at x + t + v; the same bounds.
+ * Similarity: u(x, t) = sift3d_fuse_similarity(metric, the six sums).
+ * Choice: t* is the candidate of the largest u; ties go to the smallest |t|^2, then the smallest tz, then ty, then tx.  A flat region
+ * keeps t = 0, r = 0 is the rule above exactly, and a candidate with u = 0 is still a candidate.
+ * Result per voxel and atlas: u* = u(x, t*); the picked label M_k(x + t*); the shift code
+ * ((tz + r)(2r + 1) + (ty + r))(2r + 1) + (tx + r) as a uint16.  No candidate: the atlas does not vote at x, u = 0xffff, the picked
+ * label is NaN and the code SIFT3D_FUSE_NO_SHIFT.
+ * Vote: as above, over the K planes of u* and picked labels. */
+#define SIFT3D_FUSE_MAX_SEARCH 3
+#define SIFT3D_FUSE_NO_SHIFT 0xffffu
+
+typedef struct {
+    int64_t moved;     /* voters with t* != 0 */
+    int64_t dist2_sum; /* sum of |t*|^2 over the voters, exact */
+    double search_ms;  /* device time: fuse_search_kernel */
+} sift3d_fuse_search_atlas_report;
+
+typedef struct {
+    int32_t radius; /* the search the stage ran with */
+    int32_t reserved;
+    sift3d_fuse_search_atlas_report atlas[SIFT3D_FUSE_MAX_ATLASES];
+} sift3d_fuse_search_report;
+
+/* fuse_search_kernel alone: T, W and the optional warped labels (on T's grid) host arrays; u and shift one uint16 per voxel; picked
+ * one float per voxel (NaN: no vote), which feeds sift3d_fuse_vote as it is.  labels NULL: every shift inside the volume is a
+ * candidate, picked is not written and may be NULL.  w_range as for sift3d_fuse_weights; a W without a range counts as not finite
+ * everywhere (u = 0, every tie to the smallest shift).  generic: 0 the kernel's form with b and r at compile time where one exists
+ * (b = 2, r = 1 .. 3), anything else its form for any b, r (same words).  SIFT3D_ERR_ARG with text: what sift3d_fuse_weights
+ * refuses, r outside 0 .. 3, b + r above 6, a label that sift3d_fuse_vote would refuse. */
+int sift3d_fuse_search(int device, const float *t, const float *w, const float *labels, int64_t nx, int64_t ny, int64_t nz, int32_t b, int32_t r,
+                       int32_t metric, const float w_range[2], int32_t generic, uint16_t *u, uint16_t *shift, float *picked, double *kernel_ms,
+                       char *err, int64_t err_len);
+/* The stage with a search radius.  search 0: the words and the report of sift3d_fuse_labels.  search 1 .. 3: every atlas streams
+ * through as there, and after its labels are warped fuse_search_kernel writes its u* plane and its picked labels, which
+ * fuse_label_kernel turns into its label plane; the vote is unchanged.  rep's voters, support and mean_u are those of the chosen
+ * planes, its weight_ms the quantisation plus the search kernel.  srep (may be NULL): per atlas moved, dist2_sum and search_ms.  An
+ * atlas whose range is empty under NCC has nothing to search by and votes as with search 0.  The planes stay at 4 bytes per voxel and
+ * atlas; the picked labels (4 bytes per voxel) and the shift plane (2 bytes per voxel) are one atlas' at a time, the shift plane
+ * kept only until that atlas' counts are taken.  SIFT3D_ERR_ARG with text: what sift3d_fuse_labels refuses, a search outside
+ * 0 .. 3, block + search above 6, a search with power 0 (without weights there is nothing to search by). */
+int sift3d_fuse_labels_search(int device, const float *target, int64_t nx, int64_t ny, int64_t nz, const float target_vox2key[16], int32_t K,
+                              const sift3d_fuse_atlas *atlases, const sift3d_fuse_params *p, int32_t search, uint32_t *words, sift3d_fuse_report *rep,
+                              sift3d_fuse_search_report *srep, char *err, int64_t err_len);
+/* Host helpers (also in libsift3d_host.so).
+ * The code of the shift (tx, ty, tz) under the radius r; SIFT3D_FUSE_NO_SHIFT for r outside 0 .. 3 or a component outside -r .. r. */
+uint16_t sift3d_fuse_shift_code(int32_t r, int32_t tx, int32_t ty, int32_t tz);
+/* The way back: t = (tx, ty, tz); -1 for a code that is none under r (SIFT3D_FUSE_NO_SHIFT among them), else 0. */
+int sift3d_fuse_shift_of(int32_t r, uint32_t code, int32_t t[3]);
+/* Over a plane of n codes: the voters (codes other than SIFT3D_FUSE_NO_SHIFT; returned), those with a shift other than 0 and the sum
+ * of |t|^2; -1 for a code that is none under r. */
+int64_t sift3d_fuse_shift_stats(int32_t r, const uint16_t *shift, int64_t n, int64_t *moved, int64_t *dist2_sum);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
