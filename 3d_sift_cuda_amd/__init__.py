@@ -34,6 +34,7 @@ FEATEXTRACT = os.path.join(CSRC, "_build", "featExtract")
 FEATRESAMPLE = os.path.join(CSRC, "_build", "featResample")
 FEATCOMPOSE = os.path.join(CSRC, "_build", "featCompose")
 FEATFUSE = os.path.join(CSRC, "_build", "featFuse")
+FEATOVERLAP = os.path.join(CSRC, "_build", "featOverlap")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 6   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -189,6 +190,8 @@ def hip_lib():
     _sig(L.sift3d_fuse_labels, I, I, P, I64, I64, I64, P, C.c_int32, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_fuse_search, I, I, P, P, P, I64, I64, I64, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_fuse_labels_search, I, I, P, I64, I64, I64, P, C.c_int32, P, P, C.c_int32, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_distance_map, I, I, P, I64, I64, I64, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_surface_distances, I, P, P, I64, I64, I64, P, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -261,6 +264,9 @@ def host_lib():
     _sig(L.sift3d_fuse_shift_of, I, C.c_int32, C.c_uint32, P)
     _sig(L.sift3d_fuse_shift_stats, I64, C.c_int32, P, I64, P, P)
     _sig(L.sift3d_label_overlap, I64, P, P, I64, P, P, P)
+    _sig(L.sift3d_surface_defaults, None, P)
+    _sig(L.sift3d_spacing_um, I, F, P)
+    _sig(L.sift3d_surface_stats, None, P, I64, P, I64, P)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -1412,6 +1418,89 @@ def fuse_search(target, warped, labels=None, block=2, radius=1, metric="ssd", w_
     _call("sift3d_fuse_search", int(device), t.ctypes.data, w.ctypes.data, _ptr(lb), nx, ny, nz, int(block), int(radius),
           int(BLOCKMATCH_METRICS.get(metric, metric)), wr, int(generic), u.ctypes.data, shift.ctypes.data, _ptr(picked), C.byref(ms))
     return (u, shift, picked, ms.value) if return_ms else (u, shift, picked)
+
+
+# ---- exact Euclidean distance map and surface distances between label volumes (featFuse -m, featOverlap), DESIGN.md section 7l ----
+EDT_MAX_EXTENT, EDT_MAX_SPACING_UM, EDT_MAX_VOXELS, EDT_NONE = 4096, 65535, 1 << 30, 0xffffffffffffffff
+
+
+class SurfaceParams(C.Structure):
+    """sift3d_surface_params"""
+    _fields_ = [("first_label", C.c_int32), ("max_labels", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SurfaceRecord(C.Structure):
+    """sift3d_surface_record"""
+    _fields_ = [("label", C.c_int32), ("reserved", C.c_int32), ("voxels_a", C.c_int64), ("voxels_b", C.c_int64), ("n_a", C.c_int64), ("n_b", C.c_int64),
+                ("max_ab", C.c_uint64), ("max_ba", C.c_uint64), ("p95_ab", C.c_uint64), ("p95_ba", C.c_uint64), ("sum_ab", C.c_double),
+                ("sum_ba", C.c_double), ("hausdorff_mm", C.c_double), ("hd95_mm", C.c_double), ("assd_mm", C.c_double)]
+
+
+def surface_params(**kw):
+    """sift3d_surface_defaults, then the given fields (first_label, max_labels, device)"""
+    p = SurfaceParams()
+    host_lib().sift3d_surface_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(SurfaceParams._fields_):
+            raise ValueError("no surface distance parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def spacing_um(mm):
+    """sift3d_spacing_um: a voxel size in mm as micrometres, or None where it is refused (not finite, or outside 1 .. 65535 um)"""
+    um = C.c_uint32(0)
+    return None if host_lib().sift3d_spacing_um(float(mm), C.byref(um)) != 0 else int(um.value)
+
+
+def _surface_record_dict(r):
+    return {name: getattr(r, name) for name, _ in SurfaceRecord._fields_ if name != "reserved"}
+
+
+def surface_stats(list_ab, list_ba):
+    """sift3d_surface_stats of the two lists of squared distances (um^2) of one label: a dict of the record's fields but the label
+    and its voxel counts.  The lists are copied, not sorted in place."""
+    ab, ba = np.array(list_ab, np.uint64).reshape(-1), np.array(list_ba, np.uint64).reshape(-1)
+    r = SurfaceRecord()
+    host_lib().sift3d_surface_stats(ab.ctypes.data, ab.size, ba.ctypes.data, ba.size, C.byref(r))
+    return {k: v for k, v in _surface_record_dict(r).items() if k not in ("label", "voxels_a", "voxels_b")}
+
+
+def _spacing3(spacing):
+    sp = [int(v) for v in spacing]
+    if len(sp) != 3 or any(v < 0 or v > 0xffffffff for v in sp):
+        raise ValueError("a spacing is three unsigned integers: micrometres along x, y, z")
+    return (C.c_uint32 * 3)(*sp)
+
+
+def distance_map(sites, spacing=(1000, 1000, 1000), device=0, return_ms=False):
+    """sift3d_distance_map: sites (nz, ny, nx), non-zero where a site is; spacing: micrometres along x, y, z.  Returns the squared
+    distance to the nearest site in um^2, uint64 (nz, ny, nx), EDT_NONE everywhere where there is no site.  return_ms=True returns
+    (d2, (total, x, y, z) device ms of the three passes)."""
+    s = np.ascontiguousarray(np.asarray(sites) != 0, np.uint8)
+    if s.ndim != 3:
+        raise ValueError("sites is a volume (nz, ny, nx)")
+    nz, ny, nx = s.shape
+    d2 = np.zeros(s.shape, np.uint64)
+    ms = (C.c_double * 4)()
+    _call("sift3d_distance_map", int(device), s.ctypes.data, nx, ny, nz, _spacing3(spacing), d2.ctypes.data, ms)
+    return (d2, tuple(ms)) if return_ms else d2
+
+
+def surface_distances(a, b, spacing=(1000, 1000, 1000), return_ms=False, **params):
+    """sift3d_surface_distances of two float32 label volumes (nz, ny, nx) on one grid: a list of dicts, one per label >= first_label
+    that either volume has, in ascending order (the fields of sift3d_surface_record).  params: fields of surface_params.
+    return_ms=True returns (records, the device ms of the transform kernels)."""
+    a, b = _f32(a), _f32(b)
+    if a.shape != b.shape or a.ndim != 3:
+        raise ValueError("the label volumes are (nz, ny, nx) and of one shape")
+    nz, ny, nx = a.shape
+    p = surface_params(**params)
+    rec = (SurfaceRecord * max(int(p.max_labels), 1))()
+    n, ms = C.c_int32(0), C.c_double(0.0)
+    _call("sift3d_surface_distances", a.ctypes.data, b.ctypes.data, nx, ny, nz, _spacing3(spacing), C.byref(p), rec, C.byref(n), C.byref(ms))
+    out = [_surface_record_dict(rec[k]) for k in range(n.value)]
+    return (out, ms.value) if return_ms else out
 
 
 def _map12(m):

@@ -13,13 +13,15 @@
  * Writes <output labels> (float32, the target's geometry, -f's value where no atlas votes), <output labels>.conf.nii (the winning
  * label's share of the vote, 0 .. 1) and <output labels>.fuse.txt (the parameters, the report, the voxels per label and, with -t,
  * the Dice overlap per label with the truth and their mean over the labels either volume has; with -s the radius and per atlas the
- * voxels where it voted from another place and the mean squared distance of its votes).
+ * voxels where it voted from another place and the mean squared distance of its votes; with -t -m the surface distances per label
+ * to the truth in mm: Hausdorff, its 95th percentile and the average symmetric surface distance).
  */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include "label_report.h"
 #include "nifti_min.h"
 #include "sift3d.h"
 
@@ -45,6 +47,8 @@ static void print_options(void)
     printf("               half-width + radius at most %d, and not with -p0 (default: no search).\n", SIFT3D_BLOCKMATCH_MAX_B);
     printf("  -f<value>  : value of output voxels where no atlas votes (default 0).\n");
     printf("  -t <truth> : label image on the target's grid: also write the Dice overlap per label to <output labels>.fuse.txt.\n");
+    printf("  -m         : with -t: also write the surface distances per label to the truth (Hausdorff, 95th percentile, average\n");
+    printf("               symmetric), in mm by the target's voxel size.\n");
     printf("  -d[0-9]    : set device id to be used.\n");
 }
 
@@ -78,9 +82,12 @@ static int bad_option(const char *what, const char *arg)
 }
 
 /* <out>.fuse.txt */
+/* spacing_um: NULL, or the target's voxel size for the distance block of -m; -3 with the reason in err where that block fails */
 static int write_report(const char *out_path, int K, const sift3d_fuse_params *p, const sift3d_fuse_report *rep, const sift3d_fuse_search_report *srep,
-                        int64_t n, const float *fused, const float *truth)
+                        const nifti_min_image *target, const float *fused, const float *truth, const uint32_t *spacing_um, int device, char *err,
+                        size_t err_len)
 {
+    const int64_t n = (int64_t)target->nx * target->ny * target->nz;
     int64_t *ca = (int64_t *)malloc(sizeof(int64_t) * 3 * 65536);
     char *path = (char *)malloc(strlen(out_path) + 16);
     if (!ca || !path) return -1;
@@ -112,26 +119,18 @@ static int write_report(const char *out_path, int K, const sift3d_fuse_params *p
     fprintf(o, "# label voxels\n");
     for (int l = 0; l < 65536; l++)
         if (ca[l] > 0) fprintf(o, "%d\t%lld\n", l, (long long)ca[l]);
-    if (truth) {
-        double sum = 0;
-        int64_t present = 0;
-        fprintf(o, "# label fused truth both dice\n");
-        for (int l = 0; l < 65536; l++)
-            if (ca[l] > 0 || cb[l] > 0) {
-                const double dice = (double)(2 * cboth[l]) / (double)(ca[l] + cb[l]);
-                fprintf(o, "%d\t%lld\t%lld\t%lld\t%.6f\n", l, (long long)ca[l], (long long)cb[l], (long long)cboth[l], dice);
-                sum += dice;
-                present++;
-            }
-        fprintf(o, "# mean dice %.6f over %lld labels\n", present > 0 ? sum / (double)present : 0.0, (long long)present);
-    }
+    if (truth) label_report_dice(o, ca, cb, cboth);
     free(ca);
+    if (truth && spacing_um && label_report_distances(o, device, fused, truth, target->nx, target->ny, target->nz, spacing_um, 1, err, err_len) != 0) {
+        fclose(o);
+        return -3;
+    }
     return fclose(o);
 }
 
 int main(int argc, char **argv)
 {
-    int device = 0, world_mode = 0;
+    int device = 0, world_mode = 0, measure = 0;
     int32_t search = 0;
     const char *truth_path = NULL;
     sift3d_fuse_params p;
@@ -175,6 +174,10 @@ int main(int argc, char **argv)
             if (argv[arg][2] != 0 || arg + 1 >= argc) return bad_option("-t needs a label image", argv[arg]);
             truth_path = argv[++arg];
             break;
+        case 'm':
+            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            measure = 1;
+            break;
         case 'd':
             if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count())
                 return bad_option("unknown device", argv[arg] + 2);
@@ -187,6 +190,7 @@ int main(int argc, char **argv)
     }
     if (search > 0 && p.power == 0) return bad_option("a search needs weights to search by", "-s with -p0");
     if (search > 0 && p.block + search > SIFT3D_BLOCKMATCH_MAX_B) return bad_option("the patch half-width plus the search radius must not exceed 6", "-b with -s");
+    if (measure && !truth_path) return bad_option("the surface distances are taken to a truth", "-m without -t");
     const int rest = argc - arg - 2;
     if (rest < 4 || rest % 4 != 0 || rest / 4 > SIFT3D_FUSE_MAX_ATLASES) {
         if (rest > 0 && rest % 4 != 0) printf("Error: every atlas takes four arguments: <atlas image> <atlas labels> <atlas.trans.txt> <atlas.field.nii|->\n");
@@ -206,6 +210,12 @@ int main(int argc, char **argv)
     }
     if (truth_path && (nifti_min_read(truth_path, &truth) != 0 || truth.nx != target.nx || truth.ny != target.ny || truth.nz != target.nz)) {
         printf("Error: could not read input file, or it is not on the target's grid: %s\n", truth_path);
+        return -1;
+    }
+    char err[512] = "";
+    uint32_t spacing_um[3];
+    if (measure && label_report_spacing(target.dx, target.dy, target.dz, spacing_um, err, sizeof err) != 0) {
+        printf("Error: %s: %s\n", err, target_path);
         return -1;
     }
     float tv[16];
@@ -266,7 +276,6 @@ int main(int argc, char **argv)
         printf("Error: could not fuse, insufficient memory.\n");
         return -1;
     }
-    char err[512] = "";
     sift3d_fuse_report rep;
     sift3d_fuse_search_report srep;
     const int frc = search > 0 ? sift3d_fuse_labels_search(device, target.data, target.nx, target.ny, target.nz, tv, K, atlas, &p, search, words, &rep, &srep, err,
@@ -287,9 +296,11 @@ int main(int argc, char **argv)
     }
     for (int64_t i = 0; i < n; i++)
         if (words[2 * i] & SIFT3D_FUSE_NONE) labels[i] = NAN;
-    const int wrc = write_report(out_path, K, &p, &rep, search > 0 ? &srep : NULL, n, labels, truth_path ? truth.data : NULL);
+    const int wrc = write_report(out_path, K, &p, &rep, search > 0 ? &srep : NULL, &target, labels, truth_path ? truth.data : NULL,
+                                 measure ? spacing_um : NULL, device, err, sizeof err);
     if (wrc != 0) {
-        if (wrc == -2) printf("Error: a voxel of the truth is neither non-finite nor an integer 0 .. 65535: %s\n", truth_path);
+        if (wrc == -3) printf("Error: could not take the surface distances: %s\n", err);
+        else if (wrc == -2) printf("Error: a voxel of the truth is neither non-finite nor an integer 0 .. 65535: %s\n", truth_path);
         else printf("Error: could not write the report of: %s\n", out_path);
         return -1;
     }

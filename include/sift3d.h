@@ -1186,6 +1186,66 @@ int sift3d_fuse_shift_of(int32_t r, uint32_t code, int32_t t[3]);
  * of |t|^2; -1 for a code that is none under r. */
 int64_t sift3d_fuse_shift_stats(int32_t r, const uint16_t *shift, int64_t n, int64_t *moved, int64_t *dist2_sum);
 
+/* ---- exact Euclidean distance map and surface distances between label volumes (featFuse -m, featOverlap; beyond the reference) ----
+ * DESIGN.md section 7l states the contract; tests/edt_oracle.c restates it as a serial brute force.
+ *
+ * Distance map.  sites: nx ny nz uint8 flags (x fastest, non-zero: a site); spacing_um: three integers, micrometres per voxel along
+ * x, y, z.  Extents 1 .. SIFT3D_EDT_MAX_EXTENT each and at most 2^30 voxels in all; spacings 1 .. SIFT3D_EDT_MAX_SPACING_UM.
+ *   D2(x) = min over the sites s of (sx (x0 - s0))^2 + (sy (x1 - s1))^2 + (sz (x2 - s2))^2, in um^2, one uint64 per voxel;
+ * SIFT3D_EDT_NONE everywhere where there is no site.  The largest value is 3 (4095 * 65535)^2 < 2^58: every term is an exact integer
+ * and a minimum has no order, so the 64 bits do not depend on how they are found.
+ * Surface of the label l in a label volume (labels as in the fusion: non-finite is unlabelled, else an integer 0 .. 65535): the
+ * voxels that carry l and have a face neighbour that lies outside the volume or does not carry l.
+ * Surface distances of l between the volumes A and B on one grid: the list A->B holds, per surface voxel of l in A, the D2 of the
+ * map whose sites are the surface voxels of l in B; B->A likewise; n_a and n_b elements.  Each list is sorted ascending; then
+ *   max = the last element, p95 = the element at index (95 n + 99) / 100 - 1, sum = the sum of sqrt((double)d2) in ascending order,
+ *   hausdorff_mm = sqrt((double)max(max_ab, max_ba)) / 1000, hd95_mm = sqrt((double)max(p95_ab, p95_ba)) / 1000,
+ *   assd_mm = (sum_ab + sum_ba) / (double)(n_a + n_b) / 1000.
+ * A label that one of the volumes lacks (n_a = 0 or n_b = 0) has no distances: its integer fields are SIFT3D_EDT_NONE and its sums
+ * and derived values NaN. */
+#define SIFT3D_EDT_MAX_EXTENT 4096
+#define SIFT3D_EDT_MAX_SPACING_UM 65535u
+#define SIFT3D_EDT_MAX_VOXELS ((int64_t)1 << 30)
+#define SIFT3D_EDT_NONE UINT64_MAX
+
+typedef struct {
+    int32_t first_label; /* 1: the labels below are skipped (1 skips the background, 0 includes it) */
+    int32_t max_labels;  /* 64: with more labels to evaluate the stage is refused */
+    int32_t device;      /* 0 */
+    int32_t reserved;
+} sift3d_surface_params;
+
+typedef struct {
+    int32_t label;
+    int32_t reserved;
+    int64_t voxels_a, voxels_b;               /* voxels that carry the label */
+    int64_t n_a, n_b;                         /* of them surface voxels */
+    uint64_t max_ab, max_ba, p95_ab, p95_ba;  /* um^2 */
+    double sum_ab, sum_ba;                    /* um */
+    double hausdorff_mm, hd95_mm, assd_mm;
+} sift3d_surface_record;
+
+/* The transform alone on host arrays: d2 one uint64 per voxel.  kernel_ms (may be NULL): four values, the device time of the three
+ * passes together and of the x, y and z pass.  SIFT3D_ERR_ARG with text naming the argument: an extent outside 1 .. 4096, more than
+ * 2^30 voxels, a spacing outside 1 .. 65535; all checked before anything is allocated. */
+int sift3d_distance_map(int device, const uint8_t *sites, int64_t nx, int64_t ny, int64_t nz, const uint32_t spacing_um[3], uint64_t *d2,
+                        double kernel_ms[4], char *err, int64_t err_len);
+/* The stage: the labels >= first_label that occur in a or b, in ascending order, one record each; records holds max_labels of them,
+ * *n_records how many were written.  The label planes are made once per volume; per label one launch marks both surfaces, then one
+ * transform and one gather per direction, and sift3d_surface_stats makes the record.  p NULL: defaults.  kernel_ms (may be NULL):
+ * the device time of the transform kernels.  SIFT3D_ERR_ARG with text: what sift3d_distance_map refuses, a voxel that
+ * sift3d_fuse_check_labels refuses (the volume and the voxel), more than max_labels labels (the count; nothing is dropped). */
+int sift3d_surface_distances(const float *a, const float *b, int64_t nx, int64_t ny, int64_t nz, const uint32_t spacing_um[3],
+                             const sift3d_surface_params *p, sift3d_surface_record *records, int32_t *n_records, double *kernel_ms, char *err,
+                             int64_t err_len);
+/* Host helpers (also in libsift3d_host.so). */
+void sift3d_surface_defaults(sift3d_surface_params *p);
+/* A voxel size in mm as micrometres: lroundf(mm * 1000); -1 for a value that is not finite or a result outside 1 .. 65535, else 0. */
+int sift3d_spacing_um(float mm, uint32_t *um);
+/* The two lists of one label into rec's n_a, n_b, integer and derived fields, as stated above; sorts the lists in place.  With
+ * n_a = 0 or n_b = 0 the lists are not read and may be NULL.  rec's label and voxel counts are left as they are. */
+void sift3d_surface_stats(uint64_t *list_ab, int64_t n_a, uint64_t *list_ba, int64_t n_b, sift3d_surface_record *rec);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
