@@ -169,6 +169,7 @@ def hip_lib():
     _sig(L.sift3d_hough_similarity, I, I, P, P, P, P, P, P, C.c_int32, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_match_keys, I, I, P, I64, P, I64, C.c_int32, P, C.c_char_p, I64)
     _sig(L.sift3d_get_level_slice, I, P, I, I, I64, P, P, P)
+    _sig(L.sift3d_get_dog_slice, I, P, I, I, I64, P, P, P)
     _sig(L.sift3d_resample_affine, I, I, P, I64, I64, I64, P, I64, I64, I64, P, I, F, P, C.c_char_p, I64)
     _sig(L.sift3d_resample_affine_dev, I, P, P, I64, I64, I64, P, I64, I64, I64, P, I, F)
     _sig(L.sift3d_guided_search_params, I, I, P, I64, P, I64, P, F, P, P, P, P, P, P, P, C.c_char_p, I64)
@@ -1722,6 +1723,7 @@ class Context:
         if not self._h:
             raise Sift3DError("sift3d_create%s(device=%d, %d x %d x %d) failed" % ("_slab" if slab else "", device, nx, ny, nz))
         self.device = device
+        self._shape = None   # (nz, ny, nx) of the volume last set, after its resize
 
     def set_tuning(self, knob, value):
         """sift3d_set_tuning: TUNE_* knobs (tests and A/B timing; no knob changes a result)."""
@@ -1821,6 +1823,7 @@ class Context:
         vol = _f32(vol)
         nz, ny, nx = vol.shape
         self._chk(self._L.sift3d_set_volume_resized(self._h, vol.ctypes.data, nx, ny, nz, int(resize)), "sift3d_set_volume_resized")
+        self._shape = self._resized((nz, ny, nx), resize)
 
     def reserve(self, n_extrema):
         self._chk(self._L.sift3d_reserve(self._h, int(n_extrema)), "sift3d_reserve")
@@ -1834,9 +1837,53 @@ class Context:
             part = vol[z0:z0 + n]
             self._chk(self._L.sift3d_set_volume_planes(self._h, part.ctypes.data, int(z0), int(n)), "sift3d_set_volume_planes")
         self._chk(self._L.sift3d_set_volume_end(self._h), "sift3d_set_volume_end")
+        self._shape = self._resized((nz, ny, nx), resize)
 
     def set_volume_dev(self, dev_ptr, nx, ny, nz):
         self._chk(self._L.sift3d_set_volume_dev(self._h, C.c_void_p(int(dev_ptr)), nx, ny, nz), "sift3d_set_volume_dev")
+        self._shape = (int(nz), int(ny), int(nx))
+
+    @staticmethod
+    def _resized(shape, resize):
+        return tuple(2 * d if resize > 0 else d // 2 if resize < 0 else d for d in shape)
+
+    # ---- the resident pyramid of the last detect / extract (tests) ----
+    def _slice(self, entry, octave, level, z, shape_yx):
+        out = np.empty(shape_yx, np.float32)
+        nx, ny = C.c_int64(0), C.c_int64(0)
+        self._chk(getattr(self._L, entry)(self._h, int(octave), int(level), int(z), out.ctypes.data, C.byref(nx), C.byref(ny)), entry)
+        assert (ny.value, nx.value) == tuple(shape_yx), (entry, octave, (ny.value, nx.value), shape_yx)
+        return out
+
+    def level_slice(self, octave, level, z, shape_yx):
+        """sift3d_get_level_slice: slice z of Gaussian level 0..4 of an octave, (ny_o, nx_o) float32."""
+        return self._slice("sift3d_get_level_slice", octave, level, z, shape_yx)
+
+    def dog_slice(self, octave, level, z, shape_yx):
+        """sift3d_get_dog_slice: slice z of DoG level 0..4 of an octave; raises Sift3DError ("... not stored ...") for a level
+        the last run did not store."""
+        return self._slice("sift3d_get_dog_slice", octave, level, z, shape_yx)
+
+    def pyramid(self):
+        """The resident pyramid as the last detect / extract left it, assembled slice by slice: one dict per octave of that run,
+        {"L": [L_0..L_4], "D": [D_0..D_4]}, each a (nz_o, ny_o, nx_o) float32 array -- or None for a DoG level the run did not
+        store (dog_slice).  Any other refusal raises."""
+        out = []
+        shape = self._shape
+        for o in range(int(self.timings()["n_octaves"])):
+            assert min(shape) > 2, (o, shape)
+            lv = {"L": [], "D": []}
+            for j in range(5):
+                lv["L"].append(np.stack([self.level_slice(o, j, z, shape[1:]) for z in range(shape[0])]))
+                try:
+                    lv["D"].append(np.stack([self.dog_slice(o, j, z, shape[1:]) for z in range(shape[0])]))
+                except Sift3DError as e:
+                    if "not stored" not in str(e):
+                        raise
+                    lv["D"].append(None)
+            out.append(lv)
+            shape = tuple(d // 2 for d in shape)
+        return out
 
     def detect(self, initial_image_scale=1.0):
         out, n = C.c_void_p(), C.c_int64(0)

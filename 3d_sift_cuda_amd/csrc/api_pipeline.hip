@@ -57,6 +57,7 @@ static int ensure_level_buffer(sift3d_ctx *c, float **buf)
 static int load_volume_prepare(sift3d_ctx *c, int64_t nx, int64_t ny, int64_t nz)
 {
     const int64_t xp = pitch_of(nx);
+    c->last_run.clear(); /* the levels of the last run are not this volume's */
     if (xp != nx && (c->pad_nx != nx || c->pad_ny != ny || c->pad_nz != nz)) {
         for (int i = 0; i < 6; i++)
             if (c->L[i]) HIPCHK(c, hipMemsetAsync(c->L[i], 0, sizeof(float) * (size_t)c->capTot, c->stream));
@@ -755,6 +756,7 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
     if (!c->has_volume) return set_err(c, SIFT3D_ERR_ARG, "no volume set (sift3d_set_volume)");
     HIPCHK(c, hipSetDevice(c->device));
     timing_begin(c);
+    c->last_run.clear();
     std::vector<octave_dims> oct = octave_list(c->nx, c->ny, c->nz);
     if (c->max_octaves > 0 && oct.size() > (size_t)c->max_octaves) oct.resize((size_t)c->max_octaves);
 
@@ -813,12 +815,7 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
     /* the filter that makes L_5 from L_4: the lazy form of D_4 applies it around the candidates of D_3 only */
     float next_taps[SIFT3D_MAX_TAPS];
     const int next_ntaps = sift3d_gauss_taps(s.extras[4], 0.01f, next_taps);
-    /* what differs from octave to octave in how its levels were made */
-    struct octave_run {
-        bool tiny_done; /* one workgroup built all its levels, every DoG level stored */
-        bool lazy;      /* D_0 and D_4 not stored (see the loop) */
-        float *d4tiny;  /* where its D_4 went then (or NULL) */
-    };
+    /* what differs from octave to octave in how its levels were made (octave_run: lazy, see the loop) */
     std::vector<octave_run> runs(oct.size());
     bool used_second = false;
     /* One chain of levels on the main stream.  (Round 3 tried two: the octaves after the first -- some sixty small launches
@@ -957,6 +954,7 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
         }
         c->last.n_octaves++;
     }
+    c->last_run = runs;
     HIPCHK(c, hipEventRecord(c->ev_oct[1], c->ex_stream)); /* the candidate counts are read on the main stream */
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_oct[1], 0));
     if (used_second) {

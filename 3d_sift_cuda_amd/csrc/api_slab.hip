@@ -227,3 +227,30 @@ extern "C" int sift3d_get_level_slice(sift3d_ctx *c, int octave, int level, int6
     if (ny_out) *ny_out = d.Y;
     return SIFT3D_OK;
 }
+
+/* One z-slice of a DoG level of the last run, dense like sift3d_get_level_slice's: D[level] at the octave's offset, or the small
+ * buffer of its own where the single-workgroup kernel left level 4.  A level that run did not store in full is refused. */
+extern "C" int sift3d_get_dog_slice(sift3d_ctx *c, int octave, int level, int64_t z, float *out, int64_t *nx_out, int64_t *ny_out)
+{
+    if (!c || !out) return SIFT3D_ERR_ARG;
+    NEED_LEVELS(c);
+    if (!c->has_volume || c->last_run.empty())
+        return set_err(c, SIFT3D_ERR_ARG, "DoG levels not stored: no sift3d_detect / sift3d_extract since the volume was set");
+    std::vector<octave_dims> oct = octave_list(c->nx, c->ny, c->nz);
+    if (octave < 0 || (size_t)octave >= oct.size() || (size_t)octave >= c->last_run.size() || level < 0 || level > 4)
+        return set_err(c, SIFT3D_ERR_ARG, "no DoG level %d of octave %d", level, octave);
+    const octave_dims &d = oct[(size_t)octave];
+    const octave_run &ru = c->last_run[(size_t)octave];
+    if (z < 0 || z >= d.Z) return set_err(c, SIFT3D_ERR_ARG, "slice %lld outside 0..%lld", (long long)z, (long long)d.Z - 1);
+    const float *src = c->D[level] ? c->D[level] + d.off : nullptr;
+    if (ru.lazy && (level == 0 || level == 4)) src = nullptr;
+    if (ru.tiny_done && level == 4) src = ru.d4tiny;
+    if (!src) return set_err(c, SIFT3D_ERR_ARG, "DoG level %d of octave %d not stored by the last run", level, octave);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy2DAsync(out, sizeof(float) * (size_t)d.X, src + z * d.XP * d.Y, sizeof(float) * (size_t)d.XP,
+                               sizeof(float) * (size_t)d.X, (size_t)d.Y, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nx_out) *nx_out = d.X;
+    if (ny_out) *ny_out = d.Y;
+    return SIFT3D_OK;
+}

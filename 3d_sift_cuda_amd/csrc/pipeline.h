@@ -110,6 +110,13 @@ static inline void octave_level_rows(sift3d_level rows[3], const float *const L[
     }
 }
 
+/* how an octave's levels were made by a run of the pipeline: what differs from octave to octave (run_pipeline) */
+struct octave_run {
+    bool tiny_done; /* one workgroup built all its levels, every DoG level stored */
+    bool lazy;      /* D_0 and D_4 not stored */
+    float *d4tiny;  /* where its D_4 went when tiny_done (or NULL) */
+};
+
 struct sift3d_ctx {
     int device;
     hipStream_t stream;
@@ -193,6 +200,8 @@ struct sift3d_ctx {
     int64_t nx, ny, nz;
     int64_t pad_nx, pad_ny, pad_nz; /* geometry the pad columns of the level buffers were last cleared for */
     bool has_volume;
+    std::vector<octave_run> last_run; /* per octave of the last sift3d_detect / sift3d_extract; empty: none since the volume was set
+                                       * (sift3d_get_dog_slice) */
     bool strict_extrema; /* the first extrema pass compares element by element (extrema_strict_kernel) instead of against a
                           * max / min reduction: set where a volume is set, when it holds a value the reductions would get wrong
                           * (sift3d_volume_needs_strict) */

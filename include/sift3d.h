@@ -243,6 +243,11 @@ int sift3d_extract(sift3d_ctx *ctx, float initial_image_scale, int desc_mode, fl
  * its size).  For the reference's debug output ./image.pgm: the middle slice of octave 0's first blurred level
  * (R/src_common/MultiScale.cpp:373-384), which the featExtract command line of this build writes as the reference does. */
 int sift3d_get_level_slice(sift3d_ctx *ctx, int octave, int level, int64_t z, float *out, int64_t *nx_out, int64_t *ny_out);
+/* The same for DoG level `level` (0..4; D_k = L_k - L_{k+1}) of the last sift3d_detect / sift3d_extract.  A level that run did
+ * not store in full is refused with a message that says "not stored": D_0 and D_4 of an octave whose neighbour levels were
+ * evaluated around the candidates only (SIFT3D_TUNE_LAZY_LEVELS), and every level while no run has followed the last
+ * sift3d_set_volume.  For tests, which hold the resident pyramid to the oracle's level by level. */
+int sift3d_get_dog_slice(sift3d_ctx *ctx, int octave, int level, int64_t z, float *out, int64_t *nx_out, int64_t *ny_out);
 /* Beyond the reference: stop the pyramid after n octaves.  n = 0 restores the reference's only
  * rule -- halve until a dimension is <= 2 (R/src_common/MultiScale.cpp:337,359-360) -- which is also the default; the
  * command line has no such option and never sets it.  Records are ordered octave-major, so a limited run returns

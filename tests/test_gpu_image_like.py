@@ -189,7 +189,9 @@ def test_fused_blur_shape_on_image_like(built, oracle, name):
 @pytest.mark.parametrize("shape", [(27, 29, 33), (21, 23, 18), (31, 17, 45)])
 @pytest.mark.parametrize("name", ["u8", "phantom", "nan_voxels", "nan_slab", "inf_voxels"])
 def test_small_odd_shapes_on_image_like(built, oracle, shape, name):
-    """Small odd shapes: the element-wise extrema kernel and the single-workgroup octaves."""
+    """Small odd shapes through the element-wise extrema kernel: candidates and records of octave 0 (0 to 12 candidates a
+    volume) and at most one candidate of octave 1.  The octaves one workgroup builds whole (octave 1 on) contribute nothing
+    else to these lists; their levels are compared in test_gpu_pyramid_levels.py::test_single_workgroup_octaves_from_octave_0."""
     vol = vol_of(built, name, shape)
     cand, recs = _candidates_and_records(built, oracle, vol, (0, 3) if name in il.RECORD_CLASSES else (), (-1.0,))
     same_candidates(cand, oracle.candidates(vol))

@@ -546,9 +546,11 @@ def test_context_reuse_across_row_lengths(built, oracle):
 @pytest.mark.parametrize("dims", [(100, 100, 100), (72, 72, 72), (168, 40, 36)])
 def test_context_reuse_pitched_coarse_octaves(built, oracle, dims):
     """Row lengths that ARE whole 16-byte vectors but whose coarser octaves are not (100 -> 50 -> pitch 52, 72 -> 36 ->
-    18 -> pitch 20, 168 -> 84 -> 42 -> pitch 44): the subsample writes the logical columns only, so the pad columns of a
-    coarse octave's first level must be zeroed by the pipeline itself.  A larger, dense, strongly offset volume goes
-    through the same context first so that those pad columns hold stale non-zero floats if the pipeline does not."""
+    18 -> pitch 20, 168 -> 84 -> 42 -> pitch 44), in a context a larger, dense, strongly offset volume went through first:
+    the records and the candidates are the oracle's.  That observes octaves 0 and 1 (these volumes have 20, 48 and 4
+    candidates in octave 1, one at 100^3 in octave 2 and none below), so of the pad columns the pipeline must zero itself --
+    the subsample writes the logical columns only -- it sees those of 100 -> 50.  The coarser ones (18 -> pitch 20, 42 -> 44)
+    are held to the oracle level by level in test_gpu_pyramid_levels.py::test_pitched_coarse_octaves_after_a_larger_volume."""
     big = vol_of(built, (128, 128, 128), 3) + np.float32(500.0)
     vol = vol_of(built, dims, 21)
     want, _ = oracle.extract(vol)
