@@ -1,7 +1,9 @@
 """Shared pieces of the block matching tests (test_blockmatch_cpu.py, test_gpu_blockmatch.py): the CPU oracle
 tests/blockmatch_oracle.c (built with cc -O2 -ffp-contract=off into a temporary directory and bound with ctypes), a numpy
 restatement of the block search, the stage of DESIGN.md section 7f restated on the CPU (oracle block search, FieldOracle's
-warp, fit and interpolation, the product's host helper for gates and samples), the volumes and the scenario."""
+warp, fit and interpolation, the product's host helper for gates and samples), the volumes and the scenario; and the volumes of 0
+and 1 alone on which the 32-bit sums of the quantised-integer kernels pass 2^31, with the quantiser's probe (test_gpu_integer_ends.py
+and the CPU suites of sections 7f, 7g, 7j and 7k)."""
 import ctypes as C
 
 import numpy as np
@@ -126,6 +128,146 @@ def volume(kind, shape, seed):
     z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
     v = np.sin(0.31 * x + 0.2 * y) * np.cos(0.23 * y - 0.11 * z) + 0.5 * np.sin(0.17 * z + 0.05 * x * y / max(nx, ny))
     return (1000.0 * v + rng.normal(0, 5.0, shape)).astype(np.float32)
+
+
+# ---- volumes at the ends of the integer sums -------------------------------------------------------------------------------------
+# Float32 volumes of the two finite values 0.0 and 1.0: the range is (0, 1) and the quantised values are 0 and 1023 exactly.  A 13^3
+# block of them reaches 13^3 1023^2 = 2 299 224 213, between 2^31 and 2^32 (test_gpu_integer_ends.py and the "oracle equals numpy"
+# tests of the CPU suites).
+SUM_MAX_B6 = 13 ** 3 * 1023 ** 2
+
+
+def binary(shape, seed):
+    """quantised volumes of 0 and 1023 alone: the widest sums and the extremes of A and the variances"""
+    rng = np.random.default_rng(seed)
+    qf = (1023 * rng.integers(0, 2, shape)).astype(np.int16)
+    qw = np.roll(qf, (0, 1, -1), (0, 1, 2))
+    flip = rng.random(shape) < 0.05
+    qw[flip] = 1023 - qw[flip]
+    return qf, qw
+
+
+def _holes(vols, shape, rng):
+    """NaN, +inf and -inf at a fraction 0.01 of the voxels of each volume.  fuse_cases.pair has 0.03; of two volumes with that many
+    no 13^3 patch keeps the 2052 voxel pairs that a sum of 2^31 takes (2052 x 1023^2 >= 2^31 > 2051 x 1023^2)."""
+    for vol in vols:
+        at = rng.random(shape) < 0.01
+        vol[at] = rng.choice(np.array([np.nan, np.inf, -np.inf], np.float32), int(at.sum()))
+
+
+def speckled_pair(shape, seed, holes=False, fraction=0.015):
+    """(F, W): F has a fraction 0.015 of its voxels at 1, W 0.985: nearly every voxel pair differs by the full range, and the
+    costs still vary from shift to shift; holes: NaN, +inf and -inf voxels scattered in both, as fuse_cases.pair has them.
+    fraction 0.033: the pairs of a 13^3 block that differ number 2056 +- 12, around the 2052 at which the cost is 2^31, so the
+    costs of one node's shifts lie on both sides of 2^31 (ends_pair's "straddling")"""
+    rng = np.random.default_rng(seed)
+    F = (rng.random(shape) < fraction).astype(np.float32)
+    W = (rng.random(shape) < 1.0 - fraction).astype(np.float32)
+    if holes:
+        _holes((F, W), shape, rng)
+    for vol in (F, W):
+        assert np.nanmin(np.where(np.isfinite(vol), vol, np.nan)) == 0.0 and np.nanmax(np.where(np.isfinite(vol), vol, np.nan)) == 1.0
+    return F, W
+
+
+def solid_pair(shape):
+    """(F, W): F is 0 and W is 1 but for one corner voxel in each that completes the range (F's last voxel is 1, W's first is 0).
+    F's lies in no unflagged node's block; W's lies in no window of solid_lattice's nodes.  Every cost there is the exact maximum
+    (2b + 1)^3 1023^2."""
+    F, W = np.zeros(shape, np.float32), np.ones(shape, np.float32)
+    F[-1, -1, -1], W[0, 0, 0] = 1.0, 0.0
+    return F, W
+
+
+def solid_lattice(shape, stride, b, r):
+    """lattice_numpy begun one voxel later along x: no window reaches the voxels of x = 0"""
+    first, count = lattice_numpy(shape, stride, b, r)
+    cx = (shape[2] - 2 - 2 * (b + r)) // stride + 1
+    assert cx >= 1
+    return (first[0] + 1, first[1], first[2]), (cx, count[1], count[2])
+
+
+def bright(shape, seed):
+    """a fraction 0.97 of the voxels at 1: sum q^2 of a 13^3 block exceeds 2^31 and the block is not flat"""
+    v = (np.random.default_rng(seed).random(shape) < 0.97).astype(np.float32)
+    assert v.min() == 0.0 and v.max() == 1.0
+    return v
+
+
+def bright_pair(shape, seed):
+    """(bright, bright moved by (0, 1, -1) voxels along (z, y, x) with 3 % of its voxels flipped): Sf2, Sww and Sfw exceed 2^31 at
+    b = 6, and Vf and Vw are small differences of large products"""
+    F = bright(shape, seed)
+    W = np.roll(F, (0, 1, -1), (0, 1, 2))
+    flip = np.random.default_rng(seed + 1000).random(shape) < 0.03
+    W[flip] = 1.0 - W[flip]
+    assert W.min() == 0.0 and W.max() == 1.0
+    return F, np.ascontiguousarray(W)
+
+
+def lattice3(shape):
+    """(F, W): the 3-D checkerboard (x + y + z) % 2 and its complement, which is the board moved by one voxel along any axis: the
+    six unit shifts all reach cost 0 and the zero shift has the largest cost"""
+    z, y, x = np.meshgrid(*(np.arange(n) for n in shape), indexing="ij")
+    F = ((x + y + z) % 2).astype(np.float32)
+    return F, (1.0 - F).astype(np.float32)
+
+
+def stripes(shape, axis):
+    """(F, W): stripes of period 2 along one axis (0: z, 1: y, 2: x) and their complement: only the shifts -1 and +1 along that axis
+    tie at cost 0 among the shortest"""
+    c = np.meshgrid(*(np.arange(n) for n in shape), indexing="ij")[axis]
+    F = (c % 2).astype(np.float32)
+    return F, (1.0 - F).astype(np.float32)
+
+
+def ends_pair(kind, shape, seed, own_scale=False):
+    """the pair of a family by name (speckled, straddling, solid, bright); own_scale: W's finite values on a scale of its own, 0.37 W - 55, for
+    the correlation cost, which quantises W with W's range (the two values stay two values: 0 and 1023 again)"""
+    F, W = {"speckled": lambda: speckled_pair(shape, seed), "straddling": lambda: speckled_pair(shape, seed, fraction=0.033), "solid": lambda: solid_pair(shape), "bright": lambda: bright_pair(shape, seed)}[kind]()
+    if own_scale:
+        W = (0.37 * W.astype(np.float64) - 55.0).astype(np.float32)
+    return F, W
+
+
+def ends_lattice(kind, shape, stride, b, r):
+    return solid_lattice(shape, stride, b, r) if kind == "solid" else lattice_numpy(shape, stride, b, r)
+
+
+def quantiser_probe(values, lo, hi):
+    """(volume, first, count): a float32 volume that is constant over cells of 3 x 3 x 3 voxels, one of the values per cell (x
+    fastest; the cells left over hold lo), inside a shell of one voxel at lo whose first voxel is lo and whose last is hi: the two
+    range voxels.  The block search with b = 1, r = 1, stride 3 from first over count has one node per cell, on its centre, whose
+    block is the cell: as F, the record's words 12 and 13 are 27 q and 27 q^2 of the cell's quantised value q; as W against an
+    F of lo alone, word 5 (the cost of the zero shift) is 27 q^2."""
+    values = np.asarray(values, np.float32)
+    c = int(np.ceil(len(values) ** (1.0 / 3.0) - 1e-9))
+    cells = np.full(c ** 3, lo, np.float32)
+    cells[:len(values)] = values
+    vol = np.full((3 * c + 2,) * 3, lo, np.float32)
+    vol[1:-1, 1:-1, 1:-1] = np.repeat(np.repeat(np.repeat(cells.reshape(c, c, c), 3, 0), 3, 1), 3, 2)
+    vol[-1, -1, -1] = hi
+    return vol, (2, 2, 2), (c, c, c)
+
+
+def half_way_values():
+    """what a quantiser over 0 .. 1023 can get wrong: every exact half-way value k + 0.5 (rint goes to the even neighbour), the
+    floats next to a few of them, both ends, -0.0, a denormal, a tiny value and the last float below 1023"""
+    k = np.arange(1023, dtype=np.float32) + np.float32(0.5)
+    near = np.array([0.5, 1.5, 2.5, 511.5, 512.5, 1021.5, 1022.5], np.float32)
+    return np.concatenate([k, np.nextafter(near, np.float32(np.inf)), np.nextafter(near, np.float32(-np.inf)),
+                           np.array([0.0, 1023.0, -0.0, 1e-45, 1e-30, 1022.99994], np.float32)]).astype(np.float32)
+
+
+def probe_read(words, n, word=12):
+    """the quantised value of the first n cells of a probe from the records' word 12 (27 q), 13 or 5 (27 q^2)"""
+    w = np.asarray(words).reshape(-1, WORDS)[:n, word].astype(np.int64)
+    assert (w % 27 == 0).all()
+    if word == 12:
+        return w // 27
+    q = np.rint(np.sqrt(w // 27)).astype(np.int64)
+    assert (27 * q * q == w).all()
+    return q
 
 
 def zero_field(grid):

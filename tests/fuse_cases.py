@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from _helpers import c_oracle
-from blockmatch_cases import volume
+from blockmatch_cases import SUM_MAX_B6, bright, bright_pair, lattice3, speckled_pair, stripes, volume   # noqa: F401 (the fusion tests take them from here)
 from invert_cases import forward_field
 from resample_cases import affine, rot
 
@@ -157,6 +157,24 @@ def pair(shape, seed, holes=False):
             at = rng.random(shape) < 0.03
             vol[at] = rng.choice(np.array([np.nan, np.inf, -np.inf], np.float32), int(at.sum()))
     return T, W
+
+
+def ends_volumes(kind, shape, seed):
+    """(T, W) of 0 and 1 alone, at the ends of the integer sums (blockmatch_cases.py): speckled (nearly every pair differs by the full
+    range: D near n 1023^2, u = 0), speckled_holes (with NaN and infinite voxels in both), bright (Sff, Sww and Sfw beyond 2^31 at
+    b = 6, patches that are not flat; the bright pair with W moved back, so that the patches correspond at the zero shift, the one
+    the weights look at), bright_same (W = T: D = Sff - 2 Sfw + Sww = 0 from three sums beyond 2^31, u = 32768)"""
+    if kind == "bright_same":
+        T = bright(shape, seed)
+        return T, T.copy()
+    if kind == "bright":
+        T, W = bright_pair(shape, seed)
+        return T, np.ascontiguousarray(np.roll(W, (0, -1, 1), (0, 1, 2)))
+    return speckled_pair(shape, seed, holes=kind == "speckled_holes")
+
+
+ENDS = ["speckled", "speckled_holes", "bright", "bright_same"]
+ENDS_SHAPE = (15, 17, 37)   # every extent >= 2 * 6 + 3: some patches are unclipped at b = 6; more than one 32 x 8 x 4 brick per axis, partial ones
 
 
 # ---- the scenario ------------------------------------------------------------------------------------------------------------------

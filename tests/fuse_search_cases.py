@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from _helpers import c_oracle
-from fuse_cases import METRICS, NONE, FALLBACK, FuseOracle, pair
+from fuse_cases import ENDS_SHAPE, METRICS, NONE, FALLBACK, SUM_MAX_B6, FuseOracle, bright_pair, lattice3, pair, speckled_pair, stripes   # noqa: F401
 
 NO_SHIFT = 0xffff
 
@@ -158,3 +158,43 @@ def block_labels(shape, seed, nan_block=True):
         at = rng.random(shape) < 0.02
         lab[at] = rng.choice(np.array([np.nan, np.inf], np.float32), int(at.sum()))
     return np.ascontiguousarray(lab)
+
+
+# ---- volumes at the ends of the integer sums (blockmatch_cases.py) ------------------------------------------------------------------
+SEARCH_ENDS = ["speckled", "speckled_holes", "bright"]
+SEARCH_ENDS_BR = [(2, 1), (2, 3), (3, 3), (5, 1), (6, 0)]   # the forms with b and r at compile time, the largest tiles, the widest sums
+
+
+def ends_search_volumes(kind, shape, seed):
+    """(T, W) of 0 and 1 alone: speckled (every candidate's D near n 1023^2), speckled_holes (NaN and infinite voxels in both: which
+    pairs count changes with the shift), bright (W is T moved by (tx, ty, tz) = (-1, 1, 0) with 3 % of its voxels flipped: Sff, Sww and
+    Sfw beyond 2^31 at b = 6, and a shift to find)"""
+    if kind == "bright":
+        return bright_pair(shape, seed)
+    return speckled_pair(shape, seed, holes=kind == "speckled_holes")
+
+
+def tie_pick(shape, axis=None):
+    """the shift codes (as (tx, ty, tz) per voxel, int, shape + (3,)) that the contract picks on lattice3 (axis None) or stripes
+    (axis 0: z, 1: y, 2: x) against the complement: of the shortest shifts that cost nothing the one with the least tz, then ty,
+    then tx, among those that stay inside the volume"""
+    zyx = np.meshgrid(*(np.arange(n) for n in shape), indexing="ij")
+    t = np.zeros(tuple(shape) + (3,), np.int64)
+    done = np.zeros(shape, bool)
+    for ax in ((0, 1, 2) if axis is None else (axis,)):          # -1 along z, then y, then x, where the voxel has a neighbour there
+        take = ~done & (zyx[ax] > 0)
+        t[..., 2 - ax][take] = -1
+        done |= take
+    for ax in ((2, 1, 0) if axis is None else (axis,)):          # else +1: tz = ty = 0 and tx = 1 comes before ty = 1, and that before tz = 1
+        take = ~done & (zyx[ax] < shape[ax] - 1)
+        t[..., 2 - ax][take] = 1
+        done |= take
+    assert done.all()
+    return t
+
+
+def shift_vectors(shift, r):
+    """(tx, ty, tz) per voxel of a plane of codes without NO_SHIFT"""
+    s = np.asarray(shift).astype(np.int64)
+    w = 2 * r + 1
+    return np.stack([s % w - r, s // w % w - r, s // (w * w) - r], -1)

@@ -1,11 +1,12 @@
 """CPU suite: the intensity refinement of DESIGN.md section 7f without a GPU -- the block search oracle against a numpy
-restatement, planted translations, ties, flags; the host helpers (range, lattice, grid, gates, sub-voxel step, samples, folds)
+restatement (at b = 6 also where the costs pass 2^31), planted translations, ties, flags, the quantiser at half-way values and
+over the widest and the narrowest range; the host helpers (range, lattice, grid, gates, sub-voxel step, samples, folds)
 against hand-made words; and the nonrigid scenario of section 7e refined on the CPU."""
 import numpy as np
 import pytest
 
-from blockmatch_cases import (NONE, WORDS, BlockOracle, cpu_refine_intensity, lattice_numpy, match_numpy, quantize_numpy, scenario_score,
-                              scenario_setup, shifts, volume)
+from blockmatch_cases import (NONE, SUM_MAX_B6, WORDS, BlockOracle, cpu_refine_intensity, ends_lattice, ends_pair, half_way_values, lattice3, lattice_numpy,
+                              match_numpy, probe_read, quantiser_probe, quantize_numpy, scenario_score, scenario_setup, shifts, stripes, volume)
 from field_cases import FieldOracle
 
 
@@ -19,17 +20,27 @@ def fo(tmp_path_factory):
     return FieldOracle(tmp_path_factory.mktemp("field_oracle"))
 
 
-@pytest.mark.parametrize("kind", ["random", "smooth", "constant"])
-@pytest.mark.parametrize("b,r,stride", [(1, 1, 1), (1, 3, 4), (4, 1, 5), (4, 3, 1), (4, 3, 4), (4, 3, 5)])
+ENDS = ["speckled", "straddling", "solid", "bright"]   # blockmatch_cases.ends_pair: volumes of 0 and 1 alone, at the ends of the integer sums
+
+
+@pytest.mark.parametrize("kind", ["random", "smooth", "constant"] + ENDS)
+@pytest.mark.parametrize("b,r,stride", [(1, 1, 1), (1, 3, 4), (4, 1, 5), (4, 3, 1), (4, 3, 4), (4, 3, 5), (6, 1, 1), (6, 4, 3)])
 def test_oracle_equals_numpy(built, bo, kind, b, r, stride):
-    shape = (19, 17, 24)   # (nz, ny, nx)
-    F = volume(kind, shape, 11)
-    W = np.roll(F, (1, 0, -1), (0, 1, 2)) + (0 if kind == "constant" else np.random.default_rng(2).normal(0, 1.0, shape).astype(np.float32))
+    """The int64 restatement cannot wrap, so it settles what the words are where the sums pass 2^31: at b = 6 on the volumes of 0
+    and 1 alone, on 26 x 27 x 29 (the 21^3 window of (6, 4) does not fit the smaller volume)."""
+    shape = (19, 17, 24) if b < 6 else (26, 27, 29)   # (nz, ny, nx)
+    if kind in ENDS:
+        F, W = ends_pair(kind, shape, 11)
+    else:
+        F = volume(kind, shape, 11)
+        W = np.roll(F, (1, 0, -1), (0, 1, 2)) + (0 if kind == "constant" else np.random.default_rng(2).normal(0, 1.0, shape).astype(np.float32))
     lo, hi = bo.range(F)
     assert (lo, hi) == built.blockmatch_range(F) == (F.min(), F.max())
     qf, qw = bo.quantize(F, lo, hi), bo.quantize(W, lo, hi)
     assert (qf == quantize_numpy(F, lo, hi)).all() and (qw == quantize_numpy(W, lo, hi)).all()
     assert qf.min() == 0 and qf.max() == 1023 and qw.min() >= 0 and qw.max() <= 1023
+    if kind in ENDS:
+        assert set(np.unique(qf)) == {0, 1023} and set(np.unique(qw)) == {0, 1023}
     first, count = lattice_numpy(shape, stride, b, r)
     assert (first, count) == built.blockmatch_lattice(shape, stride=stride, block=b, search=r)
     # one node more on every side: those leave the volume and are flagged
@@ -39,6 +50,76 @@ def test_oracle_equals_numpy(built, bo, kind, b, r, stride):
     inner = got[1:-1, 1:-1, 1:-1]
     assert (inner[..., 3] == 0).all() and (got[..., 3] != 0).sum() == got[..., 3].size - inner[..., 3].size
     assert (got[got[..., 3] != 0] == np.eye(WORDS, dtype=np.uint32)[3]).all()
+    # the ends: what test_gpu_integer_ends.py relies on, asserted on the oracle's words
+    top = (2 * b + 1) ** 3 * 1023 ** 2
+    if kind == "speckled":
+        print("speckled b %d r %d: least cost %d .. %d of at most %d" % (b, r, inner[..., 4].min(), inner[..., 4].max(), top))
+        assert len(np.unique(inner[..., 4])) > 1                  # the costs vary from node to node
+        if b == 6:
+            assert inner[..., 4].min() >= 2 ** 31 and top == SUM_MAX_B6 < 2 ** 32
+    if kind == "straddling" and b == 6:   # within one node, costs below and beyond 2^31: a signed compare of two costs or keys would show
+        both = (inner[..., 4] < 2 ** 31) & (np.where(inner[..., 5:12] == NONE, 0, inner[..., 5:12]).max(-1) >= 2 ** 31)
+        print("straddling b %d r %d: least cost %d .. %d, a cost on either side of 2^31 at %.3f of the nodes" % (b, r, inner[..., 4].min(), inner[..., 4].max(), both.mean()))
+        assert both.mean() > 0.25           # the record shows 8 of the (2r + 1)^3 costs: a quarter of the nodes is plenty
+    if kind == "bright":
+        print("bright b %d r %d: Sf2 %d .. %d" % (b, r, inner[..., 13].min(), inner[..., 13].max()))
+        if b == 6:
+            assert inner[..., 13].min() >= 2 ** 31
+    if kind == "solid":   # where no window reaches W's corner voxel every cost is the largest there is, and the zero shift wins
+        f1, c1 = ends_lattice(kind, shape, stride, b, r)
+        w = bo.match_q(qf, qw, f1, stride, c1, b, r)
+        assert (w[..., 3] == 0).all() and (shifts(w) == 0).all() and (w[..., 4:12] == top).all()
+        assert (w[..., 12:14] == 0).all() and w.tobytes() == match_numpy(qf, qw, f1, stride, c1, b, r).tobytes()
+
+
+@pytest.mark.parametrize("b,r", [(1, 1), (4, 3), (6, 1)])
+def test_ties_between_unit_shifts_go_to_the_least_z_then_y_then_x(bo, b, r):
+    """the checkerboard against its complement: the six unit shifts all cost 0, the zero shift the most, and s_z = -1 wins (least z
+    first); stripes along one axis: only -1 and +1 along it tie, and -1 wins.  Every node's window lies inside the volume, so
+    there is no face here at which -1 could be missing: the fusion search has those (test_fuse_search_cpu.py)."""
+    shape = (17, 18, 19)
+    first, count = lattice_numpy(shape, 1, b, r)
+    top = (2 * b + 1) ** 3 * 1023 ** 2
+    F, W = lattice3(shape)
+    w = bo.match(F, W, first, 1, count, b, r)
+    assert w.tobytes() == match_numpy(bo.quantize(F, 0, 1), bo.quantize(W, 0, 1), first, 1, count, b, r).tobytes()
+    assert (w[..., 3] == 0).all() and (shifts(w) == np.array((0, 0, -1), np.int32)).all() and (w[..., 4] == 0).all() and (w[..., 5] == top).all()
+    for axis in (0, 1, 2):
+        F, W = stripes(shape, axis)
+        w = bo.match(F, W, first, 1, count, b, r)
+        want = np.zeros(3, np.int32)
+        want[2 - axis] = -1                              # the words hold (x, y, z)
+        assert (w[..., 3] == 0).all() and (shifts(w) == want).all() and (w[..., 4] == 0).all() and (w[..., 5] == top).all()
+
+
+# ---- the quantiser ---------------------------------------------------------------------------------------------------------------
+def test_quantiser_at_half_way_values_the_ends_and_the_widest_range(bo):
+    v = half_way_values()
+    vol, first, count = quantiser_probe(v, 0.0, 1023.0)
+    assert bo.range(vol) == (np.float32(0.0), np.float32(1023.0))
+    q = bo.quantize(v, 0.0, 1023.0)
+    assert np.array_equal(q, quantize_numpy(v, 0.0, 1023.0))
+    assert np.array_equal(q[:1023], 2 * ((np.arange(1023) + 1) // 2)) and q[-6:].tolist() == [0, 1023, 0, 0, 0, 1023]   # ties to even
+    w = bo.match(vol, vol, first, 3, count, 1, 1)
+    assert (w[..., 3] == 0).all() and np.array_equal(probe_read(w, len(v), 12), q) and np.array_equal(probe_read(w, len(v), 13), q)
+    # a range wider than a float holds: hi - lo overflows in float and not in double
+    lo, hi = np.float32(-3.0e38), np.float32(3.0e38)
+    v = np.array([3.4028235e38, -3.4028235e38, 1e38, -1e38, 0.0, 3.0e38, -3.0e38], np.float32)
+    q = bo.quantize(v, lo, hi)
+    assert np.array_equal(q, quantize_numpy(v, lo, hi)) and q.tolist() == [1023, 0, 682, 341, 512, 1023, 0]
+    Fv, first, count = quantiser_probe(np.full(len(v), lo, np.float32), lo, hi)
+    Wv, _, _ = quantiser_probe(v, lo, hi)
+    w = bo.match(Fv, Wv, first, 3, count, 1, 1)
+    assert (w[..., 3] == 0).all() and np.array_equal(probe_read(w, len(v), 5), q)
+    # a range one float ulp wide
+    lo, hi = np.float32(1.0), np.nextafter(np.float32(1.0), np.float32(2.0))
+    v = np.array([lo, hi, np.nextafter(lo, np.float32(0.0)), np.nextafter(hi, np.float32(2.0)), 0.5, 2.0, -3.4e38, 3.4e38], np.float32)
+    q = bo.quantize(v, lo, hi)
+    assert np.array_equal(q, quantize_numpy(v, lo, hi)) and q.tolist() == [0, 1023, 0, 1023, 0, 1023, 0, 1023]
+    # outside a given range it clamps; what is not finite is -1
+    v = np.array([-1.0, 0.0, 0.25, 0.75, 1.0, 2.0, np.nan, np.inf, -np.inf], np.float32)
+    q = bo.quantize(v, 0.25, 0.75)
+    assert np.array_equal(q, quantize_numpy(v, 0.25, 0.75)) and q.tolist() == [0, 0, 0, 1023, 1023, 1023, -1, -1, -1]
 
 
 @pytest.mark.parametrize("s", [(0, 0, 0), (1, -2, 3), (-3, 3, -3), (2, 0, -1)])

@@ -5,7 +5,7 @@ blocks, the flags, and the nonrigid scenario of section 7e refined on the CPU fr
 import numpy as np
 import pytest
 
-from blockmatch_cases import WORDS, cpu_refine_intensity, lattice_numpy, scenario_score, scenario_setup, shifts, volume
+from blockmatch_cases import WORDS, binary as _binary, cpu_refine_intensity, ends_pair, lattice_numpy, scenario_score, scenario_setup, shifts, volume
 from blockmatch_ncc_cases import FLAT, NccOracle, cost_python, cpu_refine_intensity_metric, match_numpy_ncc, remap
 from field_cases import FieldOracle
 
@@ -20,22 +20,21 @@ def fo(tmp_path_factory):
     return FieldOracle(tmp_path_factory.mktemp("field_oracle"))
 
 
-def _binary(shape, seed):
-    """quantised volumes of 0 and 1023 alone: the widest sums and the extremes of A and the variances"""
-    rng = np.random.default_rng(seed)
-    qf = (1023 * rng.integers(0, 2, shape)).astype(np.int16)
-    qw = np.roll(qf, (0, 1, -1), (0, 1, 2))
-    flip = rng.random(shape) < 0.05
-    qw[flip] = 1023 - qw[flip]
-    return qf, qw
+ENDS = ["speckled", "solid", "bright"]   # blockmatch_cases.ends_pair: volumes of two values alone, W on a scale of its own
 
 
-@pytest.mark.parametrize("kind", ["random", "smooth", "constant", "binary"])
-@pytest.mark.parametrize("b,r,stride", [(1, 1, 1), (1, 3, 4), (4, 1, 5), (4, 3, 1), (4, 3, 4), (6, 1, 1), (6, 2, 3)])
+@pytest.mark.parametrize("kind", ["random", "smooth", "constant", "binary"] + ENDS)
+@pytest.mark.parametrize("b,r,stride", [(1, 1, 1), (1, 3, 4), (4, 1, 5), (4, 3, 1), (4, 3, 4), (6, 1, 1), (6, 2, 3), (6, 4, 3)])
 def test_oracle_equals_numpy(no, kind, b, r, stride):
-    shape = (19, 17, 24)   # (nz, ny, nx)
+    """The restatement's sums are int64 and its products Python integers: it settles the words where Sff, Sww and Sfw pass 2^31,
+    which they do at b = 6 on the bright pair (the 21^3 window of (6, 4) takes the larger volume)."""
+    shape = (19, 17, 24) if b + r < 10 else (26, 27, 29)   # (nz, ny, nx)
     if kind == "binary":
         qf, qw = _binary(shape, 7)
+    elif kind in ENDS:
+        F, W = ends_pair(kind, shape, 11, own_scale=True)
+        qf, qw = no.quantize(F, *no.range(F)), no.quantize(W, *no.range(W))
+        assert set(np.unique(qf)) == {0, 1023} and set(np.unique(qw)) == {0, 1023} and W.max() < -54.0
     else:
         F = volume(kind, shape, 11)
         W = 0.7 * np.roll(F, (1, 0, -1), (0, 1, 2)) + 40.0
@@ -52,7 +51,16 @@ def test_oracle_equals_numpy(no, kind, b, r, stride):
     inner = got[1:-1, 1:-1, 1:-1]
     assert (inner[..., 3] == 0).all() and (got[..., 3] != 0).sum() == got[..., 3].size - inner[..., 3].size
     assert (got[got[..., 3] != 0] == np.eye(WORDS, dtype=np.uint32)[3]).all()
-    assert (inner[..., 4:6] <= FLAT).all() and (inner[..., 12] == 0).sum() == 0
+    assert (inner[..., 4:6] <= FLAT).all() and ((inner[..., 12] == 0).sum() == 0 or kind in ("speckled", "solid"))   # those two have blocks of 0 alone
+    if kind == "solid":      # F's blocks are flat
+        assert (shifts(inner) == 0).all() and (inner[..., 4:12] == FLAT).all() and (inner[..., 12:14] == 0).all()
+    if kind == "bright":     # Sff beyond 2^31 (and with it Sww and Sfw of the matching shift), blocks that are not flat
+        cost = inner[..., 4]
+        print("bright b %d r %d: Sff %d .. %d, cost %d .. %d, at 2^31 %.3f, at 0 %.3f" % (b, r, inner[..., 13].min(), inner[..., 13].max(), cost.min(),
+                                                                                      cost.max(), (cost == FLAT).mean(), (cost == 0).mean()))
+        if b == 6:
+            assert inner[..., 13].min() >= 2 ** 31
+            assert ((cost > 0) & (cost < FLAT)).mean() > 0.5 and (cost == FLAT).mean() < 0.1
     if kind == "constant":   # every block is flat: every cost is 2^31 and the zero shift wins every tie
         assert (shifts(inner) == 0).all() and (inner[..., 4:6] == FLAT).all()
 

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from field_cases import FieldOracle
-from fuse_cases import FALLBACK, NONE, U_ONE, FuseOracle, cpu_fuse, fused_labels, leg, mean_dice, pair, scenario
+from fuse_cases import ENDS, ENDS_SHAPE, FALLBACK, NONE, SUM_MAX_B6, U_ONE, FuseOracle, cpu_fuse, ends_volumes, fused_labels, leg, mean_dice, pair, scenario
 from resample_cases import ResampleOracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,9 +64,13 @@ def u_python(metric, n, sf, sff, sw, sww, sfw):
 
 
 @pytest.mark.parametrize("metric", ["ssd", "ncc"])
-@pytest.mark.parametrize("shape,b,holes", [((2, 3, 4), 2, False), ((5, 9, 33), 2, False), ((11, 19, 21), 1, True), ((9, 14, 17), 6, True)])
-def test_oracle_equals_numpy(fz, metric, shape, b, holes):
-    T, W = pair(shape, 5, holes)
+@pytest.mark.parametrize("shape,b,holes,kind", [pytest.param(*c, "pair", id="shape%d-%d-%s" % (i, c[1], c[2])) for i, c in enumerate(
+    [((2, 3, 4), 2, False), ((5, 9, 33), 2, False), ((11, 19, 21), 1, True), ((9, 14, 17), 6, True)])] +     # the ids these cases have always had
+    [pytest.param(ENDS_SHAPE, b, k == "speckled_holes", k, id="%s-%d" % (k, b)) for k in ENDS for b in (2, 6)])
+def test_oracle_equals_numpy(fz, metric, shape, b, holes, kind):
+    """kind "pair": fuse_cases.pair.  The others are fuse_cases.ends_volumes on a shape with unclipped patches at b = 6: the restatement's
+    sums are int64 and cannot wrap, so it settles the sums and u where they pass 2^31."""
+    T, W = pair(shape, 5, holes) if kind == "pair" else ends_volumes(kind, shape, 5)
     qt, qw = fz.quantize(T, *fz.range(T)), fz.quantize(W, *(fz.range(T) if metric == "ssd" else fz.range(W)))
     assert qt.max() == 1023 and qt.min() == (-1 if holes else 0)
     u, sums = fz.weights_q(qt, qw, b, metric, sums=True)
@@ -75,7 +79,21 @@ def test_oracle_equals_numpy(fz, metric, shape, b, holes):
     assert sums[..., 0].max() <= (2 * b + 1) ** 3 and sums.max() < 2 ** 32
     flat = want.reshape(-1, 6)
     assert np.array_equal(u.reshape(-1), np.array([u_python(metric, *(int(v) for v in s)) for s in flat], np.uint16))
-    assert u.max() <= U_ONE and 0 < u.max() and len(np.unique(u)) > 1
+    if kind == "pair":
+        assert u.max() <= U_ONE and 0 < u.max() and len(np.unique(u)) > 1
+        return
+    # the ends: what test_gpu_integer_ends.py relies on, asserted on the oracle's sums
+    D = sums[..., 2] - 2 * sums[..., 5] + sums[..., 4]
+    print("%s %s b %d: largest sum %d, D %d .. %d, u %d .. %d" % (kind, metric, b, sums.max(), D.min(), D.max(), u.min(), u.max()))
+    assert set(np.unique(qt)) - {-1} == {0, 1023} and set(np.unique(qw)) - {-1} == {0, 1023} and u.max() <= U_ONE
+    if b == 6:
+        assert 2 ** 31 <= sums.max() <= SUM_MAX_B6 < 2 ** 32
+    if kind.startswith("speckled"):
+        assert (metric == "ncc" or (u == 0).all()) and (b < 6 or D.max() >= 2 ** 31) and (sums[..., 0].min() < (2 * b + 1) ** 3) and D.max() < 2 ** 32
+    if kind == "bright_same":
+        assert ((u == U_ONE) | ((u == 0) & (metric == "ncc"))).all() and (u == U_ONE).mean() > 0.9 and (D == 0).all() and (b < 6 or min(sums[..., i].max() for i in (2, 4, 5)) >= 2 ** 31)
+    if kind == "bright" and metric == "ncc" and b == 6:   # A, Vf and Vw are small differences of large products, and no patch is flat
+        assert ((u > 0) & (u < U_ONE)).mean() > 0.9 and len(np.unique(u)) > 100
 
 
 @pytest.mark.parametrize("metric", ["ssd", "ncc"])

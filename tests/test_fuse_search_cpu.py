@@ -10,7 +10,8 @@ import pytest
 
 from field_cases import FieldOracle
 from fuse_cases import NONE, U_ONE, fused_labels, leg, mean_dice, pair, scenario
-from fuse_search_cases import NO_SHIFT, FuseSearchOracle, block_labels, fuse_planes, shift_stats, shifted_pair, warped_planes
+from fuse_search_cases import (ENDS_SHAPE, NO_SHIFT, SEARCH_ENDS, SEARCH_ENDS_BR, SUM_MAX_B6, FuseSearchOracle, block_labels, ends_search_volumes, fuse_planes, lattice3,
+                               shift_stats, shift_vectors, shifted_pair, stripes, tie_pick, warped_planes)
 from resample_cases import ResampleOracle
 from test_fuse_cpu import SCENARIO_DICE
 
@@ -98,17 +99,22 @@ def same_picked(a, b):
         and np.array_equal(np.nan_to_num(a, nan=-1.0), np.nan_to_num(b, nan=-1.0))
 
 
-BR = [(1, 1), (1, 2), (1, 3), (2, 1), (2, 2), (2, 3), (3, 3)]
+BR = [(1, 1), (1, 2), (1, 3), (2, 1), (2, 2), (2, 3), (3, 3), (5, 1), (6, 0)]
 
 
 @pytest.mark.parametrize("metric", ["ssd", "ncc"])
-@pytest.mark.parametrize("shape,holes", [((2, 3, 4), False), ((5, 9, 33), False), ((7, 11, 21), True)])
-def test_oracle_equals_numpy_and_its_summed_area_form(fs, metric, shape, holes):
-    T, W = shifted_pair(shape, 5, (1, -1, 1), holes)
+@pytest.mark.parametrize("shape,holes,kind", [pytest.param(*c, "shifted", id="shape%d-%s" % (i, c[1])) for i, c in enumerate(
+    [((2, 3, 4), False), ((5, 9, 33), False), ((7, 11, 21), True)])] +                                       # the ids these cases have always had
+    [pytest.param(ENDS_SHAPE, k == "speckled_holes", k, id=k) for k in SEARCH_ENDS])
+def test_oracle_equals_numpy_and_its_summed_area_form(fs, metric, shape, holes, kind):
+    """kind "shifted": shifted_pair.  The others are fuse_search_cases.ends_search_volumes on a shape with unclipped patches at b = 6: the
+    restatement's sums are int64 and cannot wrap, so it settles the chosen candidate's sums and u where they pass 2^31."""
+    ends = kind != "shifted"
+    T, W = ends_search_volumes(kind, shape, 5) if ends else shifted_pair(shape, 5, (1, -1, 1), holes)
     qt, qw = fs.quantised(T, W, metric)
     assert qt.max() == 1023 and qt.min() == (-1 if holes else 0)
     labels = block_labels(shape, 3, nan_block=holes)
-    for b, r in BR:
+    for b, r in (SEARCH_ENDS_BR if ends else BR):
         u, shift, picked, sums = fs.search_q(qt, qw, labels, b, r, metric, sums=True)
         nu, nshift, npicked, nsums = search_numpy(qt, qw, labels, b, r, metric)
         assert np.array_equal(u, nu) and np.array_equal(shift, nshift) and same_picked(picked, npicked) and np.array_equal(sums, nsums), (b, r)
@@ -118,12 +124,44 @@ def test_oracle_equals_numpy_and_its_summed_area_form(fs, metric, shape, holes):
         votes = shift != NO_SHIFT
         assert np.array_equal(votes, u != 0xffff) and np.array_equal(votes, np.isfinite(picked)) and u[votes].max() <= U_ONE
         assert shift[votes].max() < (2 * r + 1) ** 3
+        if ends:      # what test_gpu_integer_ends.py relies on, asserted on the oracle's sums
+            D = sums[..., 2] - 2 * sums[..., 5] + sums[..., 4]
+            print("%s %s b %d r %d: largest sum %d, D %d .. %d, u %d .. %d" % (kind, metric, b, r, sums.max(), D.min(), D.max(), u[votes].min(), u[votes].max()))
+            assert set(np.unique(qt)) - {-1} == {0, 1023} and set(np.unique(qw)) - {-1} == {0, 1023}
+            if b == 6:
+                assert 2 ** 31 <= sums.max() <= SUM_MAX_B6 < 2 ** 32 and (kind == "bright" or D.max() >= 2 ** 31)
+            if kind.startswith("speckled") and metric == "ssd":
+                assert (u[votes] == 0).all() and (holes or (shift == fs.code(r, (0, 0, 0))).all())    # u = 0 at every candidate: the nearest that may be picked
+            if kind == "bright" and r >= 1:     # the planted shift is found (many patches of 5^3 voxels are all 1 and tell nothing)
+                found = (shift == fs.code(r, (-1, 1, 0)))[1:-1, 1:-1, 1:-1].mean()
+                print("  planted shift found at %.3f of the inner voxels" % found)
+                assert found > 0.4 and u[votes].max() > 0
+    if ends:
+        return
     # without labels every shift inside the volume is a candidate
     u, shift, picked = fs.search_q(qt, qw, None, 2, 2, metric)
     nu, nshift, _, _ = search_numpy(qt, qw, None, 2, 2, metric)
     assert picked is None and np.array_equal(u, nu) and np.array_equal(shift, nshift) and (shift != NO_SHIFT).all()
     if shape == (5, 9, 33):
         assert shift_stats(shift, 2)[0] > 0.5 * shift.size       # the moved W is found
+
+
+@pytest.mark.parametrize("metric", ["ssd", "ncc"])
+@pytest.mark.parametrize("b,r", [(1, 1), (2, 1), (2, 3), (5, 1)])
+def test_ties_between_unit_shifts_at_the_interior_and_at_the_faces(fs, metric, b, r):
+    """the checkerboard against its complement: the six unit shifts all give u = 32768 and every even shift 0 (under the correlation
+    too: the patches are equal, or anticorrelated); t = (tz, ty, tx) = (-1, 0, 0) is picked, and at the low faces, where it leaves
+    the volume, the next of the order.  Stripes along one axis: -1 along it, and +1 at the low face."""
+    shape = (7, 9, 37)
+    for axis in (None, 0, 1, 2):
+        T, W = lattice3(shape) if axis is None else stripes(shape, axis)
+        qt, qw = fs.quantised(T, W, metric)
+        u, shift, _, sums = fs.search_q(qt, qw, None, b, r, metric, sums=True)
+        nu, nshift, _, nsums = search_numpy(qt, qw, None, b, r, metric)
+        assert np.array_equal(u, nu) and np.array_equal(shift, nshift) and np.array_equal(sums, nsums)
+        assert (u == U_ONE).all() and np.array_equal(shift_vectors(shift, r), tie_pick(shape, axis)), axis
+    inner = shift_vectors(shift, r)[1:, 1:, 1:]
+    assert (inner == np.array((-1, 0, 0))).all() and (shift_vectors(shift, r)[:, :, 0] == np.array((1, 0, 0))).all()   # stripes along x: (tx, ty, tz)
 
 
 @pytest.mark.parametrize("metric", ["ssd", "ncc"])
