@@ -38,6 +38,27 @@ static const char *check_search(int b, int r)
     return nullptr;
 }
 
+/* The range W is quantised with, into wlo and whi: w_range where it is given, under NCC W's own (w: nv values), else T's (lo, hi).
+ * false: there is none -- w_range is empty or not finite, or W has no two distinct finite values */
+static bool w_range_of(int metric, const float w_range[2], const float *w, size_t nv, float lo, float hi, float *wlo, float *whi)
+{
+    *wlo = lo;
+    *whi = hi;
+    if (w_range) {
+        *wlo = w_range[0];
+        *whi = w_range[1];
+        return *whi > *wlo && std::isfinite(*wlo) && std::isfinite(*whi);
+    }
+    return metric != SIFT3D_BLOCKMATCH_NCC || sift3d_blockmatch_range(w, (int64_t)nv, wlo, whi) != 0;
+}
+
+/* the host volume v (nv values) through d_v, quantised over [lo, hi] into d_q */
+static hipError_t send_quantised(device_call &dc, const float *v, size_t nv, float lo, float hi, float *d_v, short *d_q)
+{
+    const hipError_t e = dc.to_device(d_v, v, nv);
+    return e != hipSuccess ? e : sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_q);
+}
+
 extern "C" int sift3d_fuse_weights(int device, const float *t, const float *w, int64_t nx, int64_t ny, int64_t nz, int32_t b, int32_t metric,
                                    const float w_range[2], int32_t generic, uint16_t *u, double *kernel_ms, char *err, int64_t err_len)
 {
@@ -50,16 +71,8 @@ extern "C" int sift3d_fuse_weights(int device, const float *t, const float *w, i
     float lo, hi;
     if (!sift3d_blockmatch_range(t, (int64_t)nv, &lo, &hi))
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the target has no two distinct finite values: nothing to quantise");
-    float wlo = lo, whi = hi;
-    bool ranged = true;
-    if (w_range) {
-        wlo = w_range[0];
-        whi = w_range[1];
-        ranged = whi > wlo && std::isfinite(wlo) && std::isfinite(whi);
-    } else if (metric == SIFT3D_BLOCKMATCH_NCC) {
-        ranged = sift3d_blockmatch_range(w, (int64_t)nv, &wlo, &whi) != 0;
-    }
-    if (!ranged) {
+    float wlo, whi;
+    if (!w_range_of(metric, w_range, w, nv, lo, hi, &wlo, &whi)) {
         memset(u, 0, sizeof(uint16_t) * nv);
         return SIFT3D_OK;
     }
@@ -72,10 +85,8 @@ extern "C" int sift3d_fuse_weights(int device, const float *t, const float *w, i
         (void)hipGetLastError();
         return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", 10 * nv, device);
     }
-    DEVCHK(dc, dc.to_device(d_v, t, nv));
-    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_qt));
-    DEVCHK(dc, dc.to_device(d_v, w, nv));
-    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)wlo, (double)whi, d_qw));
+    DEVCHK(dc, send_quantised(dc, t, nv, lo, hi, d_v, d_qt));
+    DEVCHK(dc, send_quantised(dc, w, nv, wlo, whi, d_v, d_qw));
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
     DEVCHK(dc, sift3d_launch_fuse_weight(dc.s, d_qt, d_qw, nx, ny, nz, b, metric == SIFT3D_BLOCKMATCH_NCC, generic, d_u));
     DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
@@ -112,15 +123,8 @@ extern "C" int sift3d_fuse_search(int device, const float *t, const float *w, co
     float lo, hi;
     if (!sift3d_blockmatch_range(t, (int64_t)nv, &lo, &hi))
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the target has no two distinct finite values: nothing to quantise");
-    float wlo = lo, whi = hi;
-    bool ranged = true;
-    if (w_range) {
-        wlo = w_range[0];
-        whi = w_range[1];
-        ranged = whi > wlo && std::isfinite(wlo) && std::isfinite(whi);
-    } else if (metric == SIFT3D_BLOCKMATCH_NCC) {
-        ranged = sift3d_blockmatch_range(w, (int64_t)nv, &wlo, &whi) != 0;
-    }
+    float wlo, whi;
+    const bool ranged = w_range_of(metric, w_range, w, nv, lo, hi, &wlo, &whi);
     device_call dc(err, err_len);
     float *d_v, *d_l = nullptr, *d_p = nullptr;
     short *d_qt, *d_qw;
@@ -131,11 +135,9 @@ extern "C" int sift3d_fuse_search(int device, const float *t, const float *w, co
         (void)hipGetLastError();
         return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", (labels ? 20 : 12) * nv, device);
     }
-    DEVCHK(dc, dc.to_device(d_v, t, nv));
-    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_qt));
+    DEVCHK(dc, send_quantised(dc, t, nv, lo, hi, d_v, d_qt));
     if (ranged) {
-        DEVCHK(dc, dc.to_device(d_v, w, nv));
-        DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)wlo, (double)whi, d_qw));
+        DEVCHK(dc, send_quantised(dc, w, nv, wlo, whi, d_v, d_qw));
     } else {
         /* no range to quantise W with: every voxel of it is invalid, every patch is empty, u = 0 and the shift 0 wins every tie */
         DEVCHK(dc, hipMemsetAsync(d_qw, 0xff, sizeof(short) * nv, dc.s));
@@ -259,8 +261,7 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
                          16 * nodes_max, device);
     }
     /* T is quantised once; its float copy's buffer then holds the warped volumes */
-    DEVCHK(dc, dc.to_device(d_w, target, nv));
-    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, n, (double)rp.lo, (double)rp.hi, d_qt));
+    DEVCHK(dc, send_quantised(dc, target, nv, rp.lo, rp.hi, d_w, d_qt));
     std::vector<float4> nodes; /* send_nodes packs into it: it lives until the stream is synchronised */
     const float nanf_ = std::nanf("");
     for (int k = 0; k < K; k++) {
@@ -282,7 +283,7 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
             return sift3d_launch_resample(dc.s, d_m, a.nx, a.ny, a.nz, d_w, nx, ny, nz, map, nearest, nanf_);
         };
         float wlo = rp.lo, whi = rp.hi;
-        if (ncc && p.power > 0) r.empty_range = !sift3d_blockmatch_range(a.image, (int64_t)nm, &wlo, &whi);
+        if (p.power > 0) r.empty_range = !w_range_of(p.metric, nullptr, a.image, nm, rp.lo, rp.hi, &wlo, &whi);
         const bool weigh = p.power > 0 && !r.empty_range;
         double ms = 0.0;
         if (weigh) {

@@ -7,6 +7,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "patch_cost.h"
 #include "sift3d.h"
 
 void sift3d_fuse_defaults(sift3d_fuse_params *p)
@@ -26,12 +27,7 @@ uint32_t sift3d_fuse_similarity(int32_t metric, int64_t n, int64_t sf, int64_t s
         return (uint32_t)(((uint64_t)n << 15) / ((uint64_t)d + (uint64_t)n));
     }
     if (metric != SIFT3D_BLOCKMATCH_NCC) return 0;
-    const int64_t a = n * sfw - sf * sw, vf = n * sff - sf * sf, vw = n * sww - sw * sw;
-    double q = 0.0;
-    if (a > 0 && vf > 0 && vw > 0) q = ((double)a * (double)a) / ((double)vf * (double)vw);
-    q = q > 1.0 ? 1.0 : q;
-    const uint32_t c = (uint32_t)rint((1.0 - q) * 2147483648.0);
-    return (0x80000000u - c) >> 16;
+    return pc_u_ncc(n, sf, sff, sw, sww, sfw);
 }
 
 static int label_ok(float v) { return !isfinite(v) || (v >= 0.0f && v <= 65535.0f && v == (float)(int32_t)v); }

@@ -18,6 +18,7 @@
  *           the node's record.
  */
 #include "sift3d_internal.h"
+#include "patch_cost.h"
 
 #define BM_THREADS 256
 #define BM_QMAX 1023
@@ -265,9 +266,7 @@ struct bm_ssd {
  * rho of the F block and the shifted W block, from five integer sums.  N is the block's voxel count; Sf and Vf = N Sff - Sf^2 come
  * from the node's words of pass 1.  Widths: Sw < 2^22 and Sww, Sfw <= 13^3 1023^2 < 2^32 for b <= 6, as the squared differences
  * are, so they are accumulated in 32 bits; A = N Sfw - Sf Sw and the variances Vf, Vw do not fit (|A|, V <= (13^3 1023)^2 < 2^43) and
- * are formed in int64.  Each converts to double exactly; the rest is one sequence of IEEE double operations (multiply, multiply,
- * divide, subtract, multiply by 2^31, rint), which the host restates operation for operation: this file is compiled with
- * -ffp-contract=off and without fast-math, and fp64 multiply and divide are correctly rounded on the device. */
+ * are formed in int64.  What they cost is patch_cost.h's pc_ncc_cost, the one sequence of double operations. */
 struct bm_ncc {
     long long N, Sf, Vf;
 
@@ -282,10 +281,7 @@ struct bm_ncc {
     {
         const long long A = N * (long long)Sfw - Sf * (long long)Sw;
         const long long Vw = N * (long long)Sww - (long long)Sw * (long long)Sw;
-        double q = 0.0;
-        if (A > 0 && Vf > 0 && Vw > 0) q = ((double)A * (double)A) / ((double)Vf * (double)Vw);
-        q = q > 1.0 ? 1.0 : q;
-        return (unsigned)rint((1.0 - q) * 2147483648.0);
+        return pc_ncc_cost(A, Vf, Vw);
     }
 
     template <int B> __device__ __forceinline__ unsigned at(const short *f, const short *w, const bm_tiles &t) const

@@ -1,22 +1,21 @@
 /*
  * kernels_fuse.hip -- the hot path of multi-atlas label fusion for gfx950 (MI355X; tests/fuse_oracle.c
  * restates it as a serial brute force).  fuse_weight_kernel<B, METRIC> gives every target voxel its similarity u (0 .. 32768) to
- * one warped atlas from six integer sums over the voxel's clipped patch; fuse_label_kernel turns the warped float labels into a
- * uint16 plane and marks the voxels where the atlas does not vote; fuse_vote_kernel votes over the K planes.  Everything is
- * integer arithmetic but section 7g's one sequence of double operations, so no result depends on the tiling, the order of the
- * additions or the wave layout.
+ * one warped atlas from the integer sums over the voxel's clipped patch (patch_sums.h; what they are worth: patch_cost.h);
+ * fuse_label_kernel turns the warped float labels into a uint16 plane and marks the voxels where the atlas does not vote;
+ * fuse_vote_kernel votes over the K planes.  Everything is integer arithmetic but patch_cost.h's one sequence of double
+ * operations, so no result depends on the tiling, the order of the additions or the wave layout.
  *
  * fuse_weight_kernel.  A workgroup of 256 threads owns warp_device.h's brick of 32 x 8 x 4 target voxels (a thread four
  * consecutive x voxels, the bricks dealt over the XCDs) and stages the brick plus a halo of b of qT and qW in LDS, one dword per
  * voxel: the two int16 values side by side and the joint validity in bit 31.  A voxel outside the volume, or with q = -1 in
- * either volume, is staged as 0: it adds nothing to any sum, so a clipped or holed patch needs no test in the loops, and all six
+ * either volume, is staged as 0: it adds nothing to any sum, so a clipped or holed patch needs no test in the loops, and all
  * sums are plain box sums.
- *   B > 0 (b at compile time; instantiated for 2): per row (dz, dy) of the patch a thread reads the 4 + 2b dwords under its four
- *   windows once and adds each column's terms to that column's sums; after the (2b + 1)^2 rows the column sums slide into the
- *   four windows.  (4 + 2b) / 4 column updates per voxel and row instead of 2b + 1.
+ *   B > 0 (b at compile time; instantiated for 2), the sliding form: per row (dz, dy) of the patch a thread reads the 4 + 2b
+ *   dwords under its four windows once and adds each column's terms to that column's sums; after the (2b + 1)^2 rows the column
+ *   sums slide into the four windows.  (4 + 2b) / 4 column updates per voxel and row instead of 2b + 1.
  *   B = 0 (any b <= 6): every patch voxel straight from the tile, per output voxel.  The column sums of the sliding form would be
  *   arrays indexed by a run-time b, which the compiler keeps in scratch.
- * Under SSD only n and D = sum (qT - qW)^2 are needed (D = Sff - 2 Sfw + Sww exactly); under NCC all six.
  *
  * fuse_vote_kernel.  One voxel per lane.  The lane copies its K (label, u) pairs into its own column of LDS (dword k * 256 + lane:
  * lanes on consecutive banks, and no lane reads another's, so no barrier), then walks them in atlas order: for the first voter of
@@ -24,69 +23,13 @@
  * be an array under a run-time index (scratch), and re-reading global memory costs K^2 / 2 loads per voxel.
  */
 #include "sift3d_internal.h"
-#include "warp_device.h"
+#include "patch_sums.h"
 
 #define FUSE_THREADS 256
-#define FUSE_U_ONE 32768u    /* u of identical patches */
 #define FUSE_U_NONE 0xffffu  /* in a u plane: the atlas does not vote here */
 #define FUSE_VALID 0x80000000u
 #define FUSE_BIT_FALLBACK (1u << 30)
 #define FUSE_BIT_NONE (1u << 31)
-
-struct fuse_sums {
-    unsigned n, sf, sff, sw, sww, sfw, d;
-};
-
-/* u under SSD: (n 2^15) / (D + n) */
-__device__ __forceinline__ unsigned fuse_u_ssd(unsigned n, unsigned d)
-{
-    if (n == 0) return 0;
-    return (unsigned)(((unsigned long long)n << 15) / ((unsigned long long)d + n));
-}
-
-/* u under NCC: section 7g's cost with n in place of N, then (2^31 - cost) >> 16 */
-__device__ __forceinline__ unsigned fuse_u_ncc(const fuse_sums &s)
-{
-    if (s.n == 0) return 0;
-    const long long N = s.n, Sf = s.sf, Sw = s.sw;
-    const long long A = N * (long long)s.sfw - Sf * Sw;
-    const long long Vf = N * (long long)s.sff - Sf * Sf;
-    const long long Vw = N * (long long)s.sww - Sw * Sw;
-    double q = 0.0;
-    if (A > 0 && Vf > 0 && Vw > 0) q = ((double)A * (double)A) / ((double)Vf * (double)Vw);
-    q = q > 1.0 ? 1.0 : q;
-    const unsigned c = (unsigned)rint((1.0 - q) * 2147483648.0);
-    return (0x80000000u - c) >> 16;
-}
-
-/* one staged dword into the sums */
-template <int NCC> __device__ __forceinline__ void fuse_add(fuse_sums &s, unsigned x)
-{
-    const int f = (int)(x & 0xffffu), w = (int)((x >> 16) & 0x7fffu);
-    s.n += x >> 31;
-    if (NCC) {
-        s.sf += (unsigned)f;
-        s.sw += (unsigned)w;
-        s.sff += (unsigned)__mul24(f, f);
-        s.sww += (unsigned)__mul24(w, w);
-        s.sfw += (unsigned)__mul24(f, w);
-    } else {
-        const int d = f - w;
-        s.d += (unsigned)__mul24(d, d);
-    }
-}
-
-__device__ __forceinline__ void fuse_merge(fuse_sums &a, const fuse_sums &b, int sign)
-{
-    const unsigned m = sign < 0 ? ~0u : 0u; /* a += b or a -= b, modulo 2^32 */
-    a.n += (b.n ^ m) - m;
-    a.sf += (b.sf ^ m) - m;
-    a.sff += (b.sff ^ m) - m;
-    a.sw += (b.sw ^ m) - m;
-    a.sww += (b.sww ^ m) - m;
-    a.sfw += (b.sfw ^ m) - m;
-    a.d += (b.d ^ m) - m;
-}
 
 template <int B, int NCC>
 __global__ __launch_bounds__(FUSE_THREADS) void fuse_weight_kernel(const short *__restrict__ qt, const short *__restrict__ qw, long long nx, long long ny,
@@ -117,12 +60,12 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_weight_kernel(const short *
         const long long i0 = x0 + tx * BRICK_VX, j = y0 + ty, k = z0 + tz;
         if (j >= ny || k >= nz || i0 >= nx) continue; /* no barrier below this line */
         const unsigned *row0 = fuse_tile + tz * exy + ty * ex + tx * BRICK_VX; /* the patch's first voxel of output voxel 0 */
-        fuse_sums out[BRICK_VX];
+        patch_sums out[BRICK_VX];
         if constexpr (B > 0) {
             constexpr int COLS = BRICK_VX + 2 * B;
-            fuse_sums col[COLS];
+            patch_sums col[COLS];
 #pragma unroll
-            for (int c = 0; c < COLS; c++) col[c] = fuse_sums{0, 0, 0, 0, 0, 0, 0};
+            for (int c = 0; c < COLS; c++) col[c] = patch_sums{0, 0, 0, 0, 0, 0, 0};
 #pragma unroll 1
             for (int dz = 0; dz < 2 * B + 1; dz++)
 #pragma unroll 1
@@ -132,29 +75,19 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_weight_kernel(const short *
 #pragma unroll
                     for (int c = 0; c < COLS; c++) x[c] = r[c];
 #pragma unroll
-                    for (int c = 0; c < COLS; c++) fuse_add<NCC>(col[c], x[c]);
+                    for (int c = 0; c < COLS; c++) ps_add_packed<NCC>(col[c], x[c]);
                 }
-            fuse_sums win = fuse_sums{0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int c = 0; c < 2 * B + 1; c++) fuse_merge(win, col[c], 1);
-#pragma unroll
-            for (int v = 0; v < BRICK_VX; v++) {
-                out[v] = win;
-                if (v + 1 < BRICK_VX) {
-                    fuse_merge(win, col[v + 2 * B + 1], 1);
-                    fuse_merge(win, col[v], -1);
-                }
-            }
+            ps_slide<B, NCC>(col, out);
         } else {
 #pragma unroll
             for (int v = 0; v < BRICK_VX; v++) {
-                fuse_sums s = fuse_sums{0, 0, 0, 0, 0, 0, 0};
+                patch_sums s = patch_sums{0, 0, 0, 0, 0, 0, 0};
 #pragma unroll 1
                 for (int dz = 0; dz < side; dz++)
 #pragma unroll 1
                     for (int dy = 0; dy < side; dy++) {
                         const unsigned *r = row0 + dz * exy + dy * ex + v;
-                        for (int dx = 0; dx < side; dx++) fuse_add<NCC>(s, r[dx]);
+                        for (int dx = 0; dx < side; dx++) ps_add_packed<NCC>(s, r[dx]);
                     }
                 out[v] = s;
             }
@@ -162,7 +95,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_weight_kernel(const short *
         unsigned short *dst = u + (k * ny + j) * nx + i0;
 #pragma unroll
         for (int v = 0; v < BRICK_VX; v++)
-            if (i0 + v < nx) dst[v] = (unsigned short)(NCC ? fuse_u_ncc(out[v]) : fuse_u_ssd(out[v].n, out[v].d));
+            if (i0 + v < nx) dst[v] = (unsigned short)ps_u<NCC>(out[v]);
     }
 }
 

@@ -2,90 +2,27 @@
  * kernels_fuse_search.hip -- the local search of the label fusion for gfx950 (MI355X; tests/fuse_search_oracle.c
  * restates it as a serial brute force).  fuse_search_kernel<B, R, NCC> lets one warped atlas compare the target patch at every voxel
  * x with its own patches at x + t, t in [-r, r]^3, and keeps per voxel the similarity u, the shift code and the label of the best
- * candidate.  The sums are integers and the similarity is section 7j's (SSD: one integer division; NCC: section 7g's one sequence of
- * double operations), so no result depends on the tiling, the order of the additions or the wave layout.
+ * candidate.  The sums and the similarity are section 7j's (patch_sums.h, patch_cost.h), so no result depends on the tiling, the
+ * order of the additions or the wave layout.
  *
- * A workgroup of 256 threads owns warp_device.h's brick of 32 x 8 x 4 target voxels (a thread four consecutive x voxels, the bricks
- * dealt over the XCDs) and stages three tiles in LDS once per brick: qT with a halo of b and qW with a halo of b + r as int16 (-1:
- * outside the volume or not finite), and one byte per voxel with a halo of r that says whether the voxel may be picked (inside the
- * volume, and its label finite where there are labels).  Whether a patch voxel counts depends on the shift -- qT at x + v and qW at
- * x + t + v must both be valid -- so the validity is the sign of (qT | qW), tested per pair; section 7j's trick of staging the joint
- * validity does not carry over.
+ * The workgroup and its brick are fuse_weight_kernel's (kernels_fuse.hip).  It stages three tiles in LDS once per brick: qT with a
+ * halo of b and qW with a halo of b + r as int16 (-1: outside the volume or not finite), and one byte per voxel with a halo of r
+ * that says whether the voxel may be picked (inside the volume, and its label finite where there are labels).  Whether a patch
+ * voxel counts depends on the shift -- qT at x + v and qW at x + t + v must both be valid -- so the validity is tested per pair;
+ * the weight kernel's trick of staging the joint validity does not carry over.
  *   The loop over the shifts is outermost, z then y then x.  The running best of each of a thread's four voxels is one dword,
  *   u << 14 | (0x3fff - rank), rank = |t|^2 << 9 | (tz + r) << 6 | (ty + r) << 3 | (tx + r): the unsigned maximum is the contract's
  *   choice (largest u, then smallest |t|^2, tz, ty, tx), and 0 says that no shift was a candidate.
- *   B > 0 (b and r at compile time; instantiated for b = 2, r = 1, 2, 3): per shift and per row (dz, dy) of the patch a thread reads
- *   the 4 + 2b values of qT and of qW under its four windows once and adds each column's terms to that column's sums; after the
- *   (2b + 1)^2 rows the column sums slide into the four windows, as in fuse_weight_kernel<2, .>.
+ *   B > 0 (b and r at compile time; instantiated for b = 2, r = 1, 2, 3): the weight kernel's sliding form per shift, a row of qT
+ *   and a row of qW in place of its row of dwords.
  *   B = 0 (any b, r with b + r <= 6): every patch voxel straight from the tiles, per output voxel and shift.
- * Under SSD only n and D = sum (qT - qW)^2 are kept; under NCC all six sums.  n 2^15 < 2^27 and D + n < 2^32 (13^3 1023^2 + 13^3), so
- * the SSD quotient is a 32-bit division with the value of the contract's 64-bit one.
  * The picked label is gathered from the warped labels at x + t* by the same thread; no scratch, no LDS atomics, no float sums.
  */
 #include "sift3d_internal.h"
-#include "warp_device.h"
+#include "patch_sums.h"
 
 #define FS_THREADS 256
 #define FS_NONE 0xffffu /* in the u and the shift plane: the atlas does not vote here */
-
-struct fs_sums {
-    unsigned n, sf, sff, sw, sww, sfw, d;
-};
-
-__device__ __forceinline__ unsigned fs_u_ssd(unsigned n, unsigned d)
-{
-    if (n == 0) return 0;
-    return (n << 15) / (d + n);
-}
-
-/* section 7g's cost with n in place of N, then (2^31 - cost) >> 16: kernels_fuse.hip's sequence, operation for operation */
-__device__ __forceinline__ unsigned fs_u_ncc(const fs_sums &s)
-{
-    if (s.n == 0) return 0;
-    const long long N = s.n, Sf = s.sf, Sw = s.sw;
-    const long long A = N * (long long)s.sfw - Sf * Sw;
-    const long long Vf = N * (long long)s.sff - Sf * Sf;
-    const long long Vw = N * (long long)s.sww - Sw * Sw;
-    double q = 0.0;
-    if (A > 0 && Vf > 0 && Vw > 0) q = ((double)A * (double)A) / ((double)Vf * (double)Vw);
-    q = q > 1.0 ? 1.0 : q;
-    const unsigned c = (unsigned)rint((1.0 - q) * 2147483648.0);
-    return (0x80000000u - c) >> 16;
-}
-
-/* one pair (qT at x + v, qW at x + t + v) into the sums; it counts where neither value is -1 */
-template <int NCC> __device__ __forceinline__ void fs_add(fs_sums &s, int f, int w)
-{
-    const int m = (f | w) >> 31; /* -1: the pair does not count */
-    s.n += (unsigned)(1 + m);
-    if (NCC) {
-        f &= ~m;
-        w &= ~m;
-        s.sf += (unsigned)f;
-        s.sw += (unsigned)w;
-        s.sff += (unsigned)__mul24(f, f);
-        s.sww += (unsigned)__mul24(w, w);
-        s.sfw += (unsigned)__mul24(f, w);
-    } else {
-        const int d = (f - w) & ~m;
-        s.d += (unsigned)__mul24(d, d);
-    }
-}
-
-template <int NCC> __device__ __forceinline__ void fs_merge(fs_sums &a, const fs_sums &b, int sign)
-{
-    const unsigned m = sign < 0 ? ~0u : 0u; /* a += b or a -= b, modulo 2^32 */
-    a.n += (b.n ^ m) - m;
-    if (NCC) {
-        a.sf += (b.sf ^ m) - m;
-        a.sff += (b.sff ^ m) - m;
-        a.sw += (b.sw ^ m) - m;
-        a.sww += (b.sww ^ m) - m;
-        a.sfw += (b.sfw ^ m) - m;
-    } else {
-        a.d += (b.d ^ m) - m;
-    }
-}
 
 /* labels: the warped labels (float, not finite: may not be picked) or nullptr (every voxel inside the volume may be picked, and
  * picked is not written).  u, shift: one uint16 per voxel. */
@@ -149,12 +86,12 @@ __global__ __launch_bounds__(FS_THREADS) void fuse_search_kernel(const short *__
                     const unsigned rank = ((unsigned)(sz * sz + sy * sy + sx * sx) << 9) | ((unsigned)(sz + r) << 6) | ((unsigned)(sy + r) << 3) | (unsigned)(sx + r);
                     const short *ws = w0 + sz * wexy + sy * wex + sx;
                     const unsigned char *ms = m0 + sz * mexy + sy * mex + sx;
-                    fs_sums out[BRICK_VX];
+                    patch_sums out[BRICK_VX];
                     if constexpr (B > 0) {
                         constexpr int COLS = BRICK_VX + 2 * B;
-                        fs_sums col[COLS];
+                        patch_sums col[COLS];
 #pragma unroll
-                        for (int c = 0; c < COLS; c++) col[c] = fs_sums{0, 0, 0, 0, 0, 0, 0};
+                        for (int c = 0; c < COLS; c++) col[c] = patch_sums{0, 0, 0, 0, 0, 0, 0};
 #pragma unroll 1
                         for (int dz = 0; dz < 2 * B + 1; dz++)
 #pragma unroll 1
@@ -167,36 +104,26 @@ __global__ __launch_bounds__(FS_THREADS) void fuse_search_kernel(const short *__
                                     w[c] = rw[c];
                                 }
 #pragma unroll
-                                for (int c = 0; c < COLS; c++) fs_add<NCC>(col[c], f[c], w[c]);
+                                for (int c = 0; c < COLS; c++) ps_add<NCC>(col[c], f[c], w[c]);
                             }
-                        fs_sums win = fs_sums{0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                        for (int c = 0; c < 2 * B + 1; c++) fs_merge<NCC>(win, col[c], 1);
-#pragma unroll
-                        for (int v = 0; v < BRICK_VX; v++) {
-                            out[v] = win;
-                            if (v + 1 < BRICK_VX) {
-                                fs_merge<NCC>(win, col[v + 2 * B + 1], 1);
-                                fs_merge<NCC>(win, col[v], -1);
-                            }
-                        }
+                        ps_slide<B, NCC>(col, out);
                     } else {
 #pragma unroll
                         for (int v = 0; v < BRICK_VX; v++) {
-                            fs_sums s = fs_sums{0, 0, 0, 0, 0, 0, 0};
+                            patch_sums s = patch_sums{0, 0, 0, 0, 0, 0, 0};
 #pragma unroll 1
                             for (int dz = 0; dz < side; dz++)
 #pragma unroll 1
                                 for (int dy = 0; dy < side; dy++) {
                                     const short *rt = t0 + dz * texy + dy * tex + v, *rw = ws + dz * wexy + dy * wex + v;
-                                    for (int dx = 0; dx < side; dx++) fs_add<NCC>(s, rt[dx], rw[dx]);
+                                    for (int dx = 0; dx < side; dx++) ps_add<NCC>(s, rt[dx], rw[dx]);
                                 }
                             out[v] = s;
                         }
                     }
 #pragma unroll
                     for (int v = 0; v < BRICK_VX; v++) {
-                        const unsigned uv = NCC ? fs_u_ncc(out[v]) : fs_u_ssd(out[v].n, out[v].d);
+                        const unsigned uv = ps_u<NCC>(out[v]);
                         const unsigned key = ms[v] ? ((uv << 14) | (0x3fffu - rank)) : 0u;
                         best[v] = key > best[v] ? key : best[v];
                     }

@@ -159,6 +159,24 @@ def pair(shape, seed, holes=False):
     return T, W
 
 
+ZERO_SHIFT_SHAPE = (9, 11, 37)   # more than one brick of the fusion kernels along x, one brick and a voxel along y and z
+
+
+def assert_zero_shift_identity(metric, u, words, first):
+    """u: fuse_weights of (T, W) at b = 2; words: the block matcher's of the same pair at b = 2 on a lattice of stride 1 from first
+    (x, y, z).  An unflagged node's patch is whole, n = N = 125, and word 5 is the cost at the zero shift from the same sums: u is
+    (2^31 - cost) >> 16 under "ncc" and (125 << 15) // (cost + 125) under "ssd".  Not vacuously: more than 100 unflagged nodes, more
+    than one value on both sides."""
+    cz, cy, cx = words.shape[:3]
+    at = u[first[2]:first[2] + cz, first[1]:first[1] + cy, first[0]:first[0] + cx].astype(np.int64)
+    node = words[..., 3] == 0
+    got, cost = at[node], words[..., 5][node].astype(np.int64)
+    want = ((1 << 31) - cost) >> 16 if metric == "ncc" else (125 << 15) // (cost + 125)
+    print("zero shift %s: %d unflagged nodes, cost %d .. %d, u %d .. %d" % (metric, node.sum(), cost.min(), cost.max(), got.min(), got.max()))
+    assert node.sum() > 100 and len(np.unique(got)) > 1 and len(np.unique(cost)) > 1
+    assert np.array_equal(got, want), (metric, int((got != want).sum()))
+
+
 def ends_volumes(kind, shape, seed):
     """(T, W) of 0 and 1 alone, at the ends of the integer sums (blockmatch_cases.py): speckled (nearly every pair differs by the full
     range: D near n 1023^2, u = 0), speckled_holes (with NaN and infinite voxels in both), bright (Sff, Sww and Sfw beyond 2^31 at

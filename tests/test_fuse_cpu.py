@@ -10,7 +10,10 @@ import numpy as np
 import pytest
 
 from field_cases import FieldOracle
-from fuse_cases import ENDS, ENDS_SHAPE, FALLBACK, NONE, SUM_MAX_B6, U_ONE, FuseOracle, cpu_fuse, ends_volumes, fused_labels, leg, mean_dice, pair, scenario
+from blockmatch_cases import lattice_numpy
+from blockmatch_ncc_cases import NccOracle
+from fuse_cases import (ENDS, ENDS_SHAPE, FALLBACK, NONE, SUM_MAX_B6, U_ONE, ZERO_SHIFT_SHAPE, FuseOracle, assert_zero_shift_identity, cpu_fuse, ends_volumes,
+                        fused_labels, leg, mean_dice, pair, scenario)
 from resample_cases import ResampleOracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,6 +97,18 @@ def test_oracle_equals_numpy(fz, metric, shape, b, holes, kind):
         assert ((u == U_ONE) | ((u == 0) & (metric == "ncc"))).all() and (u == U_ONE).mean() > 0.9 and (D == 0).all() and (b < 6 or min(sums[..., i].max() for i in (2, 4, 5)) >= 2 ** 31)
     if kind == "bright" and metric == "ncc" and b == 6:   # A, Vf and Vw are small differences of large products, and no patch is flat
         assert ((u > 0) & (u < U_ONE)).mean() > 0.9 and len(np.unique(u)) > 100
+
+
+def test_weights_equal_the_block_matchers_cost_at_the_zero_shift(fz, tmp_path):
+    """The fusion's similarity and the block matcher's cost come from the same sums (patch_cost.h in the product): at an unflagged
+    lattice node the patch is whole (n = N = 125 at b = 2) and word 5 is the cost at the zero shift, so u = (2^31 - cost) >> 16
+    under NCC and (125 << 15) // (cost + 125) under SSD.  Here between the oracles alone (fuse_oracle.c, blockmatch_oracle.c,
+    blockmatch_ncc_oracle.c); test_gpu_fuse.py holds the kernels to the same identity."""
+    T, W = pair(ZERO_SHIFT_SHAPE, 5)
+    first, count = lattice_numpy(ZERO_SHIFT_SHAPE, 1, 2, 1)
+    no = NccOracle(tmp_path)
+    for metric, oracle in (("ssd", no.ssd), ("ncc", no)):
+        assert_zero_shift_identity(metric, fz.weights(T, W, 2, metric), oracle.match(T, W, first, 1, count, 2, 1), first)
 
 
 @pytest.mark.parametrize("metric", ["ssd", "ncc"])

@@ -9,7 +9,8 @@ import pytest
 
 from _helpers import run
 from field_cases import FieldOracle
-from fuse_cases import FALLBACK, NONE, U_ONE, FuseOracle, cpu_fuse, fused_labels, leg, pair, same_report, scenario
+from blockmatch_cases import lattice_numpy
+from fuse_cases import FALLBACK, NONE, U_ONE, ZERO_SHIFT_SHAPE, FuseOracle, assert_zero_shift_identity, cpu_fuse, fused_labels, leg, pair, same_report, scenario
 from resample_cases import ResampleOracle
 
 pytestmark = pytest.mark.gpu
@@ -80,6 +81,19 @@ def test_weights_with_holes_a_given_range_and_a_volume_of_nan(built, fz, metric,
     assert np.array_equal(got, fz.weights(T, nan, 2, metric)) and not got.any()
     got = built.fuse_weights(T, nan, block=2, metric=metric, w_range=rng, generic=generic)   # the kernel itself on a volume of -1
     assert not got.any()
+
+
+def test_weights_equal_the_block_matchers_cost_at_the_zero_shift(built):
+    """The weight kernel, the block matcher and the search take a patch's worth from one source (patch_cost.h), so they are held to
+    each other: fuse_cases.assert_zero_shift_identity between fuse_weights and the block matchers' words (both quantise T with T's
+    range, and W with W's own under "ncc" and with T's under "ssd"), and the search at radius 0 gives the weight kernel's u.
+    test_fuse_cpu.py has the same identity between the oracles."""
+    T, W = pair(ZERO_SHIFT_SHAPE, 5)
+    first, count = lattice_numpy(ZERO_SHIFT_SHAPE, 1, 2, 1)
+    for metric, match in (("ssd", built.block_match), ("ncc", built.block_match_ncc)):
+        u = built.fuse_weights(T, W, block=2, metric=metric)
+        assert_zero_shift_identity(metric, u, match(T, W, first, 1, count, 2, 1), first)
+        assert np.array_equal(built.fuse_search(T, W, block=2, radius=0, metric=metric)[0], u)
 
 
 def test_weights_of_identical_volumes_and_refusals(built):
