@@ -35,6 +35,7 @@ FEATRESAMPLE = os.path.join(CSRC, "_build", "featResample")
 FEATCOMPOSE = os.path.join(CSRC, "_build", "featCompose")
 FEATFUSE = os.path.join(CSRC, "_build", "featFuse")
 FEATOVERLAP = os.path.join(CSRC, "_build", "featOverlap")
+FEATCLEAN = os.path.join(CSRC, "_build", "featClean")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 6   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -193,6 +194,8 @@ def hip_lib():
     _sig(L.sift3d_fuse_labels_search, I, I, P, I64, I64, I64, P, C.c_int32, P, P, C.c_int32, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_distance_map, I, I, P, I64, I64, I64, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_surface_distances, I, P, P, I64, I64, I64, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_label_components, I, I, P, I64, I64, I64, C.c_int32, P, P, I64, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_clean_labels, I, P, I64, I64, I64, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -268,6 +271,10 @@ def host_lib():
     _sig(L.sift3d_surface_defaults, None, P)
     _sig(L.sift3d_spacing_um, I, F, P)
     _sig(L.sift3d_surface_stats, None, P, I64, P, I64, P)
+    _sig(L.sift3d_clean_defaults, None, P)
+    _sig(L.sift3d_ccl_check_extents, I, I64, I64, I64, C.c_char_p, I64)
+    _sig(L.sift3d_clean_check, I, P, C.c_char_p, I64)
+    _sig(L.sift3d_clean_report_text, I64, P, C.c_char_p, I64)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -1502,6 +1509,103 @@ def surface_distances(a, b, spacing=(1000, 1000, 1000), return_ms=False, **param
     _call("sift3d_surface_distances", a.ctypes.data, b.ctypes.data, nx, ny, nz, _spacing3(spacing), C.byref(p), rec, C.byref(n), C.byref(ms))
     out = [_surface_record_dict(rec[k]) for k in range(n.value)]
     return (out, ms.value) if return_ms else out
+
+
+# ---- connected components of a label volume and island removal (featClean), DESIGN.md section 7m ------------------------------------
+CCL_MAX_EXTENT, CCL_MAX_VOXELS, CLEAN_MAX_MIN_VOXELS, CLEAN_MAX_ROUNDS, CCL_STAGES = 4096, 1 << 30, 1 << 24, 16, 6
+COMPONENT_DTYPE = np.dtype([("label", "<i4"), ("reserved", "<i4"), ("voxels", "<i8"), ("first", "<i8"), ("box", "<i4", (6,))])   # sift3d_component_record
+CLEAN_ROUND_FIELDS = ("components", "small", "resolved", "resolved_voxels", "unresolved", "unresolved_voxels")
+
+
+class CleanParams(C.Structure):
+    """sift3d_clean_params"""
+    _fields_ = [("min_voxels", C.c_int32), ("connectivity", C.c_int32), ("rounds", C.c_int32), ("device", C.c_int32)]
+
+
+class CleanRound(C.Structure):
+    """sift3d_clean_round"""
+    _fields_ = [(name, C.c_int64) for name in CLEAN_ROUND_FIELDS]
+
+
+class CleanReport(C.Structure):
+    """sift3d_clean_report"""
+    _fields_ = [("rounds_run", C.c_int32), ("reserved", C.c_int32), ("round", CleanRound * CLEAN_MAX_ROUNDS), ("total", CleanRound)]
+
+
+def clean_params(**kw):
+    """sift3d_clean_defaults, then the given fields (min_voxels, connectivity, rounds, device)"""
+    p = CleanParams()
+    host_lib().sift3d_clean_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(CleanParams._fields_):
+            raise ValueError("no cleaning parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def clean_check(p):
+    """sift3d_clean_check: None, or the text with which the parameters are refused"""
+    err = C.create_string_buffer(512)
+    return None if host_lib().sift3d_clean_check(C.byref(p), err, len(err)) == 0 else err.value.decode()
+
+
+def clean_report_dict(rep):
+    """a sift3d_clean_report as {"rounds_run", "rounds": [one dict per round run], "total": dict}"""
+    row = lambda r: {k: int(getattr(r, k)) for k in CLEAN_ROUND_FIELDS}
+    return {"rounds_run": int(rep.rounds_run), "rounds": [row(rep.round[r]) for r in range(rep.rounds_run)], "total": row(rep.total)}
+
+
+def clean_report_text(rep):
+    """sift3d_clean_report_text of a CleanReport"""
+    buf = C.create_string_buffer(4096)
+    n = host_lib().sift3d_clean_report_text(C.byref(rep), buf, len(buf))
+    if n < 0 or n >= len(buf):
+        raise Sift3DError("sift3d_clean_report_text -> %d" % n)
+    return buf.value.decode()
+
+
+def label_components(labels, connectivity=6, device=0, max_records=None, return_ms=False):
+    """sift3d_label_components of a float32 label volume (nz, ny, nx): (comp, records) -- the component map, uint32 of that shape
+    (0: unlabelled), and the records as an array of COMPONENT_DTYPE in key order.  max_records: the room offered for records (None:
+    as many as there are components, by calling twice where the first guess is too small); an explicit value that is too small
+    raises with the count in the text and in .n_components, the map in .comp.  return_ms=True returns (comp, records, the
+    CCL_STAGES device ms: total, label plane, brick pass, border merge, flatten, numbers and records)."""
+    v = _f32(labels)
+    if v.ndim != 3:
+        raise ValueError("labels is a volume (nz, ny, nx)")
+    nz, ny, nx = v.shape
+    comp = np.zeros(v.shape, np.uint32)
+    room = 4096 if max_records is None else int(max_records)
+    while True:
+        rec = np.zeros(max(room, 1), COMPONENT_DTYPE)
+        n, ms = C.c_int64(0), (C.c_double * CCL_STAGES)()
+        try:
+            _call("sift3d_label_components", int(device), v.ctypes.data, nx, ny, nz, int(connectivity), comp.ctypes.data, rec.ctypes.data, room, C.byref(n), ms)
+        except Sift3DError as e:
+            if max_records is None and n.value > room:
+                room = n.value
+                continue
+            e.n_components, e.comp = n.value, comp
+            raise
+        rec = rec[:n.value].copy()
+        return (comp, rec, tuple(ms)) if return_ms else (comp, rec)
+
+
+def clean_labels(labels, return_ms=False, **params):
+    """sift3d_clean_labels of a float32 label volume (nz, ny, nx): (out, report) -- the cleaned labels, float32 of that shape, and
+    the report as clean_report_dict gives it (its CleanReport under "struct").  params: fields of clean_params.  return_ms=True
+    returns (out, report, the device ms of all rounds)."""
+    v = _f32(labels)
+    if v.ndim != 3:
+        raise ValueError("labels is a volume (nz, ny, nx)")
+    nz, ny, nx = v.shape
+    p = clean_params(**params)
+    out = np.zeros(v.shape, np.float32)
+    rep, ms = CleanReport(), C.c_double(0.0)
+    _call("sift3d_clean_labels", v.ctypes.data, nx, ny, nz, C.byref(p), out.ctypes.data, C.byref(rep), C.byref(ms))
+    d = clean_report_dict(rep)
+    d["struct"] = rep
+    return (out, d, ms.value) if return_ms else (out, d)
 
 
 def _map12(m):

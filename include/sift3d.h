@@ -1251,6 +1251,92 @@ int sift3d_spacing_um(float mm, uint32_t *um);
  * n_a = 0 or n_b = 0 the lists are not read and may be NULL.  rec's label and voxel counts are left as they are. */
 void sift3d_surface_stats(uint64_t *list_ab, int64_t n_a, uint64_t *list_ba, int64_t n_b, sift3d_surface_record *rec);
 
+/* ---- connected components of a label volume and island removal (featClean; beyond the reference) ------------------------------
+ * DESIGN.md section 7m states the contract; tests/ccl_oracle.c restates it as a serial flood fill.  Everything is integers, minima
+ * and counts: no result depends on tiling, launch order or the order atomics arrive in.
+ *
+ * Labels as in the fusion: a non-finite voxel is unlabelled, any other an integer 0 .. 65535 (0 is a label like any other: its
+ * components are the holes and the background).  Extents 1 .. SIFT3D_CCL_MAX_EXTENT each, at most 2^30 voxels.  connectivity: 6
+ * (faces) or 26 (faces, edges and corners).
+ * Components: two voxels are joined if they carry the same label and are neighbours under the connectivity; a component is a class
+ * of the transitive closure; unlabelled voxels belong to none.  A component's key is the smallest linear index (x fastest) of its
+ * voxels; components are numbered 1 .. n in ascending key order.  The map holds per voxel its component's number, 0 where the voxel
+ * is unlabelled.  The record of component k is records[k - 1].
+ * Cleaning, one round on the round's input L: a component with voxels < min_voxels is small, every other kept.  For every voxel x
+ * of a small component C and every face neighbour y of x (faces only, under both connectivities) that lies inside the volume and
+ * belongs to a kept component, votes[label(y)] grows by one.  C takes the label of the most votes, ties to the smaller label;
+ * without a vote C is unresolved and keeps its label.  Every decision reads L; the round's output is L with the voxels of resolved
+ * components rewritten as (float)label, every other voxel keeping its 32 bits.  Rounds repeat on the previous output until one
+ * resolves nothing or `rounds` have run; the round that resolves nothing is counted and reported.  min_voxels = 1 returns the input
+ * bit for bit. */
+#define SIFT3D_CCL_MAX_EXTENT 4096
+#define SIFT3D_CCL_MAX_VOXELS ((int64_t)1 << 30)
+#define SIFT3D_CLEAN_MAX_MIN_VOXELS (1 << 24)
+#define SIFT3D_CLEAN_MAX_ROUNDS 16
+#define SIFT3D_CLEAN_VOTE_BYTES ((int64_t)1 << 30) /* the budget of the vote table: small components x labels present x 4 bytes */
+/* kernel_ms of sift3d_label_components: total, label plane, brick pass, border merge, flatten, numbers and records */
+#define SIFT3D_CCL_STAGES 6
+
+typedef struct {
+    int32_t label;
+    int32_t reserved;
+    int64_t voxels;
+    int64_t first;  /* the key: the smallest linear index of the component's voxels */
+    int32_t box[6]; /* min x, max x, min y, max y, min z, max z, inclusive */
+} sift3d_component_record;
+
+typedef struct {
+    int32_t min_voxels;   /* 8: components below it are small; 1 .. 2^24 */
+    int32_t connectivity; /* 6; or 26 */
+    int32_t rounds;       /* 4; 1 .. 16 */
+    int32_t device;       /* 0 */
+} sift3d_clean_params;
+
+typedef struct {
+    int64_t components;        /* of the round's input */
+    int64_t small;             /* of them below min_voxels: resolved + unresolved */
+    int64_t resolved;          /* small components that took a neighbour's label */
+    int64_t resolved_voxels;   /* the voxels rewritten */
+    int64_t unresolved;        /* small components without a vote */
+    int64_t unresolved_voxels;
+} sift3d_clean_round;
+
+typedef struct {
+    int32_t rounds_run;
+    int32_t reserved;
+    sift3d_clean_round round[SIFT3D_CLEAN_MAX_ROUNDS];
+    /* components: those of the input; resolved and resolved_voxels: summed over the rounds; small, unresolved and
+     * unresolved_voxels: the last round's */
+    sift3d_clean_round total;
+} sift3d_clean_report;
+
+/* The components of a label volume on host arrays.  comp (may be NULL): one uint32 per voxel.  records (may be NULL: only the map
+ * and the count are wanted): room for max_records.  *n_components is always set once the volume has been labelled, and comp filled;
+ * with records given and n_components > max_records the call returns SIFT3D_ERR_ARG with the count in the text and writes no record,
+ * so that the caller can come back with room.  kernel_ms (may be NULL): SIFT3D_CCL_STAGES values of device time.  SIFT3D_ERR_ARG
+ * with text, checked before anything is allocated: an extent outside 1 .. 4096, more than 2^30 voxels, a connectivity other than 6
+ * or 26; then a voxel that sift3d_fuse_check_labels refuses, named. */
+int sift3d_label_components(int device, const float *labels, int64_t nx, int64_t ny, int64_t nz, int32_t connectivity, uint32_t *comp,
+                            sift3d_component_record *records, int64_t max_records, int64_t *n_components, double *kernel_ms, char *err,
+                            int64_t err_len);
+/* The cleaning on host arrays: out one float per voxel (may be labels itself).  p NULL: defaults.  report and kernel_ms (the device
+ * time of all rounds, each from its first launch to its last) may be NULL.  The device holds 22.125 bytes per voxel (the labels 4,
+ * the label plane 2.125, the parent, root and flag planes 12, the small indices 4; sift3d_label_components holds the first 18.125
+ * and 48 bytes per record) plus the vote table.  SIFT3D_ERR_ARG with text: what sift3d_label_components refuses, what
+ * sift3d_clean_check refuses, a vote table above
+ * SIFT3D_CLEAN_VOTE_BYTES (the small components, the labels and the bytes in the text). */
+int sift3d_clean_labels(const float *labels, int64_t nx, int64_t ny, int64_t nz, const sift3d_clean_params *p, float *out,
+                        sift3d_clean_report *report, double *kernel_ms, char *err, int64_t err_len);
+/* Host helpers (also in libsift3d_host.so). */
+void sift3d_clean_defaults(sift3d_clean_params *p);
+/* 0, or -1 and into err which extent is outside 1 .. 4096 or that the volume has more than 2^30 voxels */
+int sift3d_ccl_check_extents(int64_t nx, int64_t ny, int64_t nz, char *err, int64_t err_len);
+/* 0, or -1 and into err which of min_voxels, connectivity and rounds is refused, with its value and its range */
+int sift3d_clean_check(const sift3d_clean_params *p, char *err, int64_t err_len);
+/* The report as text: one commented header line, one line per round, one total line.  Returns the length the whole text needs
+ * (without the terminating 0), as snprintf does; buf holds at most len - 1 characters of it.  4096 bytes hold every report. */
+int64_t sift3d_clean_report_text(const sift3d_clean_report *rep, char *buf, int64_t len);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
