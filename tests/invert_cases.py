@@ -39,6 +39,8 @@ class InvertOracle:
         L.oiv_invert.argtypes = [P, P, P, P, P, F, P, P, F, C.c_int, F, P, P, P]
         L.oiv_jacobian.restype = None
         L.oiv_jacobian.argtypes = [I64, I64, I64, P, P, P, P, P, P, F, C.c_double, P]
+        L.oiv_jacobian_planes.restype = None
+        L.oiv_jacobian_planes.argtypes = [I64, I64, I64, P, P, P, P, P, P, F, C.c_double, I64, I64, P]
         self.L = L
 
     def affine_inverse(self, m):
@@ -59,12 +61,18 @@ class InvertOracle:
         shape = (int(n[2]), int(n[1]), int(n[0]))
         return u.reshape((3,) + shape), st.reshape(shape), r2.reshape(shape)
 
-    def jacobian(self, out_shape, A, Cm, K, field, factor):
+    def jacobian(self, out_shape, A, Cm, K, field, factor, z0=0, z1=None):
+        """the map on out_shape = (oz, oy, ox); with z0, z1: its planes [z0, z1) alone"""
         oz, oy, ox = (int(d) for d in out_shape)
-        out = np.empty((oz, oy, ox), np.float32)
         a, c, k = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (A, Cm, K))
         fd, fn, fo, fh, _keep = _field_args(field)
-        self.L.oiv_jacobian(ox, oy, oz, a.ctypes.data, c.ctypes.data, k.ctypes.data, fd, fn, fo, fh, float(factor), out.ctypes.data)
+        if z0 == 0 and z1 is None:
+            out = np.empty((oz, oy, ox), np.float32)
+            self.L.oiv_jacobian(ox, oy, oz, a.ctypes.data, c.ctypes.data, k.ctypes.data, fd, fn, fo, fh, float(factor), out.ctypes.data)
+            return out
+        z0, z1 = max(int(z0), 0), oz if z1 is None else min(int(z1), oz)
+        out = np.empty((z1 - z0, oy, ox), np.float32)
+        self.L.oiv_jacobian_planes(ox, oy, oz, a.ctypes.data, c.ctypes.data, k.ctypes.data, fd, fn, fo, fh, float(factor), z0, z1, out.ctypes.data)
         return out
 
 

@@ -150,9 +150,10 @@ static void warp_q(const float *map, const float *cm, const float *km, const fie
     for (int r = 0; r < 3; r++) q[r] = q[r] + ((km[3 * r] * v[0] + km[3 * r + 1] * v[1]) + km[3 * r + 2] * v[2]);
 }
 
-/* J on the output grid ox oy oz: central differences of q over one voxel, the determinant in double, times factor */
-void oiv_jacobian(int64_t ox, int64_t oy, int64_t oz, const float *map, const float *cm, const float *km, const float *fdisp, const int64_t *fn,
-                  const float *fo, float fh, double factor, float *out)
+/* J on the planes z0 .. z1 - 1 of the output grid ox oy oz (out holds those planes alone): central differences of q over one
+ * voxel, the determinant in double, times factor */
+void oiv_jacobian_planes(int64_t ox, int64_t oy, int64_t oz, const float *map, const float *cm, const float *km, const float *fdisp,
+                         const int64_t *fn, const float *fo, float fh, double factor, int64_t z0, int64_t z1, float *out)
 {
     field f;
     memset(&f, 0, sizeof f);
@@ -163,7 +164,9 @@ void oiv_jacobian(int64_t ox, int64_t oy, int64_t oz, const float *map, const fl
             f.o[k] = fo[k];
         }
     f.h = fh;
-    for (int64_t k = 0; k < oz; k++)
+    if (z0 < 0) z0 = 0;
+    if (z1 > oz) z1 = oz;
+    for (int64_t k = z0; k < z1; k++)
         for (int64_t j = 0; j < oy; j++)
             for (int64_t i = 0; i < ox; i++) {
                 const int64_t at[3] = {i, j, k};
@@ -177,6 +180,13 @@ void oiv_jacobian(int64_t ox, int64_t oy, int64_t oz, const float *map, const fl
                     for (int r = 0; r < 3; r++) J[3 * r + a] = (double)((qp[r] - qm[r]) * 0.5f);
                 }
                 const double det = J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) + J[2] * (J[3] * J[7] - J[4] * J[6]);
-                out[(k * oy + j) * ox + i] = (float)(det * factor);
+                out[((k - z0) * oy + j) * ox + i] = (float)(det * factor);
             }
+}
+
+/* J on the whole output grid */
+void oiv_jacobian(int64_t ox, int64_t oy, int64_t oz, const float *map, const float *cm, const float *km, const float *fdisp, const int64_t *fn,
+                  const float *fo, float fh, double factor, float *out)
+{
+    oiv_jacobian_planes(ox, oy, oz, map, cm, km, fdisp, fn, fo, fh, factor, 0, oz, out);
 }
