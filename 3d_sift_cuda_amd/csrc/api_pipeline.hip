@@ -408,7 +408,7 @@ static int describe_begin(sift3d_ctx *c, size_t nlevels, float *taps3)
 {
     if (sift3d_gauss_taps(0.5f, 0.01f, taps3) != 3 || sift3d_gauss_taps((float)0.95, (float)0.01, c->kp.taps5) != 5)
         return set_err(c, SIFT3D_ERR_ARG, "unexpected patch tap counts");
-    if (nlevels > 96) return set_err(c, SIFT3D_ERR_ARG, "too many levels");
+    if (nlevels > SIFT3D_MAX_LEVELS) return set_err(c, SIFT3D_ERR_ARG, "too many levels");
     c->kp.ncand = 0;
     c->kp.nchunks = 0;
     c->kp.launched = 0;
@@ -810,7 +810,7 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
     }
     /* split tail: the table goes to the device now, on the stream the first part's keypoint kernel will run on, instead of
      * between that part's count and its sort */
-    if (split_tail && levels.size() <= 96)
+    if (split_tail && levels.size() <= SIFT3D_MAX_LEVELS)
         HIPCHK(c, hipMemcpyAsync(c->d_levels, levels.data(), sizeof(sift3d_level) * levels.size(), hipMemcpyHostToDevice, c->kp_stream));
     /* the filter that makes L_5 from L_4: the lazy form of D_4 applies it around the candidates of D_3 only */
     float next_taps[SIFT3D_MAX_TAPS];
@@ -963,7 +963,7 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
     }
     if (split_tail) {
         bool done = false;
-        rc = finish_split_tail(c, levels, levels.size() <= 96, desc_mode, eig_thres, size_factor, n_out, &done);
+        rc = finish_split_tail(c, levels, levels.size() <= SIFT3D_MAX_LEVELS, desc_mode, eig_thres, size_factor, n_out, &done);
         if (rc) return rc;
         if (done) {
             *feats_out = c->h_recs; /* pinned, owned by the context */
@@ -972,7 +972,7 @@ static int run_pipeline(sift3d_ctx *c, float init_scale, bool extract, int desc_
         /* fell back: every stream is idle, the extrema launches were replayed into one list on the main stream */
     }
     /* the level table goes to the device now, behind the pyramid, not after the host has waited for the extrema count */
-    const bool levels_early = extract && levels.size() <= 96;
+    const bool levels_early = extract && levels.size() <= SIFT3D_MAX_LEVELS;
     if (levels_early)
         HIPCHK(c, hipMemcpyAsync(c->d_levels, levels.data(), sizeof(sift3d_level) * levels.size(), hipMemcpyHostToDevice, c->stream));
     int64_t ncand = 0;

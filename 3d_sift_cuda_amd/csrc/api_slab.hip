@@ -35,7 +35,7 @@ extern "C" int sift3d_extrema_append_dev(sift3d_ctx *c, const float *d_prev, con
 {
     if (!c || !d_prev || !d_cur || !d_next) return SIFT3D_ERR_ARG;
     if (nx <= 0 || ny <= 0 || nz_local <= 0 || nx >= (1ll << 31) || ny >= (1ll << 31) || nz_local >= 65538 ||
-        nx * ny * nz_local > (int64_t)SIFT3D_KEY_IDX_MASK || level_id < 0 || level_id >= 96)
+        nx * ny * nz_local > (int64_t)SIFT3D_KEY_IDX_MASK || level_id < 0 || level_id >= SIFT3D_MAX_LEVELS)
         return set_err(c, SIFT3D_ERR_ARG, "bad extrema_append arguments");
     HIPCHK(c, hipSetDevice(c->device));
     int rc = fence_in(c);
@@ -57,7 +57,7 @@ extern "C" int sift3d_extrema_append_lazy_dev(sift3d_ctx *c, const float *d_prev
 {
     if (!c || !d_cur || (!d_prev && !(g_prev_a && g_prev_b)) || (!d_next && !g_next)) return SIFT3D_ERR_ARG;
     if (nx <= 0 || ny <= 0 || nz_local <= 0 || nx >= (1ll << 31) || ny >= (1ll << 31) || nz_local >= 65538 ||
-        nx * ny * nz_local > (int64_t)SIFT3D_KEY_IDX_MASK || level_id < 0 || level_id >= 96)
+        nx * ny * nz_local > (int64_t)SIFT3D_KEY_IDX_MASK || level_id < 0 || level_id >= SIFT3D_MAX_LEVELS)
         return set_err(c, SIFT3D_ERR_ARG, "bad extrema_append arguments");
     float taps[SIFT3D_MAX_TAPS];
     const int ntaps = d_next ? 0 : sift3d_gauss_taps(next_sigma, 0.01f, taps);
@@ -80,7 +80,7 @@ extern "C" int sift3d_extrema_append_lazy_dev(sift3d_ctx *c, const float *d_prev
 
 static int levels_from_desc(sift3d_ctx *c, const sift3d_level_desc *ld, int n, std::vector<sift3d_level> &levels)
 {
-    if (!ld || n <= 0 || n > 96) return set_err(c, SIFT3D_ERR_ARG, "bad level table");
+    if (!ld || n <= 0 || n > SIFT3D_MAX_LEVELS) return set_err(c, SIFT3D_ERR_ARG, "bad level table");
     levels.resize((size_t)n);
     for (int i = 0; i < n; i++) {
         sift3d_level &lv = levels[(size_t)i];

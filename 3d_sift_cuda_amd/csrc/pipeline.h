@@ -18,6 +18,8 @@
  * workgroup only becomes resident where a keypoint workgroup has retired, and the two kernels take turns instead of sharing. */
 #define SIFT3D_KP_DEFAULT_CHUNKS 1
 #define SIFT3D_D4TINY_FLOATS 32768 /* room for the octaves of at most SIFT3D_TINY_VOX voxels of one volume, pitched rows included */
+#define SIFT3D_MAX_LEVELS 96 /* rows of the device level table (sift3d_ctx::d_levels): three detection levels of 32 octaves */
+static_assert(SIFT3D_GROUPS == 2 * SIFT3D_MAX_LEVELS + 1, "a group per (level, is_max) and one for anything beyond the table");
 
 struct timed_launch {
     int stage;
@@ -149,7 +151,7 @@ struct sift3d_ctx {
     unsigned long long *keys_a, *keys_b;
     sift3d_cval *vals_a, *vals_b;
     int64_t cand_cap;
-    unsigned long long *d_count; /* [0] validated extrema, [1] own-level survivors of the level in flight, [2] survivor overflow high-water
+    unsigned long long *d_count; /* [0] validated extrema, [1] unused (every extrema pass counts in a set of surv_counts), [2] survivor overflow high-water
                                   * mark, [3] keypoints, [4] validated extrema of the second group (split tail) */
     int64_t cand_split_at;       /* 0: one list in keys_a / vals_a; n > 0: entries [0, n) take the first group's extrema (counter [0]), [n, cand_cap)
                                   * the second group's (counter [4]) -- run_pipeline's split tail */
