@@ -20,6 +20,7 @@ dlopen'ed on first use), but every compute call raises if the HIP library is
 missing or no HIP device is usable.  The package name starts with a digit, so
 load it with ``importlib.import_module("3d_sift_cuda_amd")``.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -133,6 +134,7 @@ def hip_lib():
     _sig(L.sift3d_double_size, I, P, P, I64, I64, I64, P)
     _sig(L.sift3d_halve_size, I, P, P, I64, I64, I64, P)
     _sig(L.sift3d_selftest_lds_add, I, P, P, P, I64, P, P)
+    _sig(L.sift3d_selftest_alloc_fill, I, I, C.POINTER(C.c_uint64))
     _sig(L.sift3d_set_volume, I, P, P, I64, I64, I64)
     _sig(L.sift3d_set_volume_dev, I, P, P, I64, I64, I64)
     _sig(L.sift3d_set_volume_resized, I, P, P, I64, I64, I64, I)
@@ -414,6 +416,29 @@ def host_unregister(address):
 
 def device_count():
     return int(hip_lib().sift3d_device_count())
+
+
+def _alloc_fill(byte):
+    stats = (C.c_uint64 * 2)()
+    rc = hip_lib().sift3d_selftest_alloc_fill(int(byte), stats)
+    if rc != 0:
+        raise Sift3DError("sift3d_selftest_alloc_fill(%d) failed (%d): a block of the allocator did not hold the fill byte" % (byte, rc))
+    return int(stats[0]), int(stats[1])
+
+
+@contextlib.contextmanager
+def alloc_fill(byte):
+    """sift3d_selftest_alloc_fill (include/sift3d_dev.h): inside the block every device and pinned host allocation of the
+    library, in any thread, is filled with `byte` (0..255) before the library uses it; the fill is off again afterwards.
+    Yields a function that returns (blocks, bytes) filled since it was last called.  For tests: a result must not depend
+    on what an allocation held.  Each fill waits for the device, so nothing timed belongs inside."""
+    if not 0 <= int(byte) <= 255:
+        raise ValueError("fill byte %r is not in 0..255" % (byte,))
+    _alloc_fill(byte)
+    try:
+        yield lambda: _alloc_fill(byte)
+    finally:
+        _alloc_fill(-1)
 
 
 # ---- matcher (SURVEY.md section 8f-3): exact nearest neighbours on the GPU, votes on the host ---------------------------

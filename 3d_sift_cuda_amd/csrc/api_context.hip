@@ -108,10 +108,10 @@ int alloc_cands(sift3d_ctx *c, int64_t cap)
     sift3d_cval *va = nullptr, *vb = nullptr;
     void *tmp = nullptr;
     const size_t tmp_bytes = sift3d_sort_temp_bytes(cap) + 256;
-    const bool ok = hipMalloc((void **)&ka, sizeof(unsigned long long) * (size_t)cap) == hipSuccess &&
-                    hipMalloc((void **)&kb, sizeof(unsigned long long) * (size_t)cap) == hipSuccess &&
-                    hipMalloc((void **)&va, sizeof(sift3d_cval) * (size_t)cap) == hipSuccess &&
-                    hipMalloc((void **)&vb, sizeof(sift3d_cval) * (size_t)cap) == hipSuccess && hipMalloc(&tmp, tmp_bytes) == hipSuccess;
+    const bool ok = sift3d_alloc_device((void **)&ka, sizeof(unsigned long long) * (size_t)cap) == hipSuccess &&
+                    sift3d_alloc_device((void **)&kb, sizeof(unsigned long long) * (size_t)cap) == hipSuccess &&
+                    sift3d_alloc_device((void **)&va, sizeof(sift3d_cval) * (size_t)cap) == hipSuccess &&
+                    sift3d_alloc_device((void **)&vb, sizeof(sift3d_cval) * (size_t)cap) == hipSuccess && sift3d_alloc_device(&tmp, tmp_bytes) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         hipFree(ka); hipFree(kb); hipFree(va); hipFree(vb); hipFree(tmp);
@@ -176,17 +176,17 @@ sift3d_ctx *ctx_create(int device, int64_t nx, int64_t ny, int64_t nz, bool lean
                             &c->ev_split[0], &c->ev_split[1], &c->ev_split[2]};
     for (hipEvent_t *e : events) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     for (hipEvent_t &e : c->ev_kpc) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&c->h_cnt0, sizeof(unsigned long long) * (16 + SIFT3D_KP_MAX_CHUNKS), hipHostMallocDefault) == hipSuccess;
+    ok = ok && sift3d_alloc_host((void **)&c->h_cnt0, sizeof(unsigned long long) * (16 + SIFT3D_KP_MAX_CHUNKS), hipHostMallocDefault) == hipSuccess;
     const size_t vb = sizeof(float) * (size_t)c->capN;
     const size_t tb = sizeof(float) * (size_t)c->capTot;
     /* nothing may depend on what hipMalloc hands back: the pad columns of pitched octaves are read as zeros.  The clears
      * go on the context's own stream and are waited for here: hipMemset runs on the null stream, which the context's
      * non-blocking streams are NOT ordered with, so it could still be wiping a buffer the first extraction already uses */
     if (!lean) {
-        ok = ok && hipMalloc((void **)&c->vol, vb) == hipSuccess && hipMemsetAsync(c->vol, 0, vb, c->stream) == hipSuccess;
-        for (int i = 0; i < 5 && ok; i++) ok = hipMalloc((void **)&c->L[i], tb) == hipSuccess && hipMemsetAsync(c->L[i], 0, tb, c->stream) == hipSuccess;
-        for (int i = 0; i < 4 && ok; i++) ok = hipMalloc((void **)&c->D[i], tb) == hipSuccess && hipMemsetAsync(c->D[i], 0, tb, c->stream) == hipSuccess;
-        ok = ok && hipMalloc((void **)&c->D4tiny, sizeof(float) * SIFT3D_D4TINY_FLOATS) == hipSuccess &&
+        ok = ok && sift3d_alloc_device((void **)&c->vol, vb) == hipSuccess && hipMemsetAsync(c->vol, 0, vb, c->stream) == hipSuccess;
+        for (int i = 0; i < 5 && ok; i++) ok = sift3d_alloc_device((void **)&c->L[i], tb) == hipSuccess && hipMemsetAsync(c->L[i], 0, tb, c->stream) == hipSuccess;
+        for (int i = 0; i < 4 && ok; i++) ok = sift3d_alloc_device((void **)&c->D[i], tb) == hipSuccess && hipMemsetAsync(c->D[i], 0, tb, c->stream) == hipSuccess;
+        ok = ok && sift3d_alloc_device((void **)&c->D4tiny, sizeof(float) * SIFT3D_D4TINY_FLOATS) == hipSuccess &&
              hipMemsetAsync(c->D4tiny, 0, sizeof(float) * SIFT3D_D4TINY_FLOATS, c->stream) == hipSuccess;
     }
     /* the two pass intermediates of the three-launch blur: allocated here for the volumes the numbers are quoted on; a
@@ -194,20 +194,20 @@ sift3d_ctx *ctx_create(int device, int64_t nx, int64_t ny, int64_t nz, bool lean
      * through the one-launch kernel, the coarse octaves need an eighth) -- 2 x 17 GB less at config C5's 2^32 voxels */
     if (c->capN <= SIFT3D_EAGER_T_FLOATS)
         for (int i = 0; i < 2 && ok; i++) {
-            ok = hipMalloc((void **)&c->T[i], vb) == hipSuccess;
+            ok = sift3d_alloc_device((void **)&c->T[i], vb) == hipSuccess;
             if (ok) c->capT = c->capN;
         }
-    ok = ok && hipMalloc((void **)&c->d_taps, sizeof(float) * SIFT3D_MAX_TAPS) == hipSuccess;
-    ok = ok && hipMalloc((void **)&c->d_count, sizeof(unsigned long long) * 8) == hipSuccess;
-    ok = ok && hipMalloc((void **)&c->d_levels, sizeof(sift3d_level) * SIFT3D_MAX_LEVELS) == hipSuccess;
-    ok = ok && hipMalloc((void **)&c->sampler_tokens, sizeof(int) * SIFT3D_CU_SLOTS) == hipSuccess &&
+    ok = ok && sift3d_alloc_device((void **)&c->d_taps, sizeof(float) * SIFT3D_MAX_TAPS) == hipSuccess;
+    ok = ok && sift3d_alloc_device((void **)&c->d_count, sizeof(unsigned long long) * 8) == hipSuccess;
+    ok = ok && sift3d_alloc_device((void **)&c->d_levels, sizeof(sift3d_level) * SIFT3D_MAX_LEVELS) == hipSuccess;
+    ok = ok && sift3d_alloc_device((void **)&c->sampler_tokens, sizeof(int) * SIFT3D_CU_SLOTS) == hipSuccess &&
          hipMemsetAsync(c->sampler_tokens, 0, sizeof(int) * SIFT3D_CU_SLOTS, c->stream) == hipSuccess;
-    ok = ok && hipMalloc((void **)&c->d_rec_base, sizeof(int) * (SIFT3D_KP_MAX_CHUNKS + 1)) == hipSuccess;
+    ok = ok && sift3d_alloc_device((void **)&c->d_rec_base, sizeof(int) * (SIFT3D_KP_MAX_CHUNKS + 1)) == hipSuccess;
     ok = ok && alloc_cands(c, c->capN / 32 + 8192) == SIFT3D_OK;
     c->surv_cap = c->capN / 8 + 65536; /* own-level extrema are ~0.3 % of the voxels on blob fields, ~1 % on noise */
-    ok = ok && hipMalloc((void **)&c->surv, sizeof(sift3d_survivor) * (size_t)c->surv_cap) == hipSuccess;
-    ok = ok && hipMalloc((void **)&c->surv_counts, sizeof(unsigned long long) * SIFT3D_SURV_COUNTERS * SIFT3D_SURV_SETS) == hipSuccess;
-    ok = ok && hipMalloc((void **)&c->list2_counts, sizeof(unsigned long long) * SIFT3D_LIST2_COUNTERS * SIFT3D_SURV_SETS) == hipSuccess;
+    ok = ok && sift3d_alloc_device((void **)&c->surv, sizeof(sift3d_survivor) * (size_t)c->surv_cap) == hipSuccess;
+    ok = ok && sift3d_alloc_device((void **)&c->surv_counts, sizeof(unsigned long long) * SIFT3D_SURV_COUNTERS * SIFT3D_SURV_SETS) == hipSuccess;
+    ok = ok && sift3d_alloc_device((void **)&c->list2_counts, sizeof(unsigned long long) * SIFT3D_LIST2_COUNTERS * SIFT3D_SURV_SETS) == hipSuccess;
     ok = ok && hipStreamSynchronize(c->stream) == hipSuccess; /* the clears above are done before the context is handed out */
     if (!ok) {
         free_dev(c);
@@ -337,7 +337,7 @@ int ensure_T(sift3d_ctx *c, int64_t floats)
     if (want < floats) want = floats;
     if (want > c->capN) want = c->capN;
     for (int i = 0; i < 2; i++)
-        if (hipMalloc((void **)&c->T[i], sizeof(float) * (size_t)want) != hipSuccess) {
+        if (sift3d_alloc_device((void **)&c->T[i], sizeof(float) * (size_t)want) != hipSuccess) {
             (void)hipGetLastError();
             return set_err(c, SIFT3D_ERR_MEMORY, "out of device memory for the pass intermediates (%lld floats)", (long long)want);
         }

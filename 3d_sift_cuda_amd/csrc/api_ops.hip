@@ -347,7 +347,7 @@ int cand_append(sift3d_ctx *c, const level_job &j, const cand_where &w, bool rec
             hipFree(c->surv2);
             c->surv2 = nullptr;
             c->surv2_cap = 0;
-            HIPCHK(c, hipMalloc((void **)&c->surv2, sizeof(sift3d_survivor) * (size_t)cover));
+            HIPCHK(c, sift3d_alloc_device((void **)&c->surv2, sizeof(sift3d_survivor) * (size_t)cover));
             c->surv2_cap = cover;
         }
         surv = c->surv2;
@@ -369,7 +369,7 @@ int cand_append(sift3d_ctx *c, const level_job &j, const cand_where &w, bool rec
                 hipFree(c->list2[li]);
                 c->list2[li] = nullptr;
                 c->list2_cap[li] = 0;
-                HIPCHK(c, hipMalloc((void **)&c->list2[li], sizeof(sift3d_survivor2) * (size_t)cover));
+                HIPCHK(c, sift3d_alloc_device((void **)&c->list2[li], sizeof(sift3d_survivor2) * (size_t)cover));
                 c->list2_cap[li] = cover;
             }
             lz.ntaps = j.next_ntaps;
@@ -419,7 +419,7 @@ int surv_make_room(sift3d_ctx *c, unsigned long long high_water)
         hipFree(c->surv);
         c->surv = nullptr;
         c->surv_cap = (int64_t)high_water + (int64_t)high_water / 4 + 4096;
-        HIPCHK(c, hipMalloc((void **)&c->surv, sizeof(sift3d_survivor) * (size_t)c->surv_cap));
+        HIPCHK(c, sift3d_alloc_device((void **)&c->surv, sizeof(sift3d_survivor) * (size_t)c->surv_cap));
     }
     return SIFT3D_OK;
 }

@@ -43,7 +43,7 @@
 static int ensure_level_buffer(sift3d_ctx *c, float **buf)
 {
     if (*buf) return SIFT3D_OK;
-    if (hipMalloc((void **)buf, sizeof(float) * (size_t)c->capTot) != hipSuccess) {
+    if (sift3d_alloc_device((void **)buf, sizeof(float) * (size_t)c->capTot) != hipSuccess) {
         *buf = nullptr;
         return set_err(c, SIFT3D_ERR_MEMORY, "a level buffer of %lld floats could not be allocated", (long long)c->capTot);
     }
@@ -252,8 +252,8 @@ static int ensure_host_records(sift3d_ctx *c, int64_t need, int64_t keep)
     sift3d_feature *nr = nullptr;
     int *ng = nullptr;
     const int64_t cap = need + need / 8 + 1024;
-    HIPCHK(c, hipHostMalloc((void **)&nr, sizeof(sift3d_feature) * (size_t)cap, hipHostMallocDefault));
-    if (hipHostMalloc((void **)&ng, sizeof(int) * (size_t)cap, hipHostMallocDefault) != hipSuccess) {
+    HIPCHK(c, sift3d_alloc_host((void **)&nr, sizeof(sift3d_feature) * (size_t)cap, hipHostMallocDefault));
+    if (sift3d_alloc_host((void **)&ng, sizeof(int) * (size_t)cap, hipHostMallocDefault) != hipSuccess) {
         hipHostFree(nr);
         return set_err(c, SIFT3D_ERR_MEMORY, "out of pinned host memory for %lld records", (long long)cap);
     }
@@ -291,13 +291,13 @@ static int ensure_kp_buffers(sift3d_ctx *c, int64_t ncand, int64_t host_for = -1
         c->kps_cap = 0;
         const int64_t cap = ncand + ncand / 2 + 1024, rcap = cap * (1 + SIFT3D_MAX_FRAMES);
         c->scan_tmp_bytes = sift3d_scan_temp_bytes(cap) + 256;
-        HIPCHK(c, hipMalloc((void **)&c->kps, sizeof(sift3d_dkp) * (size_t)cap));
-        HIPCHK(c, hipMalloc((void **)&c->patch0, sizeof(float) * SIFT3D_PATCH_VOX * (size_t)cap));
-        HIPCHK(c, hipMalloc((void **)&c->nrec, sizeof(int) * (size_t)cap));
-        HIPCHK(c, hipMalloc((void **)&c->offs, sizeof(int) * (size_t)cap));
-        HIPCHK(c, hipMalloc(&c->scan_tmp, c->scan_tmp_bytes));
-        HIPCHK(c, hipMalloc((void **)&c->rec_kp, sizeof(int) * (size_t)rcap));
-        HIPCHK(c, hipMalloc((void **)&c->rec_frame, sizeof(int) * (size_t)rcap));
+        HIPCHK(c, sift3d_alloc_device((void **)&c->kps, sizeof(sift3d_dkp) * (size_t)cap));
+        HIPCHK(c, sift3d_alloc_device((void **)&c->patch0, sizeof(float) * SIFT3D_PATCH_VOX * (size_t)cap));
+        HIPCHK(c, sift3d_alloc_device((void **)&c->nrec, sizeof(int) * (size_t)cap));
+        HIPCHK(c, sift3d_alloc_device((void **)&c->offs, sizeof(int) * (size_t)cap));
+        HIPCHK(c, sift3d_alloc_device(&c->scan_tmp, c->scan_tmp_bytes));
+        HIPCHK(c, sift3d_alloc_device((void **)&c->rec_kp, sizeof(int) * (size_t)rcap));
+        HIPCHK(c, sift3d_alloc_device((void **)&c->rec_frame, sizeof(int) * (size_t)rcap));
         c->kps_cap = cap;
         c->recs_cap = rcap;
     }
@@ -423,9 +423,9 @@ void describe_want_group_counts(sift3d_ctx *c, bool on) { c->place.counts = on; 
 static int ensure_place_buffers(sift3d_ctx *c)
 {
     if (c->place.d_counts) return SIFT3D_OK;
-    HIPCHK(c, hipMalloc((void **)&c->place.d_counts, sizeof(int) * SIFT3D_GROUPS));
-    HIPCHK(c, hipMalloc((void **)&c->place.d_shift, sizeof(int) * SIFT3D_GROUPS));
-    HIPCHK(c, hipHostMalloc((void **)&c->place.h_counts, sizeof(int) * SIFT3D_GROUPS, hipHostMallocDefault));
+    HIPCHK(c, sift3d_alloc_device((void **)&c->place.d_counts, sizeof(int) * SIFT3D_GROUPS));
+    HIPCHK(c, sift3d_alloc_device((void **)&c->place.d_shift, sizeof(int) * SIFT3D_GROUPS));
+    HIPCHK(c, sift3d_alloc_host((void **)&c->place.h_counts, sizeof(int) * SIFT3D_GROUPS, hipHostMallocDefault));
     return SIFT3D_OK;
 }
 

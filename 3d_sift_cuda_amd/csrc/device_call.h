@@ -67,7 +67,7 @@ struct device_call {
     /* n elements, freed with the call */
     template <class T> hipError_t alloc(T **d, size_t n)
     {
-        const hipError_t e = hipMalloc((void **)d, sizeof(T) * n);
+        const hipError_t e = sift3d_alloc_device((void **)d, sizeof(T) * n);
         if (e == hipSuccess) bufs.push_back((void *)*d);
         return e;
     }

@@ -76,6 +76,15 @@ struct sift3d_level {
     int pad;
 };
 
+/* ---- allocation (alloc_fill.hip): every device and pinned host block of the library comes through these, so that the fill
+ * hook of sift3d_selftest_alloc_fill sees it.  Released with hipFree / hipHostFree as before. ---- */
+#pragma GCC visibility push(hidden)
+hipError_t sift3d_alloc_device(void **p, size_t bytes);
+hipError_t sift3d_alloc_host(void **p, size_t bytes, unsigned flags);
+/* a piece cut from a block the caller keeps from run to run (the slab rank's arena): filled like a new block when the hook is on */
+hipError_t sift3d_alloc_reused(void *p, size_t bytes);
+#pragma GCC visibility pop
+
 /* ---- kernel launchers (kernels_volume.hip; the fused blur: kernels_blur_fused.hip) ---- */
 hipError_t sift3d_launch_blur_x(hipStream_t s, const float *in, float *out, int64_t X, int64_t Y, int64_t Z,
                                 const float *taps, int ntaps, const float *d_taps);

@@ -135,10 +135,11 @@ struct zs_rank {
         if (arena && arena_used + nfloats <= arena_cap) {
             float *p = arena + arena_used;
             arena_used += nfloats;
-            return p;
+            /* the arena keeps last run's floats: under the allocator's fill hook a piece of it is filled like a new block */
+            return sift3d_alloc_reused(p, sizeof(float) * (size_t)nfloats) == hipSuccess ? p : nullptr;
         }
         float *p = nullptr;
-        if (hipMalloc((void **)&p, sizeof(float) * (size_t)nfloats) != hipSuccess) return nullptr;
+        if (sift3d_alloc_device((void **)&p, sizeof(float) * (size_t)nfloats) != hipSuccess) return nullptr;
         allocs.push_back(p);
         return p;
     }
@@ -151,7 +152,7 @@ struct zs_rank {
             hipFree(arena);
             arena = nullptr;
             arena_cap = 0;
-            if (hipMalloc((void **)&arena, sizeof(float) * (size_t)need) == hipSuccess) arena_cap = need;
+            if (sift3d_alloc_device((void **)&arena, sizeof(float) * (size_t)need) == hipSuccess) arena_cap = need;
         }
         arena_used = need = 0;
     }
@@ -883,7 +884,7 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
                         if (h->merged) (void)hipHostFree(h->merged);
                         h->merged = nullptr;
                         h->merged_cap = slab_total + room;
-                        if (hipHostMalloc((void **)&h->merged, sizeof(sift3d_feature) * (size_t)(h->merged_cap ? h->merged_cap : 1),
+                        if (sift3d_alloc_host((void **)&h->merged, sizeof(sift3d_feature) * (size_t)(h->merged_cap ? h->merged_cap : 1),
                                           hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
                             h->merged = nullptr;
                             h->merged_cap = 0;
@@ -934,7 +935,7 @@ static int zslab_extract_impl(sift3d_zslab *h, const float *vol, float initial_i
         if (total > h->merged_cap) { /* the coarse octaves' records do not fit behind the slabs': a larger list, the slabs' part carried over (rare) */
             sift3d_feature *big = nullptr;
             const int64_t cap = total + total / 8 + 4096;
-            if (hipHostMalloc((void **)&big, sizeof(sift3d_feature) * (size_t)cap, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
+            if (sift3d_alloc_host((void **)&big, sizeof(sift3d_feature) * (size_t)cap, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
                 rc = SIFT3D_ERR_MEMORY;
                 snprintf(errbuf, sizeof errbuf, "out of pinned host memory for %lld merged records", (long long)total);
                 return;
@@ -1024,7 +1025,7 @@ extern "C" int sift3d_zslab_set_volume(sift3d_zslab *h, const float *vol, char *
         int64_t i0 = 0, i1 = plan.nz;
         if (S > 1) plan.input_range(r, i0, i1);
         hipError_t e = hipSetDevice(q.dev);
-        if (e == hipSuccess && !q.vol_dev) e = hipMalloc((void **)&q.vol_dev, sizeof(float) * (size_t)((i1 - i0) * XY));
+        if (e == hipSuccess && !q.vol_dev) e = sift3d_alloc_device((void **)&q.vol_dev, sizeof(float) * (size_t)((i1 - i0) * XY));
         if (e == hipSuccess) e = hipMemcpyAsync(q.vol_dev, vol + i0 * XY, sizeof(float) * (size_t)((i1 - i0) * XY), hipMemcpyHostToDevice, q.c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(q.c->stream); /* the caller's buffer is free again when this returns */
         if (e != hipSuccess) {

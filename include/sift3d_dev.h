@@ -1,8 +1,9 @@
 /*
  * sift3d_dev.h -- what is NOT part of the drop-in boundary of include/sift3d.h.
  *
- * (1) One hardware self-test that the product library exports, because the GPU test suite runs it on the library that
- *     ships: it checks the one hardware property an implementation choice rests on.
+ * (1) Two self-tests that the product library exports, because the GPU test suite runs them on the library that ships:
+ *     one checks the one hardware property an implementation choice rests on, the other makes the library's allocator
+ *     hand out filled blocks, so that the suite can hold every entry point to "no result depends on what an allocation held".
  * (2) Development hooks that exist only in `make DEV=1` builds (3d_sift_cuda_amd/csrc/_build_dev: the timing-ablation
  *     branches of the per-keypoint kernels, matcher plans, the overlap probe).  The product library does not export them
  *     (tests/test_abi_and_host.py checks), and nothing under 3d_sift_cuda_amd/ or tests/ calls them: tools/ only.
@@ -21,6 +22,16 @@ extern "C" {
  * ALU, lds[i] = the same sum through ds_add_f32 (host arrays).  tests/ compare the two bit for bit on random,
  * denormal, signed-zero, infinite and NaN operands. */
 int sift3d_selftest_lds_add(sift3d_ctx *ctx, const float *a, const float *b, int64_t n, float *valu, float *lds);
+
+/* Test switch of the library's allocator (no reference counterpart): with byte in 0..255 every device and pinned host
+ * block the library allocates from now on, in any thread, and every piece a slab rank cuts from its reused arena, holds
+ * that byte over its whole length before the library uses it; -1 turns the fill off (the default, which costs one atomic
+ * load per allocation).  stats (may be NULL) gets the blocks and the bytes filled since the previous call.  The call
+ * proves itself: it takes 4 KiB from the same allocator on the current device, reads it back and returns
+ * SIFT3D_ERR_DEVICE, with the fill off again, unless every byte is the pattern.  tests/ run every entry point against its
+ * oracle under 0xFF and 0x55: a result must not depend on what an allocation held.  Not for timed runs: each fill waits
+ * for the device. */
+int sift3d_selftest_alloc_fill(int byte, uint64_t stats[2]);
 
 #ifdef SIFT3D_DEV
 /* Development builds only (make DEV=1; tools/kp_ablate.py, tools/desc_ablate.py): the per-keypoint kernels return after
