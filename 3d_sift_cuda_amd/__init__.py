@@ -39,7 +39,7 @@ FEATOVERLAP = os.path.join(CSRC, "_build", "featOverlap")
 FEATCLEAN = os.path.join(CSRC, "_build", "featClean")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
-ABI_VERSION = 6   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
+ABI_VERSION = 7   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
 INFO_MIN0MAX1, INFO_REORIENT = 0x10, 0x20
 STAGES = ("blur_x", "blur_y", "blur_z_dog", "subsample", "extrema", "keypoint", "descriptor", "blur_fused", "octave_tiny")
 
@@ -686,7 +686,7 @@ def refine_similarity(fixed, moving, init, device=0, **params):
 
 
 # ---- resampling (featResample), DESIGN.md section 7c ----------------------------------------------------------------------
-INTERP = {"linear": 0, "nearest": 1}   # include/sift3d.h: sift3d_interp
+INTERP = {"linear": 0, "nearest": 1, "label": 2}   # include/sift3d.h: sift3d_interp ("label": label-aware linear)
 
 
 # ---- nonrigid alignment (featMatchMultiple -a -e -u, featResample -u), DESIGN.md section 7e ----------------------------------
@@ -1268,7 +1268,8 @@ FUSE_MAX_ATLASES, FUSE_U_ONE, FUSE_FALLBACK, FUSE_NONE = 32, 32768, 0x40000000, 
 
 class FuseParams(C.Structure):
     """sift3d_fuse_params"""
-    _fields_ = [("block", C.c_int32), ("metric", C.c_int32), ("power", C.c_int32), ("fill", C.c_float), ("max_voxels", C.c_int64)]
+    _fields_ = [("block", C.c_int32), ("metric", C.c_int32), ("power", C.c_int32), ("fill", C.c_float), ("max_voxels", C.c_int64),
+                ("label_interp", C.c_int32)]
 
 
 class FuseAtlas(C.Structure):
@@ -1290,13 +1291,14 @@ class FuseReport(C.Structure):
 
 
 def fuse_params(**kw):
-    """sift3d_fuse_defaults, then the given fields (block, metric ("ssd", "ncc" or a number), power, fill, max_voxels)."""
+    """sift3d_fuse_defaults, then the given fields (block, metric ("ssd", "ncc" or a number), power, fill, max_voxels, label_interp
+    ("nearest", "label" or a number: how the atlases' labels are warped))."""
     p = FuseParams()
     host_lib().sift3d_fuse_defaults(C.byref(p))
     for k, v in kw.items():
         if k not in dict(FuseParams._fields_):
             raise ValueError("no fusion parameter %s" % k)
-        setattr(p, k, BLOCKMATCH_METRICS.get(v, v) if k == "metric" else v)
+        setattr(p, k, BLOCKMATCH_METRICS.get(v, v) if k == "metric" else INTERP.get(v, v) if k == "label_interp" else v)
     return p
 
 
@@ -1642,7 +1644,7 @@ def _map12(m):
 
 def resample_affine(vol, out_shape, map, interp="linear", fill=0.0, device=0, return_ms=False):
     """sift3d_resample_affine: vol (nz, ny, nx) float32 resampled onto an output of out_shape = (oz, oy, ox) through the
-    3 x 4 map that takes an output voxel index (i, j, k) to a source voxel position.  interp "linear" or "nearest"; output
+    3 x 4 map that takes an output voxel index (i, j, k) to a source voxel position.  interp "linear", "nearest" or "label" (label-aware linear, for label maps); output
     voxels that map outside the source get fill.  return_ms=True returns (out, kernel_ms)."""
     v = _f32(vol)
     nz, ny, nx = v.shape

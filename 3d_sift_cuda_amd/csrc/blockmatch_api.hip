@@ -196,8 +196,8 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
             sift3d_blockmatch_round &r = rp.round[round];
             DEVCHK(dc, send_nodes(dc, cur, nodes, d_nodes));
             DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
-            DEVCHK(dc, sift3d_launch_field_warp(dc.s, d_m, mx, my, mz, d_w, fx, fy, fz, map, cterm, kterm, cur.origin, cur.spacing, cur.n, d_nodes, 0,
-                                                std::nanf("")));
+            DEVCHK(dc, sift3d_launch_field_warp(dc.s, d_m, mx, my, mz, d_w, fx, fy, fz, map, cterm, kterm, cur.origin, cur.spacing, cur.n, d_nodes,
+                                                SIFT3D_INTERP_LINEAR, std::nanf("")));
             DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
             DEVCHK(dc, dc.sync());
             DEVCHK(dc, dc.elapsed_ms(&r.warp_ms));

@@ -9,7 +9,8 @@
  * The target is the fixed image and every atlas a moving one, exactly featResample's roles: <atlas.trans.txt> is what
  * featMatchMultiple -a wrote for the atlas image against the target, <atlas.field.nii> the displacement field of -a -e -u or of
  * featResample -i ("-": none).  Four arguments per atlas, 1 .. 32 atlases.  Atlas labels are integers 0 .. 65535; a non-finite
- * voxel is unlabelled and does not vote.
+ * voxel is unlabelled and does not vote.  -l: the atlases' labels are warped by label-aware linear interpolation (section 7n), not
+ * by nearest neighbour; <output labels>.fuse.txt then says so in its second line.
  * Writes <output labels> (float32, the target's geometry, -f's value where no atlas votes), <output labels>.conf.nii (the winning
  * label's share of the vote, 0 .. 1) and <output labels>.fuse.txt (the parameters, the report, the voxels per label and, with -t,
  * the Dice overlap per label with the truth and their mean over the labels either volume has; with -s the radius and per atlas the
@@ -45,6 +46,7 @@ static void print_options(void)
     printf("  -p<0|1|2>  : power of the similarity in the vote; 0 is majority voting (default 2).\n");
     printf("  -s<radius> : every atlas votes with the label and the weight of its best-matching patch within <radius> voxels, 1 .. %d;\n", SIFT3D_FUSE_MAX_SEARCH);
     printf("               half-width + radius at most %d, and not with -p0 (default: no search).\n", SIFT3D_BLOCKMATCH_MAX_B);
+    printf("  -l         : warp the atlases' labels by label-aware linear interpolation (default: nearest neighbour).\n");
     printf("  -f<value>  : value of output voxels where no atlas votes (default 0).\n");
     printf("  -t <truth> : label image on the target's grid: also write the Dice overlap per label to <output labels>.fuse.txt.\n");
     printf("  -m         : with -t: also write the surface distances per label to the truth (Hausdorff, 95th percentile, average\n");
@@ -98,6 +100,7 @@ static int write_report(const char *out_path, int K, const sift3d_fuse_params *p
     if (!o) return -1;
     fprintf(o, "# atlases %d block %d metric %s power %d fill %g\n", K, p->block, p->metric == SIFT3D_BLOCKMATCH_NCC ? "ncc" : "ssd", p->power,
             (double)p->fill);
+    if (p->label_interp == SIFT3D_INTERP_LABEL) fprintf(o, "# label_interp label\n");
     fprintf(o, "# target quantised over %g .. %g\n", (double)rep->lo, (double)rep->hi);
     fprintf(o, "# voxels %lld none %lld fallback %lld\n", (long long)n, (long long)rep->none, (long long)rep->fallback);
     fprintf(o, "# atlas voters support mean_u empty_range\n");
@@ -166,6 +169,10 @@ int main(int argc, char **argv)
             search = (int32_t)v;
             break;
         }
+        case 'l':
+            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            p.label_interp = SIFT3D_INTERP_LABEL;
+            break;
         case 'f':
             p.fill = strtof(argv[arg] + 2, &end);
             if (end == argv[arg] + 2 || *end != 0) return bad_option("bad fill value", argv[arg]);

@@ -43,6 +43,7 @@ static void print_options(void)
     printf("  -w         : the features were extracted with -w (world coordinates, NIFTI qto_xyz matrix).\n");
     printf("  -ws        : the features were extracted with -ws (world coordinates, NIFTI sto_xyz matrix).\n");
     printf("  -n         : nearest-neighbour interpolation (label maps; default is trilinear).\n");
+    printf("  -l         : label-aware linear interpolation (label maps: the label with the largest trilinear weight; not with -n).\n");
     printf("  -f<value>  : value of output voxels that map outside the moving image (default 0).\n");
     printf("  -d[0-9]    : set device id to be used.\n");
     printf("  -u <field> : also through the displacement field featMatchMultiple -a -e -u wrote (<moving>.field.nii).\n");
@@ -217,7 +218,7 @@ static int reverse(int device, const char *fixed_path, const char *moving_path, 
 
 int main(int argc, char **argv)
 {
-    int device = 0, world_mode = 0, interp = SIFT3D_INTERP_LINEAR;
+    int device = 0, world_mode = 0, nearest = 0, label = 0;
     float fill = 0.0f;
     const char *field_path = NULL;
     int intensity = 0, rounds = -1, metric = SIFT3D_BLOCKMATCH_SSD, backward = 0, jacobian = 0;
@@ -230,7 +231,15 @@ int main(int argc, char **argv)
             if (argv[arg][2] == 's' || argv[arg][2] == 'S') world_mode = 2;
             break;
         case 'n':
-            interp = SIFT3D_INTERP_NEAREST;
+            nearest = 1;
+            break;
+        case 'l':
+            if (argv[arg][2] != 0) {
+                printf("Error: unknown command line argument: %s\n", argv[arg]);
+                print_options();
+                return -1;
+            }
+            label = 1;
             break;
         case 'f': {
             char *end = NULL;
@@ -300,6 +309,12 @@ int main(int argc, char **argv)
         print_options();
         return -1;
     }
+    if (nearest && label) {
+        printf("Error: -n and -l are two interpolations: give one\n");
+        print_options();
+        return -1;
+    }
+    const int interp = label ? SIFT3D_INTERP_LABEL : (nearest ? SIFT3D_INTERP_NEAREST : SIFT3D_INTERP_LINEAR);
     if (metric != SIFT3D_BLOCKMATCH_SSD && !intensity) {
         printf("Error: -c needs -i\n");
         print_options();

@@ -230,7 +230,8 @@ static const char *check_warp(const float *src, int64_t nx, int64_t ny, int64_t 
                               const float *map, int interp, const sift3d_field *f)
 {
     if (!src || !dst || !map || !f) return "null pointer";
-    if (interp != SIFT3D_INTERP_LINEAR && interp != SIFT3D_INTERP_NEAREST) return "interp must be SIFT3D_INTERP_LINEAR or SIFT3D_INTERP_NEAREST";
+    if (interp != SIFT3D_INTERP_LINEAR && interp != SIFT3D_INTERP_NEAREST && interp != SIFT3D_INTERP_LABEL)
+        return "interp must be SIFT3D_INTERP_LINEAR, SIFT3D_INTERP_NEAREST or SIFT3D_INTERP_LABEL";
     const char *why = check_source_extents(nx, ny, nz);
     if (!why) why = check_output_extents(ox, oy, oz);
     return why ? why : check_field(*f);
@@ -263,7 +264,7 @@ extern "C" int sift3d_resample_field(int device, const float *src, int64_t nx, i
     DEVCHK(dc, send_nodes(dc, *field, nodes, d_nodes));
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
     DEVCHK(dc, sift3d_launch_field_warp(dc.s, d_src, nx, ny, nz, d_dst, ox, oy, oz, map, c, k, field->origin, field->spacing, field->n, d_nodes,
-                                        interp == SIFT3D_INTERP_NEAREST, fill));
+                                        interp, fill));
     DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
     DEVCHK(dc, dc.download(dst, d_dst, n_out));
     DEVCHK(dc, dc.sync());

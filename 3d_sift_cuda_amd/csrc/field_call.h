@@ -16,7 +16,7 @@
 
 hipError_t sift3d_launch_field_warp(hipStream_t s, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
                                     int64_t oz, const float *map, const float *c, const float *k, const float o[3], float h, const int64_t n[3],
-                                    const float4 *nodes, int nearest, float fill);
+                                    const float4 *nodes, int mode, float fill);
 
 inline int64_t nodes_of(const sift3d_field &f) { return f.n[0] * f.n[1] * f.n[2]; }
 

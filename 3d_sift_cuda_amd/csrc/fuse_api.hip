@@ -210,6 +210,8 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
     if (K < 1 || K > SIFT3D_FUSE_MAX_ATLASES) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%d atlases: 1 .. %d are taken", (int)K, SIFT3D_FUSE_MAX_ATLASES);
     if (!target || !atlases || !words) return call_fail(err, err_len, SIFT3D_ERR_ARG, "null pointer");
     if (p.power < 0 || p.power > 2) return call_fail(err, err_len, SIFT3D_ERR_ARG, "the power must be 0, 1 or 2");
+    if (p.label_interp != SIFT3D_INTERP_NEAREST && p.label_interp != SIFT3D_INTERP_LABEL)
+        return call_fail(err, err_len, SIFT3D_ERR_ARG, "label_interp must be SIFT3D_INTERP_NEAREST (1) or SIFT3D_INTERP_LABEL (2): labels are never blended");
     const char *why = check_weights(nx, ny, nz, p.block, p.metric);
     if (!why) why = check_search(p.block, search);
     if (!why && search > 0 && p.power == 0) why = "a search needs weights to search by: the power must be 1 or 2";
@@ -274,13 +276,13 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
             return call_fail(err, err_len, SIFT3D_ERR_ARG, "atlas %d: a matrix's last row is not 0 0 0 1, or a matrix is singular", k);
         if (a.field) DEVCHK(dc, send_nodes(dc, *a.field, nodes, d_nodes));
         /* volume `src` of the atlas through its map and field onto the target grid, into d_w */
-        auto warp = [&](const float *src, int nearest) -> hipError_t {
+        auto warp = [&](const float *src, int interp) -> hipError_t {
             hipError_t e = dc.to_device(d_m, src, nm);
             if (e != hipSuccess) return e;
             if (a.field)
                 return sift3d_launch_field_warp(dc.s, d_m, a.nx, a.ny, a.nz, d_w, nx, ny, nz, map, cterm, kterm, a.field->origin, a.field->spacing,
-                                                a.field->n, d_nodes, nearest, nanf_);
-            return sift3d_launch_resample(dc.s, d_m, a.nx, a.ny, a.nz, d_w, nx, ny, nz, map, nearest, nanf_);
+                                                a.field->n, d_nodes, interp, nanf_);
+            return sift3d_launch_resample(dc.s, d_m, a.nx, a.ny, a.nz, d_w, nx, ny, nz, map, interp, nanf_);
         };
         float wlo = rp.lo, whi = rp.hi;
         if (p.power > 0) r.empty_range = !w_range_of(p.metric, nullptr, a.image, nm, rp.lo, rp.hi, &wlo, &whi);
@@ -288,7 +290,7 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
         double ms = 0.0;
         if (weigh) {
             DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
-            DEVCHK(dc, warp(a.image, 0));
+            DEVCHK(dc, warp(a.image, SIFT3D_INTERP_LINEAR));
             DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
             DEVCHK(dc, dc.sync());
             DEVCHK(dc, dc.elapsed_ms(&ms));
@@ -301,7 +303,7 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
             DEVCHK(dc, dc.elapsed_ms(&r.weight_ms));
         }
         DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
-        DEVCHK(dc, warp(a.labels, 1));
+        DEVCHK(dc, warp(a.labels, p.label_interp));
         DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
         if (search == 0 || !weigh) DEVCHK(dc, sift3d_launch_fuse_label(dc.s, d_w, n, !weigh, d_lab + nv * k, d_u + nv * k));
         DEVCHK(dc, dc.sync());

@@ -17,6 +17,7 @@ void sift3d_fuse_defaults(sift3d_fuse_params *p)
     p->power = 2;
     p->fill = 0.0f;
     p->max_voxels = (int64_t)1 << 28;
+    p->label_interp = SIFT3D_INTERP_NEAREST;
 }
 
 uint32_t sift3d_fuse_similarity(int32_t metric, int64_t n, int64_t sf, int64_t sff, int64_t sw, int64_t sww, int64_t sfw)

@@ -92,7 +92,7 @@ hipError_t sift3d_launch_field_fit(hipStream_t s, const float4 *ys, const float4
     return hipGetLastError();
 }
 
-template <int NEAREST>
+template <int MODE>
 __global__ __launch_bounds__(256) void field_warp_kernel(const float *__restrict__ src, long long nx, long long ny, long long nz, float *__restrict__ dst,
                                                          long long ox, long long oy, long long oz, warp_map m, const float4 *__restrict__ nodes, float fill,
                                                          long long nbx, long long nby, long long nbricks, int vec)
@@ -109,22 +109,22 @@ __global__ __launch_bounds__(256) void field_warp_kernel(const float *__restrict
         for (int v = 0; v < BRICK_VX; v++) {
             float q[3];
             warp_position<1>(m, nodes, (float)(i0 + v), (float)j, (float)k, q);
-            r[v] = sample_volume<NEAREST>(src, nx, ny, nz, hx, hy, hz, q[0], q[1], q[2], fill);
+            r[v] = sample_volume<MODE>(src, nx, ny, nz, hx, hy, hz, q[0], q[1], q[2], fill);
         }
         store_row4(dst + (k * oy + j) * ox + i0, ox, i0, r, vec);
     }
 }
 
 /* map, c: 12 floats (3 x 4 row-major); k: 9; the node grid n (each 2 .. 2^24), origin o, spacing h; nodes: float4 (v0, v1,
- * v2, 0), x fastest.  The caller has checked the shapes. */
+ * v2, 0), x fastest; mode: a sift3d_interp.  The caller has checked the shapes and the mode. */
 hipError_t sift3d_launch_field_warp(hipStream_t s, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
                                     int64_t oz, const float *map, const float *c, const float *k, const float o[3], float h, const int64_t n[3],
-                                    const float4 *nodes, int nearest, float fill)
+                                    const float4 *nodes, int mode, float fill)
 {
     warp_map m;
     fill_warp_map(m, map, c, k, true, o, h, n);
     const brick_launch b = brick_launch_of(dst, ox, oy, oz);
-    auto kernel = nearest ? field_warp_kernel<1> : field_warp_kernel<0>;
+    auto kernel = mode == WARP_LABEL ? field_warp_kernel<WARP_LABEL> : mode == WARP_NEAREST ? field_warp_kernel<WARP_NEAREST> : field_warp_kernel<WARP_LINEAR>;
     hipLaunchKernelGGL(kernel, dim3(b.grid), dim3(256), 0, s, src, (long long)nx, (long long)ny, (long long)nz, dst, (long long)ox, (long long)oy,
                        (long long)oz, m, nodes, fill, b.nbx, b.nby, b.nbricks, b.vec);
     return hipGetLastError();

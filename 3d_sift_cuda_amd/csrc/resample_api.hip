@@ -11,7 +11,8 @@ static const char *check_args(const float *src, int64_t nx, int64_t ny, int64_t 
                               const float *map, int interp)
 {
     if (!src || !dst || !map) return "null pointer";
-    if (interp != SIFT3D_INTERP_LINEAR && interp != SIFT3D_INTERP_NEAREST) return "interp must be SIFT3D_INTERP_LINEAR or SIFT3D_INTERP_NEAREST";
+    if (interp != SIFT3D_INTERP_LINEAR && interp != SIFT3D_INTERP_NEAREST && interp != SIFT3D_INTERP_LABEL)
+        return "interp must be SIFT3D_INTERP_LINEAR, SIFT3D_INTERP_NEAREST or SIFT3D_INTERP_LABEL";
     const char *why = check_source_extents(nx, ny, nz);
     return why ? why : check_output_extents(ox, oy, oz);
 }
@@ -34,7 +35,7 @@ extern "C" int sift3d_resample_affine(int device, const float *src, int64_t nx, 
     }
     DEVCHK(dc, dc.to_device(d_src, src, n_in));
     DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
-    DEVCHK(dc, sift3d_launch_resample(dc.s, d_src, nx, ny, nz, d_dst, ox, oy, oz, map, interp == SIFT3D_INTERP_NEAREST, fill));
+    DEVCHK(dc, sift3d_launch_resample(dc.s, d_src, nx, ny, nz, d_dst, ox, oy, oz, map, interp, fill));
     DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
     DEVCHK(dc, dc.download(dst, d_dst, n_out));
     DEVCHK(dc, dc.sync());
@@ -51,6 +52,6 @@ extern "C" int sift3d_resample_affine_dev(sift3d_ctx *c, const float *d_src, int
     HIPCHK(c, hipSetDevice(c->device));
     int rc = fence_in(c);
     if (rc) return rc;
-    HIPCHK(c, sift3d_launch_resample(c->stream, d_src, nx, ny, nz, d_dst, ox, oy, oz, map, interp == SIFT3D_INTERP_NEAREST, fill));
+    HIPCHK(c, sift3d_launch_resample(c->stream, d_src, nx, ny, nz, d_dst, ox, oy, oz, map, interp, fill));
     return fence_out(c);
 }

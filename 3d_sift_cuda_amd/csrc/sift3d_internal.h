@@ -230,7 +230,7 @@ hipError_t sift3d_launch_ratio(hipStream_t s, const signed char *db, const int *
 hipError_t sift3d_launch_hough(hipStream_t s, const float *p0, const float *p1, const float *s0, const float *s1, const float *o0, const float *o1,
                                int M, float lo, float hi, int one, int *counts, int *flags, float *hyp);
 hipError_t sift3d_launch_resample(hipStream_t s, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
-                                  int64_t oz, const float *map, int nearest, float fill);
+                                  int64_t oz, const float *map, int mode, float fill);
 hipError_t sift3d_launch_guided(hipStream_t s, const void *f_rows, const int *f_norm, const float *f_pos, const unsigned *f_info, const int *f_idx,
                                 int n_f, const int *cell_start, const long long *keys, const double grid_o[3], double edge, const long long grid_n[3],
                                 int dense, const void *m_rows, const float *m_pos, const unsigned *m_info, const int *order, int n_m,

@@ -13,6 +13,12 @@
  * i0 = (int64)f, i1 = min(i0 + 1, n - 1), interpolated along x, then y, then z, each step (1 - w) * a + w * b; all eight
  * corners are read and weighed, so a NaN or infinite corner of weight 0 still reaches the result (IEEE, no -fno-honor-nans).
  * Nearest: i = min((int64)floorf(q + 0.5f), n - 1).  No texture sampler: its filter weights are fixed-point.
+ * Label (section 7n): linear's eight corners c = a + 2b + 4d with the weights W_c = (X_a * Y_b) * Z_d (X_0 = ux, X_1 = wx, ...).
+ * Corners of equal value (==) are one class, the non-finite ones together the unlabelled class; a class' score is the sum
+ * ((t_0 + t_1) + ... + t_7), t_c = W_c for its corners and 0.0f for the others.  The largest score wins, at equal scores a
+ * labelled class before the unlabelled one and the smaller value before the larger; the result is the value of the winner's
+ * lowest-numbered corner with its bits, a quiet NaN for the unlabelled class.  In registers and without a branch: the masked sum
+ * of every corner, then one pass over the corners under that rule.  tests/label_interp_oracle.c restates it.
  *
  * The field's term (section 7e).  The key position kappa = C p (the map's order), g = (kappa - o) / h, and where
  * 0 <= g <= n - 1 on every axis the trilinear interpolation v of the float4 nodes (one dwordx4 load per corner; the
@@ -144,13 +150,47 @@ __device__ __forceinline__ void warp_position(const MAP &m, const float4 *__rest
 
 /* ---- the image sampler ---- */
 
-/* src (nx x ny x nz, x fastest) at the position (qx, qy, qz); hx = (float)(nx - 1) and so on; `fill` outside */
-template <int NEAREST>
+#define WARP_LINEAR 0  /* include/sift3d.h: sift3d_interp */
+#define WARP_NEAREST 1
+#define WARP_LABEL 2
+
+/* the label-aware vote over eight corner values L and their weights W (the header's "Label") */
+__device__ __forceinline__ float label_vote(const float (&L)[8], const float (&W)[8])
+{
+    /* The class key: the value itself, +inf for every non-finite one.  Then two corners are of one class exactly when their keys
+     * compare equal (-0 == 0, inf == inf, no NaN left), a labelled class is one whose key is below +inf, and "labelled before
+     * unlabelled, then the smaller value" is one comparison of keys.  A finite key has its corner's bits. */
+    const float inf = __builtin_inff();
+    float K[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) K[c] = fabsf(L[c]) < inf ? L[c] : inf;
+    float best = K[0], best_s = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        float s = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            /* each pair is compared once: the indices are compile-time constants after unrolling */
+            const float t = e == c ? W[e] : (K[c < e ? c : e] == K[c < e ? e : c] ? W[e] : 0.0f);
+            s = e == 0 ? t : s + t;
+        }
+        /* corner 0 opens; a later corner takes over only when its class is strictly better, so a class keeps its lowest corner.
+         * & and |, not && and ||: selects, no branches */
+        const bool better = (c == 0) | (s > best_s) | ((s == best_s) & (K[c] < best));
+        best = better ? K[c] : best;
+        best_s = better ? s : best_s;
+    }
+    return best < inf ? best : __builtin_nanf("");
+}
+
+/* src (nx x ny x nz, x fastest) at the position (qx, qy, qz); hx = (float)(nx - 1) and so on; `fill` outside.  MODE: WARP_* */
+template <int MODE>
 __device__ __forceinline__ float sample_volume(const float *__restrict__ src, long long nx, long long ny, long long nz, float hx, float hy, float hz,
                                                float qx, float qy, float qz, float fill)
 {
+    static_assert(MODE == WARP_LINEAR || MODE == WARP_NEAREST || MODE == WARP_LABEL, "sample_volume: unknown mode");
     if (!(qx >= 0.0f && qx <= hx && qy >= 0.0f && qy <= hy && qz >= 0.0f && qz <= hz)) return fill;
-    if (NEAREST) {
+    if (MODE == WARP_NEAREST) {
         /* q <= n - 1 <= 2^24 - 1 here: the int conversions give the values of (int64) ones, in one instruction */
         long long ix = (int)floorf(qx + 0.5f), iy = (int)floorf(qy + 0.5f), iz = (int)floorf(qz + 0.5f);
         ix = ix < nx - 1 ? ix : nx - 1;
@@ -165,12 +205,20 @@ __device__ __forceinline__ float sample_volume(const float *__restrict__ src, lo
     const float *r00 = src + (z0 * ny + y0) * nx, *r10 = src + (z0 * ny + y1) * nx, *r01 = src + (z1 * ny + y0) * nx,
                 *r11 = src + (z1 * ny + y1) * nx;
     const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
-    const float c00 = ux * r00[x0] + wx * r00[x1]; /* (y0, z0) */
-    const float c10 = ux * r10[x0] + wx * r10[x1]; /* (y1, z0) */
-    const float c01 = ux * r01[x0] + wx * r01[x1]; /* (y0, z1) */
-    const float c11 = ux * r11[x0] + wx * r11[x1]; /* (y1, z1) */
-    const float c0 = uy * c00 + wy * c10, c1 = uy * c01 + wy * c11;
-    return uz * c0 + wz * c1;
+    if constexpr (MODE == WARP_LABEL) {
+        /* linear's eight gathers; corner c = a + 2b + 4d */
+        const float L[8] = {r00[x0], r00[x1], r10[x0], r10[x1], r01[x0], r01[x1], r11[x0], r11[x1]};
+        const float xy00 = ux * uy, xy10 = wx * uy, xy01 = ux * wy, xy11 = wx * wy;
+        const float W[8] = {xy00 * uz, xy10 * uz, xy01 * uz, xy11 * uz, xy00 * wz, xy10 * wz, xy01 * wz, xy11 * wz};
+        return label_vote(L, W);
+    } else {
+        const float c00 = ux * r00[x0] + wx * r00[x1]; /* (y0, z0) */
+        const float c10 = ux * r10[x0] + wx * r10[x1]; /* (y1, z0) */
+        const float c01 = ux * r01[x0] + wx * r01[x1]; /* (y0, z1) */
+        const float c11 = ux * r11[x0] + wx * r11[x1]; /* (y1, z1) */
+        const float c0 = uy * c00 + wy * c10, c1 = uy * c01 + wy * c11;
+        return uz * c0 + wz * c1;
+    }
 }
 
 /* ---- the brick of output voxels ---- */

@@ -49,9 +49,9 @@ extern "C" {
 /* Layout version of the structures this header passes by pointer (sift3d_zslab_stats, sift3d_timings, sift3d_feature, ...).
  * The library writes WHOLE structures through the caller's pointers, so a binding compiled against another layout would be
  * overrun: a binding checks sift3d_abi_version() == SIFT3D_ABI_VERSION once, when it loads the library (the in-tree ctypes
- * mirror and featExtract do).  6: the tuning enum gained SIFT3D_TUNE_FUSED_STAGGER, sift3d_set_libm_variant (round 6); 5: sift3d_zslab_stats gained comm_sets, resident_volume, merge_ms, halo_bytes_subsample, enqueue_ms (round 5); 4: transport,
+ * mirror and featExtract do).  7: sift3d_fuse_params gained label_interp, sift3d_interp gained SIFT3D_INTERP_LABEL; 6: the tuning enum gained SIFT3D_TUNE_FUSED_STAGGER, sift3d_set_libm_variant (round 6); 5: sift3d_zslab_stats gained comm_sets, resident_volume, merge_ms, halo_bytes_subsample, enqueue_ms (round 5); 4: transport,
  * transport_fell_back, rccl_version (round 4). */
-#define SIFT3D_ABI_VERSION 6
+#define SIFT3D_ABI_VERSION 7
 int sift3d_abi_version(void);
 
 #define SIFT3D_DESC_LEN 64
@@ -628,8 +628,19 @@ int sift3d_refine_similarity(int device, const sift3d_feature *fixed, int64_t n_
  * A sample is taken where 0 <= q <= n - 1 on every axis (a NaN position fails); every other output voxel gets fill.
  * Linear: trilinear over the eight corners, x then y then z, each step (1 - w) * a + w * b -- a NaN or infinite corner of
  * weight 0 still reaches the result.  Nearest: the voxel min(floorf(q + 0.5f), n - 1).  Source extents 1 .. 2^24, output
- * extents 1 .. 2^31 - 1 with at most 2^40 voxels; 64-bit indices throughout. */
-typedef enum { SIFT3D_INTERP_LINEAR = 0, SIFT3D_INTERP_NEAREST = 1 } sift3d_interp;
+ * extents 1 .. 2^31 - 1 with at most 2^40 voxels; 64-bit indices throughout.
+ * Label (label-aware linear, for label maps; DESIGN.md section 7n, restated by tests/label_interp_oracle.c): linear's f = floorf(q),
+ * w = q - f, i0, i1 = min(i0 + 1, n - 1) and u = 1.0f - w.  Corner c = a + 2b + 4d (a, b, d in {0, 1} along x, y, z) has the value
+ * L_c = src[(z_d ny + y_b) nx + x_a] and the weight W_c = (X_a * Y_b) * Z_d, X_0 = ux, X_1 = wx and likewise Y and Z (float
+ * multiplies in that association).  Two corners are of one class when their values compare equal with == (-0 and 0 are one
+ * class); all non-finite corners (NaN, +-inf) together are the unlabelled class.  A class' score is ((..((t_0 + t_1) + t_2) ..) +
+ * t_7) in float, t_c = W_c for its corners and 0.0f for the others.  The largest score wins; at equal scores a labelled class
+ * beats the unlabelled one, and among labelled classes the smaller value wins.  The result is the value of the winner's
+ * lowest-numbered corner with its bits (-0 survives), a quiet NaN where the unlabelled class wins.  It follows that a corner of
+ * weight 0 decides nothing (unlike linear, a NaN corner of weight 0 does not reach the result), that the identity map returns the
+ * source's bits on every finite voxel, and that the result is always a value the source holds, or NaN, or fill.  The mode is
+ * defined on any float volume: the resampler makes no integer check.  Extents as above. */
+typedef enum { SIFT3D_INTERP_LINEAR = 0, SIFT3D_INTERP_NEAREST = 1, SIFT3D_INTERP_LABEL = 2 } sift3d_interp;
 /* Host arrays in and out, on `device`.  *kernel_ms (may be NULL): device time of the resampling kernel. */
 int sift3d_resample_affine(int device, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
                            int64_t oz, const float map[12], int interp, float fill, double *kernel_ms, char *err, int64_t err_len);
@@ -1046,7 +1057,8 @@ int64_t sift3d_compose_residual(const int64_t n[3], const uint32_t *status, cons
  * is a moving one with an intensity volume, a label volume of the same extents, its moving_to_fixed 4 x 4 and an optional field:
  * featResample's roles.  Atlas label voxels are non-finite (unlabelled) or integers 0 .. 65535; anything else is SIFT3D_ERR_ARG.
  * Warp: W_k = the atlas intensities through sift3d_resample_field's arithmetic (sift3d_resample_affine's without a field), linear,
- * fill NaN; M_k = the atlas labels through the same map, nearest, fill NaN.
+ * fill NaN; M_k = the atlas labels through the same map, nearest (label_interp SIFT3D_INTERP_LABEL: label-aware linear, section 7n;
+ * its result is a label the atlas holds or NaN, so everything after the warp is the same), fill NaN.
  * Quantisation: section 7f's q (-1: not finite).  T with T's range (sift3d_blockmatch_range; an empty range refuses the call);
  * W_k with T's range under SIFT3D_BLOCKMATCH_SSD and with the range of atlas k's own intensity volume under SIFT3D_BLOCKMATCH_NCC
  * (an empty one gives that atlas u = 0 everywhere).
@@ -1074,6 +1086,7 @@ typedef struct {
     int32_t power;      /* 2; 0, 1 or 2 */
     float fill;         /* 0: the value featFuse writes where no atlas votes (the words do not depend on it) */
     int64_t max_voxels; /* 2^28: above max_voxels target voxels times atlases the stage is refused */
+    int32_t label_interp; /* SIFT3D_INTERP_NEAREST: how M_k is warped; or SIFT3D_INTERP_LABEL.  Anything else is SIFT3D_ERR_ARG */
 } sift3d_fuse_params;
 void sift3d_fuse_defaults(sift3d_fuse_params *p);
 
@@ -1115,7 +1128,8 @@ int sift3d_fuse_vote(int device, int32_t K, const uint16_t *const *u, const floa
 /* The stage.  T is quantised once and stays on the device; the atlases stream through one at a time (warp, quantise, weigh, warp the
  * labels); the u and label planes stay for the vote, 4 bytes per voxel and atlas.  Power 0 launches no weight kernel and warps no
  * intensities.  p NULL: defaults.  words: 2 nx ny nz; rep may be NULL.  SIFT3D_ERR_ARG with text: what the above refuse, a matrix
- * that sift3d_resample_map refuses, a field that sift3d_resample_field refuses, nx ny nz K above max_voxels. */
+ * that sift3d_resample_map refuses, a field that sift3d_resample_field refuses, nx ny nz K above max_voxels, a label_interp that is
+ * neither SIFT3D_INTERP_NEAREST nor SIFT3D_INTERP_LABEL (on the host, before any launch). */
 int sift3d_fuse_labels(int device, const float *target, int64_t nx, int64_t ny, int64_t nz, const float target_vox2key[16], int32_t K,
                        const sift3d_fuse_atlas *atlases, const sift3d_fuse_params *p, uint32_t *words, sift3d_fuse_report *rep, char *err,
                        int64_t err_len);
