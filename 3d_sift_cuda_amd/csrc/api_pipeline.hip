@@ -391,6 +391,7 @@ static void kp_params_of(sift3d_ctx *c, int desc_mode, float eig_thres, float si
     p.sampler_tokens = c->sampler_tokens;
     p.sampler_cap = c->tune[SIFT3D_TUNE_SAMPLER_CAP];
     p.desc_seg = c->tune[SIFT3D_TUNE_DESC_SEGMENT] * 8;
+    p.desc_order = c->tune[SIFT3D_TUNE_DESC_ORDER];
     p.rec_shift = nullptr;
 }
 

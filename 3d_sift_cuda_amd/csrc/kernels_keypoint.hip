@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "desc_bins.h"
+#include "sample_order.h"
 #include "sift3d_internal.h"
 
 #define PD SIFT3D_PATCH_DIM
@@ -357,17 +358,20 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 #define NRAD_PAD 516
 #define NINT 729 /* interior voxels 1..9 in each axis */
 
-/* sampleImage3D, R/src_common/MultiScale.cpp:2614-2714 (bounds test done by the caller) */
+/* sampleImage3D, R/src_common/MultiScale.cpp:2614-2714 (bounds test done by the caller).  order: nullptr, or the list
+ * wave_sort_samples left -- the j-th sample taken is patch voxel order[j] */
 template <int NT>
 __device__ __forceinline__ void wave_sample_patch(float *patch, const float *__restrict__ img, int X, int XP, int Y, int Z, int Zl,
-                                                  int z_off, float fx, float fy, float fz, float scale, const float *ori9)
+                                                  int z_off, float fx, float fy, float fz, float scale, const float *ori9,
+                                                  const unsigned short *order = nullptr)
 {
     float inv[9];
     invert3(ori9, inv);
     const float rad = 2.0f * scale;
     const int sr = PD / 2;
     const float sc = rad / (float)(sr);
-    /* Which sample a lane takes changes no value, only which memory lines the 64 gathers of one instruction touch: the
+    /* Which sample a lane takes changes no value, only which memory lines the 64 gathers of one instruction touch.  Without
+     * a list (the keypoint kernel's identity frame, SIFT3D_TUNE_DESC_ORDER 0, the development stops) the
      * lanes walk the patch axis that runs closest to the volume's x first (then the one closest to y), so that
      * neighbouring lanes read neighbouring voxels of a row wherever the frame allows it (descriptor kernel at 512^3:
      * 4.12 -> 3.97 ms; the patch in Z-curve blocks of 4 x 4 x 4 instead of lines: no better). */
@@ -392,20 +396,11 @@ __device__ __forceinline__ void wave_sample_patch(float *patch, const float *__r
             pix[u] = 0;
             sidx[u] = 0;
             if (t < PV) {
-                const int s = (t % PD) * st_fast + ((t / PD) % PD) * st_mid + (t / (PD * PD)) * st_slow; /* the patch voxel this lane samples */
+                /* the patch voxel this lane samples */
+                const int s = order ? order[t] : (t % PD) * st_fast + ((t / PD) % PD) * st_mid + (t / (PD * PD)) * st_slow;
                 sidx[u] = s;
-                const int xx = s % PD - sr, yy = (s / PD) % PD - sr, zz = s / (PD * PD) - sr;
-                float in3[3] = {(float)xx, (float)yy, (float)zz};
                 float o[3];
-#pragma unroll
-                for (int i = 0; i < 3; i++) {
-                    float a = 0;
-#pragma unroll
-                    for (int j = 0; j < 3; j++) a += inv[i * 3 + j] * in3[j];
-                    o[i] = a;
-                }
-                o[0] *= sc; o[1] *= sc; o[2] *= sc;
-                o[0] += fx; o[1] += fy; o[2] += fz;
+                sample_order_position(inv, sc, fx, fy, fz, s, o);
                 if (o[0] < 0 || o[0] >= X) pix[u] = 0;
                 else pix[u] = trilinear(img, X, XP, Y, Z, Zl, z_off, o[0], o[1], o[2]);
             }
@@ -413,6 +408,52 @@ __device__ __forceinline__ void wave_sample_patch(float *patch, const float *__r
 #pragma unroll
         for (int u = 0; u < 3; u++)
             if (s0 + NT * u < PV) patch[sidx[u]] = pix[u];
+    }
+    __syncthreads();
+}
+
+/* The order in which wave_sample_patch is to take the samples of a re-oriented record: by the image row they read
+ * (sample_order.h), a counting sort by the NT lanes of the workgroup.  tmp: PV words that are dead until the sampling (the patch
+ * itself).  Which sample of a bin gets which rank is the arrival order of the LDS atomics and varies from run to run; the list
+ * is a permutation of the patch voxels either way, and a patch value is the same whichever lane computes it, so no result
+ * depends on it. */
+template <int NT>
+__device__ __forceinline__ void wave_sort_samples(sample_order_scratch &so, unsigned *tmp, int Y, int Z, float fx, float fy, float fz,
+                                                  float scale, const float *ori9)
+{
+    static_assert(NT == SAMPLE_ORDER_LANES && NT == 128, "the prefix is shared by two wavefronts");
+    float inv[9];
+    invert3(ori9, inv);
+    const float rad = 2.0f * scale;
+    const float sc = rad / (float)(PD / 2);
+    const sample_order_bins b = sample_order_bins_of(rad, fy, fz);
+    const int nbins = sample_order_nbins(b), lane = threadIdx.x;
+    for (int w = lane; w < (nbins + 1) / 2; w += NT) so.count[w] = 0;
+    __syncthreads();
+    for (int s = lane; s < PV; s += NT) {
+        float o[3];
+        sample_order_position(inv, sc, fx, fy, fz, s, o);
+        const int key = sample_order_key(b, o[1], o[2], Y, Z);
+        const unsigned old = atomicAdd(&so.count[sample_order_word(key)], sample_order_one(key));
+        tmp[s] = ((unsigned)key << 16) | (unsigned)sample_order_field(old, key); /* bin and rank in it */
+    }
+    __syncthreads();
+    int first, last;
+    sample_order_chunk(nbins, lane, first, last);
+    const unsigned mine = sample_order_chunk_total(so.count, first, last);
+    unsigned incl = mine; /* inclusive scan over the wavefront's 64 lanes */
+#pragma unroll
+    for (int d = 1; d < 64; d *= 2) {
+        const unsigned up = __shfl_up(incl, d, 64);
+        if ((lane & 63) >= d) incl += up;
+    }
+    if (lane == 63) so.wave_total = incl;
+    __syncthreads();
+    sample_order_chunk_prefix(so.count, first, last, incl - mine + (lane >= 64 ? so.wave_total : 0u));
+    __syncthreads();
+    for (int s = lane; s < PV; s += NT) {
+        const unsigned kr = tmp[s];
+        so.order[sample_order_slot(so.count, (int)(kr >> 16), (int)(kr & 0xffffu))] = (unsigned short)s;
     }
     __syncthreads();
 }
@@ -1061,8 +1102,9 @@ struct kpB_brief { /* BRIEF family: blur output (the middle pass goes back into 
 template <bool SIFT>
 struct kpB_smem {
     float patch[PV + 1];
-    struct {
+    union {
         typename std::conditional<SIFT, kpB_sift, kpB_brief>::type v;
+        sample_order_scratch order; /* the sampling order of a re-oriented record: dead once the patch is sampled, before v is first written */
     } u;
     float sc[16];
     float taps[8];
@@ -1071,6 +1113,9 @@ struct kpB_smem {
 static_assert(sizeof(kpB_smem<true>) > 160 * 1024 / 16 && sizeof(kpB_smem<true>) <= 160 * 1024 / 15 && sizeof(kpB_smem<false>) > 160 * 1024 / 16 &&
                   sizeof(kpB_smem<false>) <= 160 * 1024 / 15,
               "15 records per CU by LDS (160 KB)");
+/* kpB_sift::all is set before the sort and first read long after it */
+static_assert(sizeof(sample_order_scratch) <= offsetof(kpB_sift, all) && sizeof(sample_order_scratch) <= sizeof(kpB_brief),
+              "the sampling order overlays only what is dead while a patch is sampled");
 
 template <bool SIFT>
 __global__ __launch_bounds__(DESC_NT) void descriptor_kernel(sift3d_kp_params p, const sift3d_dkp *__restrict__ kps,
@@ -1114,6 +1159,8 @@ __global__ __launch_bounds__(DESC_NT) void descriptor_kernel(sift3d_kp_params p,
          * token of its CU (a counter in memory, indexed by the hardware's XCC / SE / SH / CU numbers) before the phase and
          * gives it back after it; the others wait asleep and cost no issue slots.  Which CU a counter really belongs to
          * only affects speed. */
+        /* the order of the samples is worked out first: a workgroup that waits for a token has it ready */
+        if (p.desc_order) wave_sort_samples<DESC_NT>(sm.u.order, reinterpret_cast<unsigned *>(sm.patch), lv.Y, lv.Z, kp->x, kp->y, kp->z, kp->scale, ori);
         int *tok = nullptr;
         if (p.sampler_cap > 0) {
             unsigned hw, xcc;
@@ -1131,7 +1178,10 @@ __global__ __launch_bounds__(DESC_NT) void descriptor_kernel(sift3d_kp_params p,
             }
             __syncthreads();
         }
-        wave_sample_patch<DESC_NT>(sm.patch, lv.img, lv.X, lv.XP, lv.Y, lv.Z, lv.Zl, lv.z_off, kp->x, kp->y, kp->z, kp->scale, ori);
+        if (p.desc_order)
+            wave_sample_patch<DESC_NT>(sm.patch, lv.img, lv.X, lv.XP, lv.Y, lv.Z, lv.Zl, lv.z_off, kp->x, kp->y, kp->z, kp->scale, ori, sm.u.order.order);
+        else
+            wave_sample_patch<DESC_NT>(sm.patch, lv.img, lv.X, lv.XP, lv.Y, lv.Z, lv.Zl, lv.z_off, kp->x, kp->y, kp->z, kp->scale, ori);
         if (tok && lane == 0) atomicSub(tok, 1);
     }
     /* ... and every record is normalised once more in main (featExtract.cpp:480) */

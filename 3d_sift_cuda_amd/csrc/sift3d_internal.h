@@ -182,6 +182,7 @@ struct sift3d_kp_params {
     int *sampler_tokens; /* phase B: per-CU count of workgroups in their sampling phase (SIFT3D_CU_SLOTS ints, zero between runs) */
     int sampler_cap;     /* at most this many per CU sample at a time (0: no limit) */
     int desc_seg;        /* descriptor kernel: records per segment of the XCD-contiguous order (a multiple of 8; 0: the whole list is one) */
+    int desc_order;      /* descriptor kernel: 1 = the lanes take a re-oriented record's samples in image-row order (sample_order.h), 0 = in patch order */
     const int *rec_shift; /* descriptor kernel: NULL, or SIFT3D_GROUPS ints -- record r of group g is stored at slot r + rec_shift[g] (several
                            * contexts writing one merged list: the slab driver) */
 };

@@ -290,6 +290,9 @@ typedef enum {
                                  * runs half a step behind the first (z pass and stores of a plane at the start of the next step), each
                                  * (half, role) pair of wavefronts running its own straight-line copy of the march.  0: by measurement
                                  * (default: from 11 taps up); 1: off (the kernel of rounds 2 - 5); 2: on */
+    SIFT3D_TUNE_DESC_ORDER,     /* descriptor kernel: which lane samples which patch voxel.  1 (default): in image order -- a counting sort by
+                                 * the image row (z, y cell) a sample reads hands the four lanes of a quad samples of one row
+                                 * (csrc/sample_order.h); 0: in patch order, fast patch axis closest to x */
     SIFT3D_TUNE_COUNT
 } sift3d_tuning;
 int sift3d_set_tuning(sift3d_ctx *ctx, int knob, int value);
