@@ -37,6 +37,7 @@ FEATCOMPOSE = os.path.join(CSRC, "_build", "featCompose")
 FEATFUSE = os.path.join(CSRC, "_build", "featFuse")
 FEATOVERLAP = os.path.join(CSRC, "_build", "featOverlap")
 FEATCLEAN = os.path.join(CSRC, "_build", "featClean")
+FEATCOMPARE = os.path.join(CSRC, "_build", "featCompare")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 7   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -198,6 +199,8 @@ def hip_lib():
     _sig(L.sift3d_surface_distances, I, P, P, I64, I64, I64, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_label_components, I, I, P, I64, I64, I64, C.c_int32, P, P, I64, P, P, C.c_char_p, I64)
     _sig(L.sift3d_clean_labels, I, P, I64, I64, I64, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_joint_histogram, I, I, P, P, I64, I64, I64, P, P, C.c_int32, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_image_similarity, I, P, P, P, I64, I64, I64, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -277,6 +280,11 @@ def host_lib():
     _sig(L.sift3d_ccl_check_extents, I, I64, I64, I64, C.c_char_p, I64)
     _sig(L.sift3d_clean_check, I, P, C.c_char_p, I64)
     _sig(L.sift3d_clean_report_text, I64, P, C.c_char_p, I64)
+    _sig(L.sift3d_similarity_defaults, None, P)
+    _sig(L.sift3d_similarity_check, I, P, C.c_char_p, I64)
+    _sig(L.sift3d_similarity_measures, I, P, C.c_int32, P, F, F, C.c_int32, P)
+    _sig(L.sift3d_similarity_label_measures, None, C.c_int32, P, F, F, C.c_int32, P)
+    _sig(L.sift3d_similarity_report_text, I64, P, P, C.c_int32, C.c_char_p, I64)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -1633,6 +1641,129 @@ def clean_labels(labels, return_ms=False, **params):
     d = clean_report_dict(rep)
     d["struct"] = rep
     return (out, d, ms.value) if return_ms else (out, d)
+
+
+# ---- similarity of two images on one grid (featCompare), DESIGN.md section 7o -------------------------------------------------------
+SIMILARITY_MAX_BINS, SIMILARITY_MAX_LABELS, SIMILARITY_BINS = 64, 64, (8, 16, 32, 64)
+SIMILARITY_SUMS = ("n", "sa", "sb", "saa", "sbb", "sab")
+SIMILARITY_MEASURES = ("mi", "nmi", "rho", "rms", "h_a", "h_b", "h_ab")
+SIMILARITY_FLUSH = {"slices": 0, "atomics": 1}
+
+
+class SimilarityParams(C.Structure):
+    """sift3d_similarity_params"""
+    _fields_ = [("bins", C.c_int32), ("same_scale", C.c_int32), ("max_labels", C.c_int32), ("device", C.c_int32), ("flush", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SimilarityRecord(C.Structure):
+    """sift3d_similarity_record"""
+    _fields_ = [("bins", C.c_int32), ("same_scale", C.c_int32), ("empty_range", C.c_int32), ("reserved", C.c_int32), ("a_lo", C.c_float), ("a_hi", C.c_float),
+                ("b_lo", C.c_float), ("b_hi", C.c_float), ("excluded", C.c_int64), ("sums", C.c_int64 * len(SIMILARITY_SUMS))] + \
+               [(name, C.c_double) for name in SIMILARITY_MEASURES] + [("kernel_ms", C.c_double), ("hist", C.c_int64 * (SIMILARITY_MAX_BINS * SIMILARITY_MAX_BINS))]
+
+
+class SimilarityLabelRecord(C.Structure):
+    """sift3d_similarity_label_record"""
+    _fields_ = [("label", C.c_int32), ("reserved", C.c_int32), ("sums", C.c_int64 * len(SIMILARITY_SUMS)), ("rho", C.c_double), ("rms", C.c_double)]
+
+
+def similarity_params(**kw):
+    """sift3d_similarity_defaults, then the given fields (bins, same_scale, max_labels, device, flush: 0 / "slices", 1 / "atomics")"""
+    p = SimilarityParams()
+    host_lib().sift3d_similarity_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(SimilarityParams._fields_):
+            raise ValueError("no similarity parameter %s" % k)
+        setattr(p, k, int(SIMILARITY_FLUSH.get(v, v)) if k == "flush" else int(v))
+    return p
+
+
+def similarity_check(p):
+    """sift3d_similarity_check: None, or the text with which the parameters are refused"""
+    err = C.create_string_buffer(512)
+    return None if host_lib().sift3d_similarity_check(C.byref(p), err, len(err)) == 0 else err.value.decode()
+
+
+def _image_similarity_dict(r, labels):
+    bins = int(r.bins)
+    d = {"bins": bins, "same_scale": int(r.same_scale), "empty_range": int(r.empty_range), "range_a": (np.float32(r.a_lo), np.float32(r.a_hi)),
+         "range_b": (np.float32(r.b_lo), np.float32(r.b_hi)), "excluded": int(r.excluded), "sums": [int(v) for v in r.sums], "n": int(r.sums[0]),
+         "hist": np.array(r.hist[:bins * bins], np.int64).reshape(bins, bins), "kernel_ms": float(r.kernel_ms), "struct": r}
+    d.update({name: float(getattr(r, name)) for name in SIMILARITY_MEASURES})
+    if labels is not None:
+        d["labels"] = [{"label": int(l.label), "sums": [int(v) for v in l.sums], "n": int(l.sums[0]), "rho": float(l.rho), "rms": float(l.rms)} for l in labels]
+        d["label_structs"] = labels
+    return d
+
+
+def similarity_measures(hist, sums, lo=0.0, hi=1.0, same_scale=False):
+    """sift3d_similarity_measures of a joint histogram (bins x bins int64) and its six sums: a dict of mi, nmi, rho, rms, h_a, h_b,
+    h_ab; lo, hi: A's range (read under same_scale only)"""
+    h = np.ascontiguousarray(hist, np.int64)
+    s = np.ascontiguousarray(sums, np.int64).reshape(len(SIMILARITY_SUMS))
+    bins = h.shape[0]
+    if h.ndim != 2 or h.shape[1] != bins:
+        raise ValueError("hist is bins x bins")
+    r = SimilarityRecord()
+    if host_lib().sift3d_similarity_measures(h.ctypes.data, bins, s.ctypes.data, float(lo), float(hi), int(bool(same_scale)), C.byref(r)) != 0:
+        raise Sift3DError("sift3d_similarity_measures: bins = %d is not 8, 16, 32 or 64" % bins)
+    return {name: float(getattr(r, name)) for name in SIMILARITY_MEASURES}
+
+
+def similarity_label_measures(label, sums, lo=0.0, hi=1.0, same_scale=False):
+    """sift3d_similarity_label_measures: (rho, rms) of one label's six sums"""
+    s = np.ascontiguousarray(sums, np.int64).reshape(len(SIMILARITY_SUMS))
+    r = SimilarityLabelRecord()
+    host_lib().sift3d_similarity_label_measures(int(label), s.ctypes.data, float(lo), float(hi), int(bool(same_scale)), C.byref(r))
+    return float(r.rho), float(r.rms)
+
+
+def similarity_report_text(result):
+    """sift3d_similarity_report_text of what image_similarity returned"""
+    lab = result.get("label_structs")
+    args = (C.byref(result["struct"]), None if lab is None else C.byref(lab), 0 if lab is None else len(result["labels"]))
+    need = host_lib().sift3d_similarity_report_text(*args, None, 0)
+    if need < 0:
+        raise Sift3DError("sift3d_similarity_report_text -> %d" % need)
+    buf = C.create_string_buffer(need + 1)
+    if host_lib().sift3d_similarity_report_text(*args, buf, len(buf)) != need:
+        raise Sift3DError("sift3d_similarity_report_text: the length changed")
+    return buf.value.decode()
+
+
+def joint_histogram(a, b, a_range, b_range, bins=64, device=0, return_ms=False):
+    """sift3d_joint_histogram of two float32 volumes (nz, ny, nx) quantised with the given (lo, hi) ranges: (hist int64 bins x bins,
+    the six sums as Python integers, excluded).  return_ms=True appends kernel_ms."""
+    a, b = _f32(a), _f32(b)
+    if a.shape != b.shape or a.ndim != 3:
+        raise ValueError("the images are (nz, ny, nx) and of one shape")
+    nz, ny, nx = a.shape
+    bins = int(bins)
+    hist, sums = np.zeros((max(bins, 0), max(bins, 0)), np.int64), np.zeros(len(SIMILARITY_SUMS), np.int64)
+    ar, br = (C.c_float * 2)(*[float(v) for v in a_range]), (C.c_float * 2)(*[float(v) for v in b_range])
+    excluded, ms = C.c_int64(0), C.c_double(0.0)
+    _call("sift3d_joint_histogram", int(device), a.ctypes.data, b.ctypes.data, nx, ny, nz, ar, br, bins, hist.ctypes.data, sums.ctypes.data, C.byref(excluded),
+          C.byref(ms))
+    out = (hist, [int(v) for v in sums], int(excluded.value))
+    return out + (ms.value,) if return_ms else out
+
+
+def image_similarity(a, b, labels=None, **params):
+    """sift3d_image_similarity of two float32 volumes (nz, ny, nx) on one grid: a dict of the record's fields (hist as int64 bins x
+    bins, sums as Python integers, n, range_a, range_b, the measures, kernel_ms; the structures under "struct" and
+    "label_structs") and, with labels (a float32 label volume of that shape), "labels": one dict per label.  params: fields of
+    similarity_params."""
+    a, b = _f32(a), _f32(b)
+    lb = None if labels is None else _f32(labels)
+    if a.shape != b.shape or a.ndim != 3 or (lb is not None and lb.shape != a.shape):
+        raise ValueError("the images and the labels are (nz, ny, nx) and of one shape")
+    nz, ny, nx = a.shape
+    p = similarity_params(**params)
+    rec = SimilarityRecord()
+    lrec = None if lb is None else (SimilarityLabelRecord * SIMILARITY_MAX_LABELS)()
+    n = C.c_int32(0)
+    _call("sift3d_image_similarity", a.ctypes.data, b.ctypes.data, _ptr(lb), nx, ny, nz, C.byref(p), C.byref(rec), lrec, C.byref(n))
+    return _image_similarity_dict(rec, None if lb is None else (SimilarityLabelRecord * n.value)(*lrec[:n.value]))
 
 
 def _map12(m):

@@ -1354,6 +1354,98 @@ int sift3d_clean_check(const sift3d_clean_params *p, char *err, int64_t err_len)
  * (without the terminating 0), as snprintf does; buf holds at most len - 1 characters of it.  4096 bytes hold every report. */
 int64_t sift3d_clean_report_text(const sift3d_clean_report *rep, char *buf, int64_t len);
 
+/* ---- similarity of two images on one grid (featCompare; beyond the reference) ---------------------------------------------------
+ * DESIGN.md section 7o states the contract; tests/similarity_oracle.c restates it serially.  The GPU makes counts and integer sums
+ * only, so no result depends on tiling, launch order or the order atomics arrive in; every derived value is host arithmetic.
+ *
+ * Inputs: A and B are nx ny nz floats, x fastest; extents 1 .. 4096 each, at most 2^30 voxels; bins one of 8, 16, 32, 64.
+ * Quantisation: section 7f's q (above: -1 for a non-finite value, else 0 .. 1023, in double, ties to even).  A with A's range
+ * (sift3d_blockmatch_range); B with B's own range, or with A's under same_scale.  An image that needs a range and has no two
+ * distinct finite values is no error: empty_range is 1 for A, 2 for B (never under same_scale, where B needs none), 3 for both;
+ * then no voxel counts (n = 0, excluded = nx ny nz), the histogram is zero, every derived value is NaN and nothing is launched.
+ * A voxel counts when qA >= 0 and qB >= 0; excluded is the number of the others.
+ * Joint histogram: hist[i bins + j], int64, is the number of counted voxels with qA >> s = i and qB >> s = j, s = 10 - log2 bins.
+ * Sums over the counted voxels, int64 each (below 2^51): [0] n, [1] Sa = sum qA, [2] Sb, [3] Saa = sum qA^2, [4] Sbb, [5] Sab.
+ * Per label (optional third volume L of section 7j's labels: non-finite is unlabelled, else an integer 0 .. 65535): for every
+ * label that occurs on a counted voxel, in ascending order, the same six sums over the counted voxels that carry it.  A counted
+ * voxel with a non-finite L is in no label's row and stays in the whole-image numbers.  More than max_labels such labels refuse
+ * the call.  There is no histogram per label.
+ * Derived values (sift3d_similarity_measures; one sequence of double operations, built without contraction):
+ *   D = Saa - 2 Sab + Sbb;  rms = sqrt((double)D / (double)n) * (((double)hi - (double)lo) / 1023.0) under same_scale (lo, hi: A's
+ *   range), else NaN;
+ *   rho: C = n Sab - Sa Sb, Va = n Saa - Sa^2, Vb = n Sbb - Sb^2, each exact in 128-bit integers and converted to double once;
+ *   rho = (double)C / (sqrt(Va) * sqrt(Vb)), NaN unless Va > 0 and Vb > 0;
+ *   H(c) = log((double)n) - S / (double)n, S the left-to-right sum of (double)c * log((double)c) over the cells c > 0 in ascending
+ *   index order: h_a over the row sums, h_b over the column sums, h_ab over the bins^2 cells in row-major order;
+ *   mi = (h_a + h_b) - h_ab;  nmi = (h_a + h_b) / h_ab, NaN unless h_ab > 0;  n = 0: NaN throughout.
+ *   Per label: n, rho and rms from that label's sums, by the same text. */
+#define SIFT3D_SIMILARITY_MAX_BINS 64
+#define SIFT3D_SIMILARITY_MAX_LABELS 64
+#define SIFT3D_SIMILARITY_SUMS 6
+
+typedef struct {
+    int32_t bins;       /* 64; or 8, 16, 32 */
+    int32_t same_scale; /* 0; 1: B is quantised with A's range and rms is given */
+    int32_t max_labels; /* 64; 1 .. SIFT3D_SIMILARITY_MAX_LABELS */
+    int32_t device;     /* 0 */
+    int32_t flush;      /* 1: 64-bit global atomic adds of the workgroups' non-zero cells; 0: the workgroups' histograms as slices in
+                           global memory, summed by a second kernel.  Both are exact; DESIGN.md section 7o has their times */
+    int32_t reserved;
+} sift3d_similarity_params;
+
+typedef struct {
+    int32_t bins, same_scale;
+    int32_t empty_range; /* 0; 1: A has no range; 2: B; 3: both */
+    int32_t reserved;
+    float a_lo, a_hi, b_lo, b_hi; /* the ranges the images were quantised with (b: a's under same_scale) */
+    int64_t excluded;
+    int64_t sums[SIFT3D_SIMILARITY_SUMS]; /* n, Sa, Sb, Saa, Sbb, Sab */
+    double mi, nmi, rho, rms, h_a, h_b, h_ab;
+    double kernel_ms; /* device time of the launches */
+    int64_t hist[SIFT3D_SIMILARITY_MAX_BINS * SIFT3D_SIMILARITY_MAX_BINS]; /* the first bins^2 words */
+} sift3d_similarity_record;
+
+typedef struct {
+    int32_t label;
+    int32_t reserved;
+    int64_t sums[SIFT3D_SIMILARITY_SUMS];
+    double rho, rms;
+} sift3d_similarity_label_record;
+
+/* The kernel alone on host arrays, with the ranges the caller passes (lo, hi each: finite, hi > lo): hist bins^2 int64, sums
+ * SIFT3D_SIMILARITY_SUMS int64, *excluded; kernel_ms may be NULL.  SIFT3D_ERR_ARG with text naming the argument, before anything
+ * is allocated: a null pointer, an extent outside 1 .. 4096, more than 2^30 voxels, bins other than 8, 16, 32, 64, a range that
+ * is not finite or has hi <= lo. */
+int sift3d_joint_histogram(int device, const float *a, const float *b, int64_t nx, int64_t ny, int64_t nz, const float a_range[2],
+                           const float b_range[2], int32_t bins, int64_t *hist, int64_t *sums, int64_t *excluded, double *kernel_ms, char *err,
+                           int64_t err_len);
+/* The stage: takes the ranges, checks the labels, launches and computes the derived values.  labels may be NULL; with labels,
+ * label_records has room for p->max_labels records and *n_labels is how many were written.  p NULL: defaults.  SIFT3D_ERR_ARG with
+ * text, before anything is allocated: what sift3d_joint_histogram refuses, what sift3d_similarity_check refuses, a voxel of labels
+ * that sift3d_fuse_check_labels refuses (the voxel in the text), more than max_labels labels on counted voxels (the count in the
+ * text; nothing is dropped). */
+int sift3d_image_similarity(const float *a, const float *b, const float *labels, int64_t nx, int64_t ny, int64_t nz,
+                            const sift3d_similarity_params *p, sift3d_similarity_record *record, sift3d_similarity_label_record *label_records,
+                            int32_t *n_labels, char *err, int64_t err_len);
+/* Host helpers (also in libsift3d_host.so). */
+void sift3d_similarity_defaults(sift3d_similarity_params *p);
+/* 0, or -1 and into err which of bins, same_scale, max_labels and flush is refused, with its value */
+int sift3d_similarity_check(const sift3d_similarity_params *p, char *err, int64_t err_len);
+/* The derived values of a histogram (bins^2 int64; may be record->hist) and its sums into record's bins, same_scale, sums, mi, nmi,
+ * rho, rms, h_a, h_b and h_ab; lo, hi: A's range (read under same_scale only).  Nothing else of record is touched.  -1 for a null
+ * pointer or bins other than 8, 16, 32, 64, else 0. */
+int sift3d_similarity_measures(const int64_t *hist, int32_t bins, const int64_t *sums, float lo, float hi, int32_t same_scale,
+                               sift3d_similarity_record *record);
+/* rho and rms of one label's sums into rec, by the same text; rec's label and sums are set from the arguments */
+void sift3d_similarity_label_measures(int32_t label, const int64_t *sums, float lo, float hi, int32_t same_scale,
+                                      sift3d_similarity_label_record *rec);
+/* The report as text: "# range_a lo hi", "# range_b lo hi", "# same_scale 0|1", "# voxels counted excluded", the line
+ * "mi nmi rho rms h_a h_b h_ab" and, with n_labels >= 0 and label_records given, "# label n rho rms" and one line per label.  A NaN
+ * is written as nan.  Returns the length the whole text needs (without the terminating 0), as snprintf does; buf holds at most
+ * len - 1 characters of it.  8192 bytes hold every report. */
+int64_t sift3d_similarity_report_text(const sift3d_similarity_record *record, const sift3d_similarity_label_record *label_records,
+                                      int32_t n_labels, char *buf, int64_t len);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
