@@ -89,11 +89,11 @@ static int ratio_search(int device, const sift3d_feature *db, int64_t n_db, cons
     DEVCHK(dc, dc.upload(&d_stats, stats, 6));
     DEVCHK(dc, sift3d_launch_knn_norms(dc.s, d_db, n_db, d_dbn, d_stats));
     DEVCHK(dc, sift3d_launch_knn_norms(dc.s, d_q, n_q, d_qn, d_stats + 3));
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     const sift3d_scale_intervals &iv = sift3d_scale_ivs();
     DEVCHK(dc, sift3d_launch_ratio(dc.s, d_db, d_dbn, n_db, d_q, d_qn, n_q, d_geo, d_info, iv.lo[0], iv.hi[0], d_out, d_out + n_q, d_out + 2 * n_q,
                                    d_out + 3 * n_q));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download(i1, d_out, (size_t)n_q));
     DEVCHK(dc, dc.download(d1, d_out + n_q, (size_t)n_q));
     DEVCHK(dc, dc.download(i2, d_out + 2 * n_q, (size_t)n_q));

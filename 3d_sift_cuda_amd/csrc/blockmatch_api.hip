@@ -12,7 +12,6 @@
 
 #include "field_call.h"
 
-hipError_t sift3d_launch_bm_quantize(hipStream_t s, const float *src, int64_t n, double lo, double hi, short *dst);
 hipError_t sift3d_launch_block_match(hipStream_t s, const short *qf, const short *qw, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
                                      int64_t stride, const int64_t n[3], int b, int r, int generic, unsigned *out);
 hipError_t sift3d_launch_block_match_ncc(hipStream_t s, const short *qf, const short *qw, int64_t nx, int64_t ny, int64_t nz, const int64_t first[3],
@@ -72,17 +71,13 @@ static int block_match(int metric, int device, const float *f, const float *w, i
     unsigned *d_out;
     DEVCHK(dc, dc.open(device));
     if (dc.alloc(&d_v, nv) != hipSuccess || dc.alloc(&d_qf, nv) != hipSuccess || dc.alloc(&d_qw, nv) != hipSuccess ||
-        dc.alloc(&d_out, N * SIFT3D_BLOCKMATCH_WORDS) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu bytes on device %d", 8 * nv, 64 * N, device);
-    }
-    DEVCHK(dc, dc.to_device(d_v, f, nv));
-    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_qf));
-    DEVCHK(dc, dc.to_device(d_v, w, nv));
-    DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)wlo, (double)whi, d_qw));
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+        dc.alloc(&d_out, N * SIFT3D_BLOCKMATCH_WORDS) != hipSuccess)
+        return dc.no_memory();
+    DEVCHK(dc, send_quantised(dc, f, nv, lo, hi, d_v, d_qf));
+    DEVCHK(dc, send_quantised(dc, w, nv, wlo, whi, d_v, d_qw));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, launch_search(metric, dc.s, d_qf, d_qw, nx, ny, nz, first, stride, count, b, r, generic, d_out));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download((unsigned *)out, d_out, N * SIFT3D_BLOCKMATCH_WORDS));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));
@@ -180,14 +175,10 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
         DEVCHK(dc, dc.open(device));
         if (dc.alloc(&d_w, nf) != hipSuccess || dc.alloc(&d_m, nm) != hipSuccess || dc.alloc(&d_qf, nf) != hipSuccess ||
             dc.alloc(&d_qw, nf) != hipSuccess || dc.alloc(&d_words, (size_t)NL * SIFT3D_BLOCKMATCH_WORDS) != hipSuccess ||
-            dc.alloc(&d_nodes, max_nodes) != hipSuccess) {
-            (void)hipGetLastError();
-            return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu + %zu + %zu bytes on device %d", 8 * nf, 4 * nm,
-                             64 * (size_t)NL, 16 * max_nodes, device);
-        }
+            dc.alloc(&d_nodes, max_nodes) != hipSuccess)
+            return dc.no_memory();
         /* F is quantised once; its float copy's buffer then holds W */
-        DEVCHK(dc, dc.to_device(d_w, fixed, nf));
-        DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, (int64_t)nf, (double)rp.lo, (double)rp.hi, d_qf));
+        DEVCHK(dc, send_quantised(dc, fixed, nf, rp.lo, rp.hi, d_w, d_qf));
         DEVCHK(dc, dc.to_device(d_m, moving, nm));
         std::vector<uint32_t> words((size_t)NL * SIFT3D_BLOCKMATCH_WORDS);
         std::vector<float> y((size_t)(3 * NL)), v((size_t)(3 * NL));
@@ -195,16 +186,16 @@ extern "C" int sift3d_refine_field_intensity_metric(int device, const float *fix
         for (int round = 0; round < p.rounds; round++) {
             sift3d_blockmatch_round &r = rp.round[round];
             DEVCHK(dc, send_nodes(dc, cur, nodes, d_nodes));
-            DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+            DEVCHK(dc, dc.mark(0));
             DEVCHK(dc, sift3d_launch_field_warp(dc.s, d_m, mx, my, mz, d_w, fx, fy, fz, map, cterm, kterm, cur.origin, cur.spacing, cur.n, d_nodes,
                                                 SIFT3D_INTERP_LINEAR, std::nanf("")));
-            DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+            DEVCHK(dc, dc.mark(1));
             DEVCHK(dc, dc.sync());
             DEVCHK(dc, dc.elapsed_ms(&r.warp_ms));
-            DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+            DEVCHK(dc, dc.mark(0));
             DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, (int64_t)nf, (double)wlo, (double)whi, d_qw));
             DEVCHK(dc, launch_search(metric, dc.s, d_qf, d_qw, fx, fy, fz, first, p.stride, count, p.block, p.search, 0, d_words));
-            DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+            DEVCHK(dc, dc.mark(1));
             DEVCHK(dc, dc.download(words.data(), d_words, words.size()));
             DEVCHK(dc, dc.sync());
             DEVCHK(dc, dc.elapsed_ms(&r.match_ms));

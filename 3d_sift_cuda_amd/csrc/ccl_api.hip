@@ -10,7 +10,6 @@
 
 #include "device_call.h"
 
-hipError_t sift3d_launch_ccl_labels(hipStream_t s, const float *labels, int64_t n, unsigned short *lab, unsigned long long *valid);
 hipError_t sift3d_launch_ccl_bricks(hipStream_t s, int conn, const unsigned short *lab, const unsigned long long *valid, int64_t nx, int64_t ny, int64_t nz,
                                     unsigned *parent);
 hipError_t sift3d_launch_ccl_merge(hipStream_t s, int conn, const unsigned short *lab, const unsigned long long *valid, int64_t nx, int64_t ny, int64_t nz,
@@ -39,15 +38,7 @@ struct ccl_planes {
     int *flag = nullptr;                /* the root flags; in the cleaning then the small flags */
     void *scan_tmp = nullptr;
     size_t scan_bytes = 0;
-    hipEvent_t e[CCL_EVENTS] = {};
-    ccl_planes() = default;
-    ccl_planes(const ccl_planes &) = delete;
-    void operator=(const ccl_planes &) = delete;
-    ~ccl_planes()
-    {
-        for (hipEvent_t x : e)
-            if (x) hipEventDestroy(x);
-    }
+    stage_events<CCL_EVENTS> ev;
     /* false without memory */
     bool alloc(device_call &dc, size_t nv)
     {
@@ -59,27 +50,21 @@ struct ccl_planes {
         scan_tmp = tmp;
         return ok;
     }
-    hipError_t create_events()
-    {
-        hipError_t rc = hipSuccess;
-        for (int i = 0; i < CCL_EVENTS && rc == hipSuccess; i++) rc = hipEventCreate(&e[i]);
-        return rc;
-    }
     /* the first half: f to the roots, their flags and the flags' scan (in the parent plane); *ncomp the number of components.
      * Synchronises, since the caller sizes the records by the count. */
     hipError_t label(device_call &dc, int conn, int64_t nx, int64_t ny, int64_t nz, int64_t *ncomp)
     {
         const int64_t n = nx * ny * nz;
         int last[2] = {0, 0};
-        hipError_t rc = hipEventRecord(e[0], dc.s);
-        if (rc == hipSuccess) rc = sift3d_launch_ccl_labels(dc.s, f, n, lab, valid);
-        if (rc == hipSuccess) rc = hipEventRecord(e[1], dc.s);
+        hipError_t rc = ev.record(0, dc.s);
+        if (rc == hipSuccess) rc = sift3d_launch_label_plane(dc.s, f, n, lab, valid);
+        if (rc == hipSuccess) rc = ev.record(1, dc.s);
         if (rc == hipSuccess) rc = sift3d_launch_ccl_bricks(dc.s, conn, lab, valid, nx, ny, nz, parent);
-        if (rc == hipSuccess) rc = hipEventRecord(e[2], dc.s);
+        if (rc == hipSuccess) rc = ev.record(2, dc.s);
         if (rc == hipSuccess) rc = sift3d_launch_ccl_merge(dc.s, conn, lab, valid, nx, ny, nz, parent);
-        if (rc == hipSuccess) rc = hipEventRecord(e[3], dc.s);
+        if (rc == hipSuccess) rc = ev.record(3, dc.s);
         if (rc == hipSuccess) rc = sift3d_launch_ccl_flatten(dc.s, parent, n, root, flag);
-        if (rc == hipSuccess) rc = hipEventRecord(e[4], dc.s);
+        if (rc == hipSuccess) rc = ev.record(4, dc.s);
         /* the parent plane is free: it takes the scan */
         if (rc == hipSuccess) rc = sift3d_scan_counts(dc.s, scan_tmp, scan_bytes, flag, (int *)parent, n);
         if (rc == hipSuccess) rc = dc.download(&last[0], (const int *)parent + (n - 1), 1);
@@ -94,29 +79,17 @@ struct ccl_planes {
         const int64_t n = nx * ny * nz;
         hipError_t rc = sift3d_launch_ccl_number(dc.s, root, (const int *)parent, flag, lab, nx, ny, n, rec);
         if (rc == hipSuccess && rec) rc = sift3d_launch_ccl_records(dc.s, root, nx, ny, n, rec);
-        if (rc == hipSuccess) rc = hipEventRecord(e[5], dc.s);
+        if (rc == hipSuccess) rc = ev.record(5, dc.s);
         return rc;
     }
     /* total, label plane, brick pass, border merge, flatten, numbers and records; the stream has been synchronised */
     hipError_t elapsed(double ms[SIFT3D_CCL_STAGES]) const
     {
-        for (int i = 0; i < SIFT3D_CCL_STAGES; i++) {
-            float t = 0;
-            const hipError_t rc = i == 0 ? hipEventElapsedTime(&t, e[0], e[5]) : hipEventElapsedTime(&t, e[i - 1], e[i]);
-            if (rc != hipSuccess) return rc;
-            ms[i] = (double)t;
-        }
-        return hipSuccess;
+        hipError_t rc = ev.elapsed(0, 5, &ms[0]);
+        for (int i = 1; i < SIFT3D_CCL_STAGES && rc == hipSuccess; i++) rc = ev.elapsed(i - 1, i, &ms[i]);
+        return rc;
     }
 };
-
-/* SIFT3D_OK, or SIFT3D_ERR_ARG and the first voxel that is no label */
-static int check_labels(const float *labels, int64_t n, char *err, int64_t err_len)
-{
-    const int64_t at = sift3d_fuse_check_labels(labels, n);
-    if (at < 0) return SIFT3D_OK;
-    return call_fail(err, err_len, SIFT3D_ERR_ARG, "the label %g at voxel %lld is neither non-finite nor an integer 0 .. 65535", (double)labels[at], (long long)at);
-}
 
 extern "C" int sift3d_label_components(int device, const float *labels, int64_t nx, int64_t ny, int64_t nz, int32_t connectivity, uint32_t *comp,
                                        sift3d_component_record *records, int64_t max_records, int64_t *n_components, double *kernel_ms, char *err,
@@ -131,29 +104,22 @@ extern "C" int sift3d_label_components(int device, const float *labels, int64_t 
     if (connectivity != 6 && connectivity != 26) return call_fail(err, err_len, SIFT3D_ERR_ARG, "connectivity = %d: 6 or 26", (int)connectivity);
     if (records && max_records < 0) return call_fail(err, err_len, SIFT3D_ERR_ARG, "max_records = %lld: negative", (long long)max_records);
     const int64_t n = nx * ny * nz;
-    const int bad = check_labels(labels, n, err, err_len);
+    const int bad = check_labels("", labels, n, err, err_len);
     if (bad != SIFT3D_OK) return bad;
 
     const size_t nv = (size_t)n;
     device_call dc(err, err_len);
     ccl_planes pl;
     DEVCHK(dc, dc.open(device, false));
-    DEVCHK(dc, pl.create_events());
-    if (!pl.alloc(dc, nv)) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", 18 * nv + nv / 8 + pl.scan_bytes, device);
-    }
+    DEVCHK(dc, pl.ev.create());
+    if (!pl.alloc(dc, nv)) return dc.no_memory();
     DEVCHK(dc, dc.to_device(pl.f, labels, nv));
     int64_t ncomp = 0;
     DEVCHK(dc, pl.label(dc, connectivity, nx, ny, nz, &ncomp));
     *n_components = ncomp;
     const bool fits = records && ncomp <= max_records;
     sift3d_component_record *d_rec = nullptr;
-    if (fits && ncomp > 0 && dc.alloc(&d_rec, (size_t)ncomp) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d for the records of %lld components",
-                         sizeof(sift3d_component_record) * (size_t)ncomp, device, (long long)ncomp);
-    }
+    if (fits && ncomp > 0 && dc.alloc(&d_rec, (size_t)ncomp) != hipSuccess) return dc.no_memory(" for the records of %lld components", (long long)ncomp);
     DEVCHK(dc, pl.number(dc, nx, ny, nz, d_rec));
     if (comp) DEVCHK(dc, dc.download((unsigned *)comp, pl.root, nv));
     if (d_rec) DEVCHK(dc, dc.download(records, d_rec, (size_t)ncomp));
@@ -178,15 +144,15 @@ extern "C" int sift3d_clean_labels(const float *labels, int64_t nx, int64_t ny, 
     if (sift3d_ccl_check_extents(nx, ny, nz, err, err_len) != 0) return SIFT3D_ERR_ARG;
     if (sift3d_clean_check(&p, err, err_len) != 0) return SIFT3D_ERR_ARG;
     const int64_t n = nx * ny * nz;
-    const int bad = check_labels(labels, n, err, err_len);
+    const int bad = check_labels("", labels, n, err, err_len);
     if (bad != SIFT3D_OK) return bad;
     /* the labels present, in ascending order, and the index of each among them; a round brings no new label */
-    std::vector<unsigned short> present, lidx(65536, 0);
+    std::vector<unsigned short> present, lidx(SIFT3D_LABEL_COUNT, 0);
     {
-        std::vector<unsigned char> seen(65536, 0);
+        std::vector<unsigned char> seen(SIFT3D_LABEL_COUNT, 0);
         for (int64_t i = 0; i < n; i++)
             if (std::isfinite(labels[i])) seen[(int)labels[i]] = 1;
-        for (int l = 0; l < 65536; l++)
+        for (int l = 0; l < SIFT3D_LABEL_COUNT; l++)
             if (seen[l]) {
                 lidx[l] = (unsigned short)present.size();
                 present.push_back((unsigned short)l);
@@ -203,14 +169,12 @@ extern "C" int sift3d_clean_labels(const float *labels, int64_t nx, int64_t ny, 
     unsigned *d_votes = nullptr, *d_fresh = nullptr;
     size_t cap_small = 0;
     DEVCHK(dc, dc.open(p.device, false));
-    DEVCHK(dc, pl.create_events());
-    if (!pl.alloc(dc, nv) || dc.alloc(&d_sidx, nv) != hipSuccess || dc.alloc(&d_lidx, 65536) != hipSuccess || dc.alloc(&d_present, 65536) != hipSuccess ||
-        dc.alloc(&d_counts, 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", 22 * nv + nv / 8 + pl.scan_bytes, p.device);
-    }
+    DEVCHK(dc, pl.ev.create());
+    if (!pl.alloc(dc, nv) || dc.alloc(&d_sidx, nv) != hipSuccess || dc.alloc(&d_lidx, SIFT3D_LABEL_COUNT) != hipSuccess ||
+        dc.alloc(&d_present, SIFT3D_LABEL_COUNT) != hipSuccess || dc.alloc(&d_counts, 4) != hipSuccess)
+        return dc.no_memory();
     DEVCHK(dc, dc.to_device(pl.f, labels, nv));
-    DEVCHK(dc, dc.to_device(d_lidx, lidx.data(), 65536));
+    DEVCHK(dc, dc.to_device(d_lidx, lidx.data(), SIFT3D_LABEL_COUNT));
     if (nl > 0) DEVCHK(dc, dc.to_device(d_present, present.data(), (size_t)nl));
     sift3d_clean_report rep;
     memset(&rep, 0, sizeof rep);
@@ -237,17 +201,14 @@ extern "C" int sift3d_clean_labels(const float *labels, int64_t nx, int64_t ny, 
         }
         rr.small = nsmall;
         unsigned long long counts[4] = {0, 0, 0, 0};
-        hipEvent_t e0 = pl.e[0], e1 = pl.e[5];
         if (nsmall > 0) {
             const int64_t bytes = nsmall * nl * (int64_t)sizeof(unsigned);
             if (bytes > SIFT3D_CLEAN_VOTE_BYTES)
                 return call_fail(err, err_len, SIFT3D_ERR_ARG, "round %d: %lld small components and %d labels need a vote table of %lld bytes: more than %lld",
                                  r + 1, (long long)nsmall, nl, (long long)bytes, (long long)SIFT3D_CLEAN_VOTE_BYTES);
             if ((size_t)nsmall > cap_small) {
-                if (dc.alloc(&d_votes, (size_t)nsmall * nl) != hipSuccess || dc.alloc(&d_fresh, (size_t)nsmall) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %lld bytes on device %d for the vote table", (long long)bytes, p.device);
-                }
+                if (dc.alloc(&d_votes, (size_t)nsmall * nl) != hipSuccess || dc.alloc(&d_fresh, (size_t)nsmall) != hipSuccess)
+                    return dc.no_memory(" for the vote table");
                 cap_small = (size_t)nsmall;
             }
             DEVCHK(dc, hipMemsetAsync(d_votes, 0, (size_t)bytes, dc.s));
@@ -255,13 +216,13 @@ extern "C" int sift3d_clean_labels(const float *labels, int64_t nx, int64_t ny, 
             DEVCHK(dc, sift3d_launch_ccl_votes(dc.s, pl.root, pl.lab, pl.flag, d_sidx, d_lidx, nx, ny, nz, nl, d_votes));
             DEVCHK(dc, sift3d_launch_ccl_decide(dc.s, pl.flag, d_sidx, d_size, d_votes, d_present, nl, ncomp, d_fresh, d_counts));
             DEVCHK(dc, sift3d_launch_ccl_apply(dc.s, pl.root, pl.flag, d_sidx, d_fresh, n, pl.f));
-            DEVCHK(dc, hipEventRecord(pl.e[5], dc.s)); /* the round ends here */
+            DEVCHK(dc, pl.ev.record(5, dc.s)); /* the round ends here */
             DEVCHK(dc, dc.download(counts, d_counts, 4));
         }
         DEVCHK(dc, dc.sync());
-        float t = 0;
-        DEVCHK(dc, hipEventElapsedTime(&t, e0, e1));
-        total_ms += (double)t;
+        double ms = 0.0;
+        DEVCHK(dc, pl.ev.elapsed(0, 5, &ms));
+        total_ms += ms;
         rr.resolved = (int64_t)counts[0];
         rr.resolved_voxels = (int64_t)counts[1];
         rr.unresolved = (int64_t)counts[2];

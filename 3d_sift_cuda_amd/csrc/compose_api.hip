@@ -16,17 +16,6 @@ hipError_t sift3d_launch_compose_residual(hipStream_t s, const float4 *f1, const
                                           const float o2[3], float h2, const int64_t n2[3], const float go[3], float gh, const int64_t gn[3],
                                           const double p1[12], const double p2[12], const double pc[12], const float4 *w4, double *res2);
 
-namespace {
-/* the third event of a call that times two kernels: device_call holds two */
-struct extra_event {
-    hipEvent_t e = nullptr;
-    ~extra_event()
-    {
-        if (e) hipEventDestroy(e);
-    }
-};
-} // namespace
-
 extern "C" int sift3d_compose_nodes(int device, const float m1[16], const float m2[16], const float mc[16], const sift3d_field *field1,
                                     const sift3d_field *field2, const sift3d_compose_params *pp, const sift3d_field *grid, float *w, uint32_t *status,
                                     double *res2, double kernel_ms[2], char *err, int64_t err_len)
@@ -62,43 +51,36 @@ extern "C" int sift3d_compose_nodes(int device, const float m1[16], const float 
     const size_t N1 = field1 ? (size_t)nodes_of(*field1) : 0, N2 = field2 ? (size_t)nodes_of(*field2) : 0;
     std::vector<float4> nodes1, nodes2; /* send_nodes packs into them: they live until the stream is synchronised */
     device_call dc(err, err_len);
-    extra_event mid;
+    stage_events<3> ev; /* around the composition and, with res2, the residual after it */
     float4 *d_f1 = nullptr, *d_f2 = nullptr, *d_w4 = nullptr;
     float *d_w;
     unsigned *d_status;
     double *d_res = nullptr;
-    DEVCHK(dc, dc.open(device));
+    DEVCHK(dc, dc.open(device, false));
+    DEVCHK(dc, ev.create());
     if ((field1 && dc.alloc(&d_f1, N1) != hipSuccess) || (field2 && dc.alloc(&d_f2, N2) != hipSuccess) || dc.alloc(&d_w, 3 * N) != hipSuccess ||
-        dc.alloc(&d_status, N) != hipSuccess || (res2 && (dc.alloc(&d_w4, N) != hipSuccess || dc.alloc(&d_res, NC) != hipSuccess))) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu bytes on device %d", sizeof(float4) * (N1 + N2),
-                         16 * N + (res2 ? 16 * N + 8 * NC : 0), device);
-    }
-    if (res2) DEVCHK(dc, hipEventCreate(&mid.e));
+        dc.alloc(&d_status, N) != hipSuccess || (res2 && (dc.alloc(&d_w4, N) != hipSuccess || dc.alloc(&d_res, NC) != hipSuccess)))
+        return dc.no_memory();
     if (field1) DEVCHK(dc, send_nodes(dc, *field1, nodes1, d_f1));
     if (field2) DEVCHK(dc, send_nodes(dc, *field2, nodes2, d_f2));
     const float *o1 = field1 ? field1->origin : nullptr, *o2 = field2 ? field2->origin : nullptr;
     const int64_t *n1 = field1 ? field1->n : nullptr, *n2 = field2 ? field2->n : nullptr;
     const float h1 = field1 ? field1->spacing : 0.0f, h2 = field2 ? field2->spacing : 0.0f;
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, ev.record(0, dc.s));
     DEVCHK(dc, sift3d_launch_field_compose(dc.s, d_f1, o1, h1, n1, d_f2, o2, h2, n2, grid->origin, grid->spacing, grid->n, P1, P2, Pc, d_w, d_w4,
                                            d_status));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, ev.record(1, dc.s));
     if (res2) {
         DEVCHK(dc, sift3d_launch_compose_residual(dc.s, d_f1, o1, h1, n1, d_f2, o2, h2, n2, grid->origin, grid->spacing, grid->n, P1, P2, Pc, d_w4,
                                                   d_res));
-        DEVCHK(dc, hipEventRecord(mid.e, dc.s));
+        DEVCHK(dc, ev.record(2, dc.s));
         DEVCHK(dc, dc.download(res2, d_res, NC));
     }
     DEVCHK(dc, dc.download(w, d_w, 3 * N));
     DEVCHK(dc, dc.download((unsigned *)status, d_status, N));
     DEVCHK(dc, dc.sync());
-    DEVCHK(dc, dc.elapsed_ms(kernel_ms));
-    if (res2 && kernel_ms) {
-        float t = 0;
-        DEVCHK(dc, hipEventElapsedTime(&t, dc.e1, mid.e));
-        kernel_ms[1] = (double)t;
-    }
+    if (kernel_ms) DEVCHK(dc, ev.elapsed(0, 1, &kernel_ms[0]));
+    if (res2 && kernel_ms) DEVCHK(dc, ev.elapsed(1, 2, &kernel_ms[1]));
     return SIFT3D_OK;
 }
 

@@ -9,7 +9,6 @@
 
 #include "device_call.h"
 
-hipError_t sift3d_launch_edt_labels(hipStream_t s, const float *labels, int64_t n, unsigned short *lab, unsigned long long *valid);
 hipError_t sift3d_launch_edt_surface(hipStream_t s, const unsigned short *lab_a, const unsigned long long *valid_a, const unsigned short *lab_b,
                                      const unsigned long long *valid_b, int64_t nx, int64_t ny, int64_t nz, unsigned l, unsigned char *sites_a,
                                      unsigned char *sites_b, unsigned *counts);
@@ -38,47 +37,28 @@ static int check_map(int64_t nx, int64_t ny, int64_t nz, const uint32_t spacing_
 }
 
 /* the four events around the three passes of one transform */
-struct edt_events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    edt_events() = default;
-    edt_events(const edt_events &) = delete;
-    void operator=(const edt_events &) = delete;
-    ~edt_events()
-    {
-        for (hipEvent_t x : e)
-            if (x) hipEventDestroy(x);
-    }
-    hipError_t create()
-    {
-        hipError_t rc = hipSuccess;
-        for (int i = 0; i < 4 && rc == hipSuccess; i++) rc = hipEventCreate(&e[i]);
-        return rc;
-    }
-    /* total, x, y, z into ms[0 .. 3]; the stream has been synchronised */
-    hipError_t elapsed(double ms[4]) const
-    {
-        const int from[4] = {0, 0, 1, 2}, to[4] = {3, 1, 2, 3};
-        for (int i = 0; i < 4; i++) {
-            float t = 0;
-            const hipError_t rc = hipEventElapsedTime(&t, e[from[i]], e[to[i]]);
-            if (rc != hipSuccess) return rc;
-            ms[i] = (double)t;
-        }
-        return hipSuccess;
-    }
-};
+typedef stage_events<4> edt_events;
+
+/* total, x, y, z into ms[0 .. 3]; the stream has been synchronised */
+static hipError_t edt_elapsed(const edt_events &ev, double ms[4])
+{
+    const int from[4] = {0, 0, 1, 2}, to[4] = {3, 1, 2, 3};
+    hipError_t rc = hipSuccess;
+    for (int i = 0; i < 4 && rc == hipSuccess; i++) rc = ev.elapsed(from[i], to[i], &ms[i]);
+    return rc;
+}
 
 /* sites to d2 through the uint16 plane dx and the 64-bit plane tmp */
 static hipError_t run_map(hipStream_t s, const unsigned char *sites, int64_t nx, int64_t ny, int64_t nz, const uint32_t sp[3], unsigned short *dx,
                           unsigned long long *tmp, unsigned long long *d2, const edt_events &ev)
 {
-    hipError_t rc = hipEventRecord(ev.e[0], s);
+    hipError_t rc = ev.record(0, s);
     if (rc == hipSuccess) rc = sift3d_launch_edt_x(s, sites, nx, ny, nz, dx);
-    if (rc == hipSuccess) rc = hipEventRecord(ev.e[1], s);
+    if (rc == hipSuccess) rc = ev.record(1, s);
     if (rc == hipSuccess) rc = sift3d_launch_edt_line(s, 1, dx, tmp, nx, ny, nz, sp[0], sp[1]);
-    if (rc == hipSuccess) rc = hipEventRecord(ev.e[2], s);
+    if (rc == hipSuccess) rc = ev.record(2, s);
     if (rc == hipSuccess) rc = sift3d_launch_edt_line(s, 2, tmp, d2, nx, ny, nz, sp[0], sp[2]);
-    if (rc == hipSuccess) rc = hipEventRecord(ev.e[3], s);
+    if (rc == hipSuccess) rc = ev.record(3, s);
     return rc;
 }
 
@@ -98,15 +78,13 @@ extern "C" int sift3d_distance_map(int device, const uint8_t *sites, int64_t nx,
     unsigned long long *d_tmp, *d_d2;
     DEVCHK(dc, dc.open(device, false));
     DEVCHK(dc, ev.create());
-    if (dc.alloc(&d_sites, nv) != hipSuccess || dc.alloc(&d_dx, nv) != hipSuccess || dc.alloc(&d_tmp, nv) != hipSuccess || dc.alloc(&d_d2, nv) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", 19 * nv, device);
-    }
+    if (dc.alloc(&d_sites, nv) != hipSuccess || dc.alloc(&d_dx, nv) != hipSuccess || dc.alloc(&d_tmp, nv) != hipSuccess || dc.alloc(&d_d2, nv) != hipSuccess)
+        return dc.no_memory();
     DEVCHK(dc, dc.to_device(d_sites, (const unsigned char *)sites, nv));
     DEVCHK(dc, run_map(dc.s, d_sites, nx, ny, nz, spacing_um, d_dx, d_tmp, d_d2, ev));
     DEVCHK(dc, dc.download((unsigned long long *)d2, d_d2, nv));
     DEVCHK(dc, dc.sync());
-    if (kernel_ms) DEVCHK(dc, ev.elapsed(kernel_ms));
+    if (kernel_ms) DEVCHK(dc, edt_elapsed(ev, kernel_ms));
     return SIFT3D_OK;
 }
 
@@ -123,23 +101,19 @@ extern "C" int sift3d_surface_distances(const float *a, const float *b, int64_t 
     if (!a || !b || !records || !n_records) return call_fail(err, err_len, SIFT3D_ERR_ARG, "null pointer");
     const int bad = check_map(nx, ny, nz, spacing_um, err, err_len);
     if (bad != SIFT3D_OK) return bad;
-    if (p.first_label < 0 || p.first_label > 65535) return call_fail(err, err_len, SIFT3D_ERR_ARG, "first_label = %d: 0 .. 65535", (int)p.first_label);
+    if (p.first_label < 0 || p.first_label >= SIFT3D_LABEL_COUNT) return call_fail(err, err_len, SIFT3D_ERR_ARG, "first_label = %d: 0 .. 65535", (int)p.first_label);
     if (p.max_labels < 1) return call_fail(err, err_len, SIFT3D_ERR_ARG, "max_labels = %d: at least 1", (int)p.max_labels);
     const int64_t n = nx * ny * nz;
     const float *vols[2] = {a, b};
-    std::vector<int64_t> counts(3 * 65536);
-    int64_t *ca = counts.data(), *cb = ca + 65536;
-    if (sift3d_label_overlap(a, b, n, ca, cb, cb + 65536) < 0) { /* it has checked both volumes: only a refusal looks for the voxel */
-        for (int v = 0; v < 2; v++) {
-            const int64_t at = sift3d_fuse_check_labels(vols[v], n);
-            if (at >= 0)
-                return call_fail(err, err_len, SIFT3D_ERR_ARG, "volume %c: the label %g at voxel %lld is neither non-finite nor an integer 0 .. 65535", "ab"[v],
-                                 (double)vols[v][at], (long long)at);
-        }
+    std::vector<int64_t> counts(3 * SIFT3D_LABEL_COUNT);
+    int64_t *ca = counts.data(), *cb = ca + SIFT3D_LABEL_COUNT;
+    if (sift3d_label_overlap(a, b, n, ca, cb, cb + SIFT3D_LABEL_COUNT) < 0) { /* it has checked both volumes: only a refusal looks for the voxel */
+        if (check_labels("volume a: ", a, n, err, err_len) != SIFT3D_OK || check_labels("volume b: ", b, n, err, err_len) != SIFT3D_OK)
+            return SIFT3D_ERR_ARG;
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "the label volumes cannot be counted");
     }
     std::vector<int32_t> labels;
-    for (int32_t l = p.first_label; l < 65536; l++)
+    for (int32_t l = p.first_label; l < SIFT3D_LABEL_COUNT; l++)
         if (ca[l] > 0 || cb[l] > 0) labels.push_back(l);
     if (labels.size() > (size_t)p.max_labels)
         return call_fail(err, err_len, SIFT3D_ERR_ARG, "%zu labels from %d on occur in the volumes: more than max_labels = %d", labels.size(), (int)p.first_label,
@@ -160,13 +134,11 @@ extern "C" int sift3d_surface_distances(const float *a, const float *b, int64_t 
     if (dc.alloc(&d_f, nv) != hipSuccess || dc.alloc(&d_lab[0], nv) != hipSuccess || dc.alloc(&d_lab[1], nv) != hipSuccess ||
         dc.alloc(&d_valid[0], nw) != hipSuccess || dc.alloc(&d_valid[1], nw) != hipSuccess || dc.alloc(&d_sites[0], nv) != hipSuccess ||
         dc.alloc(&d_sites[1], nv) != hipSuccess || dc.alloc(&d_dx, nv) != hipSuccess || dc.alloc(&d_tmp, nv) != hipSuccess || dc.alloc(&d_d2, nv) != hipSuccess ||
-        dc.alloc(&d_cnt, 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", 29 * nv, p.device);
-    }
+        dc.alloc(&d_cnt, 4) != hipSuccess)
+        return dc.no_memory();
     for (int v = 0; v < 2; v++) {
         DEVCHK(dc, dc.to_device(d_f, vols[v], nv));
-        DEVCHK(dc, sift3d_launch_edt_labels(dc.s, d_f, n, d_lab[v], d_valid[v]));
+        DEVCHK(dc, sift3d_launch_label_plane(dc.s, d_f, n, d_lab[v], d_valid[v]));
     }
     std::vector<unsigned long long> list_ab, list_ba;
     double total_ms = 0.0;
@@ -195,11 +167,11 @@ extern "C" int sift3d_surface_distances(const float *a, const float *b, int64_t 
         DEVCHK(dc, sift3d_launch_edt_gather(dc.s, d_sites[1], d_d2, n, cnt[1], d_cnt + 3, d_tmp));
         DEVCHK(dc, dc.download(list_ba.data(), d_tmp, list_ba.size()));
         DEVCHK(dc, dc.sync());
-        double ms[4];
-        DEVCHK(dc, ev_ab.elapsed(ms));
-        total_ms += ms[0];
-        DEVCHK(dc, ev_ba.elapsed(ms));
-        total_ms += ms[0];
+        double ms_ab, ms_ba;
+        DEVCHK(dc, ev_ab.elapsed(0, 3, &ms_ab));
+        DEVCHK(dc, ev_ba.elapsed(0, 3, &ms_ba));
+        total_ms += ms_ab;
+        total_ms += ms_ba;
         sift3d_surface_stats((uint64_t *)list_ab.data(), cnt[0], (uint64_t *)list_ba.data(), cnt[1], &r);
     }
     *n_records = (int32_t)labels.size();

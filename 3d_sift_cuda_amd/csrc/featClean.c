@@ -53,7 +53,7 @@ static int64_t count_components(int device, const float *labels, int64_t nx, int
         }
         const int rc = sift3d_label_components(device, labels, nx, ny, nz, connectivity, NULL, rec, room, &n, NULL, err, (int64_t)err_len);
         if (rc == SIFT3D_OK) {
-            memset(per_label, 0, sizeof(int64_t) * 65536);
+            memset(per_label, 0, sizeof(int64_t) * SIFT3D_LABEL_COUNT);
             for (int64_t k = 0; k < n; k++) per_label[rec[k].label]++;
             free(rec);
             return n;
@@ -70,9 +70,9 @@ static int score(FILE *o, const char *title, int device, const float *labels, co
                  size_t err_len)
 {
     const int64_t n = (int64_t)truth->nx * truth->ny * truth->nz;
-    if (sift3d_label_overlap(labels, truth->data, n, counts, counts + 65536, counts + 2 * 65536) < 0) return -2;
+    if (sift3d_label_overlap(labels, truth->data, n, counts, counts + SIFT3D_LABEL_COUNT, counts + 2 * SIFT3D_LABEL_COUNT) < 0) return -2;
     fprintf(o, "# %s against the truth\n", title);
-    label_report_dice(o, counts, counts + 65536, counts + 2 * 65536);
+    label_report_dice(o, counts, counts + SIFT3D_LABEL_COUNT, counts + 2 * SIFT3D_LABEL_COUNT);
     if (spacing_um && label_report_distances(o, device, labels, truth->data, truth->nx, truth->ny, truth->nz, spacing_um, 1, err, err_len) != 0) return -1;
     return 0;
 }
@@ -165,7 +165,7 @@ int main(int argc, char **argv)
     }
     const int64_t n = (int64_t)in.nx * in.ny * in.nz;
     out = (float *)malloc(sizeof(float) * (size_t)n);
-    counts = (int64_t *)malloc(sizeof(int64_t) * 5 * 65536); /* three of the overlap, the components per label before and after */
+    counts = (int64_t *)malloc(sizeof(int64_t) * 5 * SIFT3D_LABEL_COUNT); /* three of the overlap, the components per label before and after */
     if (!out || !counts) {
         printf("Error: insufficient memory.\n");
         goto done;
@@ -175,7 +175,7 @@ int main(int argc, char **argv)
         printf("Error: could not clean the labels: %s: %s\n", err, in_path);
         goto done;
     }
-    int64_t *before = counts + 3 * 65536, *after = counts + 4 * 65536;
+    int64_t *before = counts + 3 * SIFT3D_LABEL_COUNT, *after = counts + 4 * SIFT3D_LABEL_COUNT;
     const int64_t n_before = count_components(p.device, in.data, in.nx, in.ny, in.nz, p.connectivity, before, err, sizeof err);
     const int64_t n_after = n_before < 0 ? -1 : count_components(p.device, out, in.nx, in.ny, in.nz, p.connectivity, after, err, sizeof err);
     if (n_before < 0 || n_after < 0) {
@@ -195,7 +195,7 @@ int main(int argc, char **argv)
     sift3d_clean_report_text(&rep, text, sizeof text);
     fputs(text, o);
     fprintf(o, "# label components_before components_after\n");
-    for (int l = 0; l < 65536; l++)
+    for (int l = 0; l < SIFT3D_LABEL_COUNT; l++)
         if (before[l] > 0 || after[l] > 0) fprintf(o, "%d\t%lld\t%lld\n", l, (long long)before[l], (long long)after[l]);
     fprintf(o, "# components %lld before %lld after\n", (long long)n_before, (long long)n_after);
     if (truth_path) {

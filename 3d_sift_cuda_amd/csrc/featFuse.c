@@ -90,10 +90,10 @@ static int write_report(const char *out_path, int K, const sift3d_fuse_params *p
                         size_t err_len)
 {
     const int64_t n = (int64_t)target->nx * target->ny * target->nz;
-    int64_t *ca = (int64_t *)malloc(sizeof(int64_t) * 3 * 65536);
+    int64_t *ca = (int64_t *)malloc(sizeof(int64_t) * 3 * SIFT3D_LABEL_COUNT);
     char *path = (char *)malloc(strlen(out_path) + 16);
     if (!ca || !path) return -1;
-    int64_t *cb = ca + 65536, *cboth = cb + 65536;
+    int64_t *cb = ca + SIFT3D_LABEL_COUNT, *cboth = cb + SIFT3D_LABEL_COUNT;
     sprintf(path, "%s.fuse.txt", out_path);
     FILE *o = fopen(path, "w");
     free(path);
@@ -120,7 +120,7 @@ static int write_report(const char *out_path, int K, const sift3d_fuse_params *p
         return -2;
     }
     fprintf(o, "# label voxels\n");
-    for (int l = 0; l < 65536; l++)
+    for (int l = 0; l < SIFT3D_LABEL_COUNT; l++)
         if (ca[l] > 0) fprintf(o, "%d\t%lld\n", l, (long long)ca[l]);
     if (truth) label_report_dice(o, ca, cb, cboth);
     free(ca);

@@ -102,12 +102,12 @@ int main(int argc, char **argv)
         }
     }
     const int64_t n = (int64_t)a.nx * a.ny * a.nz;
-    ca = (int64_t *)malloc(sizeof(int64_t) * 3 * 65536);
+    ca = (int64_t *)malloc(sizeof(int64_t) * 3 * SIFT3D_LABEL_COUNT);
     if (!ca) {
         printf("Error: insufficient memory.\n");
         goto done;
     }
-    if (sift3d_label_overlap(a.data, b.data, n, ca, ca + 65536, ca + 2 * 65536) < 0) {
+    if (sift3d_label_overlap(a.data, b.data, n, ca, ca + SIFT3D_LABEL_COUNT, ca + 2 * SIFT3D_LABEL_COUNT) < 0) {
         printf("Error: a voxel of an image is neither non-finite nor an integer 0 .. 65535: %s\n",
                sift3d_fuse_check_labels(a.data, n) >= 0 ? a_path : b_path);
         goto done;
@@ -117,7 +117,7 @@ int main(int argc, char **argv)
         printf("Error: could not write output file: %s\n", out_path);
         goto done;
     }
-    label_report_dice(o, ca, ca + 65536, ca + 2 * 65536);
+    label_report_dice(o, ca, ca + SIFT3D_LABEL_COUNT, ca + 2 * SIFT3D_LABEL_COUNT);
     if (measure && label_report_distances(o, device, a.data, b.data, a.nx, a.ny, a.nz, spacing_um, zero ? 0 : 1, err, sizeof err) != 0) {
         printf("Error: could not take the surface distances: %s\n", err);
         goto done;

@@ -83,14 +83,11 @@ int fit_on_grid(device_call &dc, const float *y, const float *v, int64_t n, cons
     DEVCHK(dc, dc.upload(&d_y, ys.data(), NS));
     DEVCHK(dc, dc.upload(&d_v, vs.data(), NS));
     DEVCHK(dc, dc.upload(&d_start, start.data(), start.size()));
-    if (dc.alloc(&d_out, (size_t)N * 3) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(dc.err, dc.err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", sizeof(float) * 3 * (size_t)N, dc.device);
-    }
+    if (dc.alloc(&d_out, (size_t)N * 3) != hipSuccess) return dc.no_memory();
     const double co[3] = {mn[0], mn[1], mn[2]};
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_field_fit(dc.s, d_y, d_v, d_start, co, edge, cn, g.origin, g.spacing, g.n, R * R, (double)lambda * 16777216.0, d_out));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download(disp, d_out, (size_t)N * 3));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));
@@ -255,17 +252,13 @@ extern "C" int sift3d_resample_field(int device, const float *src, int64_t nx, i
     float *d_src, *d_dst;
     float4 *d_nodes;
     DEVCHK(dc, dc.open(device));
-    if (dc.alloc(&d_src, n_in) != hipSuccess || dc.alloc(&d_dst, n_out) != hipSuccess || dc.alloc(&d_nodes, (size_t)N) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu + %zu bytes on device %d", sizeof(float) * n_in,
-                         sizeof(float) * n_out, sizeof(float4) * (size_t)N, device);
-    }
+    if (dc.alloc(&d_src, n_in) != hipSuccess || dc.alloc(&d_dst, n_out) != hipSuccess || dc.alloc(&d_nodes, (size_t)N) != hipSuccess) return dc.no_memory();
     DEVCHK(dc, dc.to_device(d_src, src, n_in));
     DEVCHK(dc, send_nodes(dc, *field, nodes, d_nodes));
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_field_warp(dc.s, d_src, nx, ny, nz, d_dst, ox, oy, oz, map, c, k, field->origin, field->spacing, field->n, d_nodes,
                                         interp, fill));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download(dst, d_dst, n_out));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));

@@ -1,7 +1,8 @@
 /*
  * field_call.h -- what the entry points that take or make a displacement field share (field_api.hip, blockmatch_api.hip,
  * invert_api.hip, resample_api.hip): the checks of a field and of the volume extents with their messages, the packing of a
- * field's nodes for the device, the residuals of a fit and the two-pass fit of DESIGN.md section 7e.  Internal: nothing
+ * field's nodes for the device, the residuals of a fit and the two-pass fit of DESIGN.md section 7e; and what the users of the
+ * quantised intensities share (blockmatch_api.hip, fuse_api.hip): a host volume to the device and through section 7f's quantiser.  Internal: nothing
  * here is part of the C-ABI.
  */
 #ifndef SIFT3D_FIELD_CALL_H
@@ -17,6 +18,7 @@
 hipError_t sift3d_launch_field_warp(hipStream_t s, const float *src, int64_t nx, int64_t ny, int64_t nz, float *dst, int64_t ox, int64_t oy,
                                     int64_t oz, const float *map, const float *c, const float *k, const float o[3], float h, const int64_t n[3],
                                     const float4 *nodes, int mode, float fill);
+hipError_t sift3d_launch_bm_quantize(hipStream_t s, const float *src, int64_t n, double lo, double hi, short *dst);
 
 inline int64_t nodes_of(const sift3d_field &f) { return f.n[0] * f.n[1] * f.n[2]; }
 
@@ -59,6 +61,13 @@ inline hipError_t send_nodes(device_call &dc, const sift3d_field &f, std::vector
 {
     pack_nodes(f, nodes);
     return dc.to_device(d_nodes, nodes.data(), nodes.size());
+}
+
+/* the host volume v (nv values) through d_v, quantised over [lo, hi] into d_q (quantize.h) */
+inline hipError_t send_quantised(device_call &dc, const float *v, size_t nv, float lo, float hi, float *d_v, short *d_q)
+{
+    const hipError_t e = dc.to_device(d_v, v, nv);
+    return e != hipSuccess ? e : sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_q);
 }
 
 /* e_i = |v_i - v(y_i)| in double */

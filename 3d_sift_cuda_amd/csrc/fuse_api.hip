@@ -11,7 +11,6 @@
 
 #include "field_call.h"
 
-hipError_t sift3d_launch_bm_quantize(hipStream_t s, const float *src, int64_t n, double lo, double hi, short *dst);
 hipError_t sift3d_launch_fuse_weight(hipStream_t s, const short *qt, const short *qw, int64_t nx, int64_t ny, int64_t nz, int b, int ncc, int generic,
                                      unsigned short *u);
 hipError_t sift3d_launch_fuse_label(hipStream_t s, const float *labels, int64_t n, int clear_u, unsigned short *lab, unsigned short *u);
@@ -52,13 +51,6 @@ static bool w_range_of(int metric, const float w_range[2], const float *w, size_
     return metric != SIFT3D_BLOCKMATCH_NCC || sift3d_blockmatch_range(w, (int64_t)nv, wlo, whi) != 0;
 }
 
-/* the host volume v (nv values) through d_v, quantised over [lo, hi] into d_q */
-static hipError_t send_quantised(device_call &dc, const float *v, size_t nv, float lo, float hi, float *d_v, short *d_q)
-{
-    const hipError_t e = dc.to_device(d_v, v, nv);
-    return e != hipSuccess ? e : sift3d_launch_bm_quantize(dc.s, d_v, (int64_t)nv, (double)lo, (double)hi, d_q);
-}
-
 extern "C" int sift3d_fuse_weights(int device, const float *t, const float *w, int64_t nx, int64_t ny, int64_t nz, int32_t b, int32_t metric,
                                    const float w_range[2], int32_t generic, uint16_t *u, double *kernel_ms, char *err, int64_t err_len)
 {
@@ -81,28 +73,25 @@ extern "C" int sift3d_fuse_weights(int device, const float *t, const float *w, i
     short *d_qt, *d_qw;
     unsigned short *d_u;
     DEVCHK(dc, dc.open(device));
-    if (dc.alloc(&d_v, nv) != hipSuccess || dc.alloc(&d_qt, nv) != hipSuccess || dc.alloc(&d_qw, nv) != hipSuccess || dc.alloc(&d_u, nv) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", 10 * nv, device);
-    }
+    if (dc.alloc(&d_v, nv) != hipSuccess || dc.alloc(&d_qt, nv) != hipSuccess || dc.alloc(&d_qw, nv) != hipSuccess || dc.alloc(&d_u, nv) != hipSuccess)
+        return dc.no_memory();
     DEVCHK(dc, send_quantised(dc, t, nv, lo, hi, d_v, d_qt));
     DEVCHK(dc, send_quantised(dc, w, nv, wlo, whi, d_v, d_qw));
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_fuse_weight(dc.s, d_qt, d_qw, nx, ny, nz, b, metric == SIFT3D_BLOCKMATCH_NCC, generic, d_u));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download((unsigned short *)u, d_u, nv));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));
     return SIFT3D_OK;
 }
 
-/* SIFT3D_OK, or SIFT3D_ERR_ARG and the atlas and first voxel whose label is neither non-finite nor an integer 0 .. 65535 */
-static int check_labels(int k, const float *labels, int64_t n, char *err, int64_t err_len)
+/* check_labels of atlas k's labels */
+static int check_atlas_labels(int k, const float *labels, int64_t n, char *err, int64_t err_len)
 {
-    const int64_t bad = sift3d_fuse_check_labels(labels, n);
-    if (bad < 0) return SIFT3D_OK;
-    return call_fail(err, err_len, SIFT3D_ERR_ARG, "atlas %d: the label %g at voxel %lld is neither non-finite nor an integer 0 .. 65535", k,
-                     (double)labels[bad], (long long)bad);
+    char who[32];
+    snprintf(who, sizeof who, "atlas %d: ", k);
+    return check_labels(who, labels, n, err, err_len);
 }
 
 extern "C" int sift3d_fuse_search(int device, const float *t, const float *w, const float *labels, int64_t nx, int64_t ny, int64_t nz, int32_t b, int32_t r,
@@ -117,7 +106,7 @@ extern "C" int sift3d_fuse_search(int device, const float *t, const float *w, co
     if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "%s", why);
     const size_t nv = (size_t)(nx * ny * nz);
     if (labels) {
-        const int rc = check_labels(0, labels, (int64_t)nv, err, err_len);
+        const int rc = check_atlas_labels(0, labels, (int64_t)nv, err, err_len);
         if (rc != SIFT3D_OK) return rc;
     }
     float lo, hi;
@@ -131,10 +120,8 @@ extern "C" int sift3d_fuse_search(int device, const float *t, const float *w, co
     unsigned short *d_u, *d_s;
     DEVCHK(dc, dc.open(device));
     if (dc.alloc(&d_v, nv) != hipSuccess || dc.alloc(&d_qt, nv) != hipSuccess || dc.alloc(&d_qw, nv) != hipSuccess || dc.alloc(&d_u, nv) != hipSuccess ||
-        dc.alloc(&d_s, nv) != hipSuccess || (labels && (dc.alloc(&d_l, nv) != hipSuccess || dc.alloc(&d_p, nv) != hipSuccess))) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", (labels ? 20 : 12) * nv, device);
-    }
+        dc.alloc(&d_s, nv) != hipSuccess || (labels && (dc.alloc(&d_l, nv) != hipSuccess || dc.alloc(&d_p, nv) != hipSuccess)))
+        return dc.no_memory();
     DEVCHK(dc, send_quantised(dc, t, nv, lo, hi, d_v, d_qt));
     if (ranged) {
         DEVCHK(dc, send_quantised(dc, w, nv, wlo, whi, d_v, d_qw));
@@ -143,9 +130,9 @@ extern "C" int sift3d_fuse_search(int device, const float *t, const float *w, co
         DEVCHK(dc, hipMemsetAsync(d_qw, 0xff, sizeof(short) * nv, dc.s));
     }
     if (labels) DEVCHK(dc, dc.to_device(d_l, labels, nv));
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_fuse_search(dc.s, d_qt, d_qw, d_l, nx, ny, nz, b, r, metric == SIFT3D_BLOCKMATCH_NCC, generic, d_u, d_s, d_p));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download((unsigned short *)u, d_u, nv));
     DEVCHK(dc, dc.download((unsigned short *)shift, d_s, nv));
     if (labels) DEVCHK(dc, dc.download(picked, d_p, nv));
@@ -164,7 +151,7 @@ extern "C" int sift3d_fuse_vote(int device, int32_t K, const uint16_t *const *u,
     if (!u || !labels || !words || n < 1 || n > (1ll << 38)) return call_fail(err, err_len, SIFT3D_ERR_ARG, "null pointer, or n outside 1 .. 2^38");
     for (int k = 0; k < K; k++) {
         if (!u[k] || !labels[k]) return call_fail(err, err_len, SIFT3D_ERR_ARG, "atlas %d: null pointer", k);
-        const int rc = check_labels(k, labels[k], n, err, err_len);
+        const int rc = check_atlas_labels(k, labels[k], n, err, err_len);
         if (rc != SIFT3D_OK) return rc;
         for (int64_t i = 0; i < n; i++)
             if (u[k][i] > SIFT3D_FUSE_U_ONE)
@@ -177,18 +164,16 @@ extern "C" int sift3d_fuse_vote(int device, int32_t K, const uint16_t *const *u,
     unsigned *d_words;
     DEVCHK(dc, dc.open(device));
     if (dc.alloc(&d_l, nv) != hipSuccess || dc.alloc(&d_u, nv * K) != hipSuccess || dc.alloc(&d_lab, nv * K) != hipSuccess ||
-        dc.alloc(&d_words, 2 * nv) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", nv * (12 + 4 * (size_t)K), device);
-    }
+        dc.alloc(&d_words, 2 * nv) != hipSuccess)
+        return dc.no_memory();
     for (int k = 0; k < K; k++) {
         DEVCHK(dc, dc.to_device(d_u + nv * k, (const unsigned short *)u[k], nv));
         DEVCHK(dc, dc.to_device(d_l, labels[k], nv));
         DEVCHK(dc, sift3d_launch_fuse_label(dc.s, d_l, n, 0, d_lab + nv * k, d_u + nv * k));
     }
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_fuse_vote(dc.s, d_u, d_lab, K, n, power, d_words));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download((unsigned *)words, d_words, 2 * nv));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));
@@ -229,7 +214,7 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
         if (!why && a.nx * a.ny > (1ll << 38) / a.nz) why = "volume larger than 2^38 voxels";
         if (!why && a.field) why = check_field(*a.field);
         if (why) return call_fail(err, err_len, SIFT3D_ERR_ARG, "atlas %d: %s", k, why);
-        const int rc = check_labels(k, a.labels, a.nx * a.ny * a.nz, err, err_len);
+        const int rc = check_atlas_labels(k, a.labels, a.nx * a.ny * a.nz, err, err_len);
         if (rc != SIFT3D_OK) return rc;
         nm_max = std::max(nm_max, (size_t)(a.nx * a.ny * a.nz));
         if (a.field) nodes_max = std::max(nodes_max, (size_t)nodes_of(*a.field));
@@ -250,18 +235,12 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
     float4 *d_nodes;
     std::vector<unsigned short> hs; /* one atlas' shift plane, for the search report */
     DEVCHK(dc, dc.open(device));
-    if (search > 0 && (dc.alloc(&d_pick, nv) != hipSuccess || dc.alloc(&d_shift, nv) != hipSuccess)) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", 6 * nv, device);
-    }
+    if (search > 0 && (dc.alloc(&d_pick, nv) != hipSuccess || dc.alloc(&d_shift, nv) != hipSuccess)) return dc.no_memory();
     if (search > 0) hs.resize(nv);
     if (dc.alloc(&d_w, nv) != hipSuccess || dc.alloc(&d_m, nm_max) != hipSuccess || dc.alloc(&d_qt, nv) != hipSuccess || dc.alloc(&d_qw, nv) != hipSuccess ||
         dc.alloc(&d_u, nv * K) != hipSuccess || dc.alloc(&d_lab, nv * K) != hipSuccess || dc.alloc(&d_words, 2 * nv) != hipSuccess ||
-        dc.alloc(&d_nodes, nodes_max) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu + %zu bytes on device %d", nv * (16 + 4 * (size_t)K), 4 * nm_max,
-                         16 * nodes_max, device);
-    }
+        dc.alloc(&d_nodes, nodes_max) != hipSuccess)
+        return dc.no_memory();
     /* T is quantised once; its float copy's buffer then holds the warped volumes */
     DEVCHK(dc, send_quantised(dc, target, nv, rp.lo, rp.hi, d_w, d_qt));
     std::vector<float4> nodes; /* send_nodes packs into it: it lives until the stream is synchronised */
@@ -289,22 +268,22 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
         const bool weigh = p.power > 0 && !r.empty_range;
         double ms = 0.0;
         if (weigh) {
-            DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+            DEVCHK(dc, dc.mark(0));
             DEVCHK(dc, warp(a.image, SIFT3D_INTERP_LINEAR));
-            DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+            DEVCHK(dc, dc.mark(1));
             DEVCHK(dc, dc.sync());
             DEVCHK(dc, dc.elapsed_ms(&ms));
             r.warp_ms += ms;
-            DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+            DEVCHK(dc, dc.mark(0));
             DEVCHK(dc, sift3d_launch_bm_quantize(dc.s, d_w, n, (double)wlo, (double)whi, d_qw));
             if (search == 0) DEVCHK(dc, sift3d_launch_fuse_weight(dc.s, d_qt, d_qw, nx, ny, nz, p.block, ncc, 0, d_u + nv * k));
-            DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+            DEVCHK(dc, dc.mark(1));
             DEVCHK(dc, dc.sync());
             DEVCHK(dc, dc.elapsed_ms(&r.weight_ms));
         }
-        DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+        DEVCHK(dc, dc.mark(0));
         DEVCHK(dc, warp(a.labels, p.label_interp));
-        DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+        DEVCHK(dc, dc.mark(1));
         if (search == 0 || !weigh) DEVCHK(dc, sift3d_launch_fuse_label(dc.s, d_w, n, !weigh, d_lab + nv * k, d_u + nv * k));
         DEVCHK(dc, dc.sync());
         DEVCHK(dc, dc.elapsed_ms(&ms));
@@ -313,9 +292,9 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
             /* d_w holds the warped labels: the search picks among them, and the picked ones go the way the labels went.  An atlas
              * with an empty range has nothing to search by and has voted above as in section 7j: u = 0 and the shift 0. */
             sift3d_fuse_search_atlas_report &sr = sp.atlas[k];
-            DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+            DEVCHK(dc, dc.mark(0));
             DEVCHK(dc, sift3d_launch_fuse_search(dc.s, d_qt, d_qw, d_w, nx, ny, nz, p.block, search, ncc, 0, d_u + nv * k, d_shift, d_pick));
-            DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+            DEVCHK(dc, dc.mark(1));
             DEVCHK(dc, sift3d_launch_fuse_label(dc.s, d_pick, n, 0, d_lab + nv * k, d_u + nv * k));
             DEVCHK(dc, dc.download(hs.data(), d_shift, nv));
             DEVCHK(dc, dc.sync());
@@ -324,9 +303,9 @@ static int fuse_stage(int device, const float *target, int64_t nx, int64_t ny, i
             sift3d_fuse_shift_stats(search, hs.data(), n, &sr.moved, &sr.dist2_sum);
         }
     }
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_fuse_vote(dc.s, d_u, d_lab, K, n, p.power, d_words));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download((unsigned *)words, d_words, 2 * nv));
     std::vector<unsigned short> hu(nv * K), hl(nv * K);
     DEVCHK(dc, dc.download(hu.data(), d_u, nv * K));

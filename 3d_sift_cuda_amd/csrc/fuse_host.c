@@ -31,7 +31,7 @@ uint32_t sift3d_fuse_similarity(int32_t metric, int64_t n, int64_t sf, int64_t s
     return pc_u_ncc(n, sf, sff, sw, sww, sfw);
 }
 
-static int label_ok(float v) { return !isfinite(v) || (v >= 0.0f && v <= 65535.0f && v == (float)(int32_t)v); }
+static int label_ok(float v) { return !isfinite(v) || (v >= 0.0f && v <= (float)(SIFT3D_LABEL_COUNT - 1) && v == (float)(int32_t)v); }
 
 int64_t sift3d_fuse_check_labels(const float *labels, int64_t n)
 {
@@ -44,9 +44,9 @@ int64_t sift3d_label_overlap(const float *a, const float *b, int64_t n, int64_t 
 {
     if (!a || !b || !count_a || !count_b || !count_both || n < 0) return -1;
     if (sift3d_fuse_check_labels(a, n) >= 0 || sift3d_fuse_check_labels(b, n) >= 0) return -1;
-    memset(count_a, 0, sizeof(int64_t) * 65536);
-    memset(count_b, 0, sizeof(int64_t) * 65536);
-    memset(count_both, 0, sizeof(int64_t) * 65536);
+    memset(count_a, 0, sizeof(int64_t) * SIFT3D_LABEL_COUNT);
+    memset(count_b, 0, sizeof(int64_t) * SIFT3D_LABEL_COUNT);
+    memset(count_both, 0, sizeof(int64_t) * SIFT3D_LABEL_COUNT);
     for (int64_t i = 0; i < n; i++) {
         const int fa = isfinite(a[i]), fb = isfinite(b[i]);
         if (fa) count_a[(int32_t)a[i]]++;
@@ -54,7 +54,7 @@ int64_t sift3d_label_overlap(const float *a, const float *b, int64_t n, int64_t 
         if (fa && fb && a[i] == b[i]) count_both[(int32_t)a[i]]++;
     }
     int64_t present = 0;
-    for (int l = 0; l < 65536; l++) present += count_a[l] > 0 || count_b[l] > 0;
+    for (int l = 0; l < SIFT3D_LABEL_COUNT; l++) present += count_a[l] > 0 || count_b[l] > 0;
     return present;
 }
 

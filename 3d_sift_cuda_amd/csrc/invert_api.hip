@@ -56,16 +56,14 @@ extern "C" int sift3d_invert_nodes(int device, const float m[16], const float m_
     double *d_res;
     DEVCHK(dc, dc.open(device));
     if ((forward && dc.alloc(&d_nodes, NF) != hipSuccess) || dc.alloc(&d_u, 3 * N) != hipSuccess || dc.alloc(&d_status, N) != hipSuccess ||
-        dc.alloc(&d_res, N) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu bytes on device %d", sizeof(float4) * NF, 24 * N, device);
-    }
+        dc.alloc(&d_res, N) != hipSuccess)
+        return dc.no_memory();
     if (forward) DEVCHK(dc, send_nodes(dc, *forward, nodes, d_nodes));
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_field_invert(dc.s, d_nodes, forward ? forward->origin : nullptr, forward ? forward->spacing : 0.0f,
                                           forward ? forward->n : nullptr, grid->origin, grid->spacing, grid->n, P, Q, A, (double)p.tol * (double)p.tol,
                                           p.max_iter, d_u, d_status, d_res));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download(u, d_u, 3 * N));
     DEVCHK(dc, dc.download((unsigned *)status, d_status, N));
     if (res2) DEVCHK(dc, dc.download(res2, d_res, N));
@@ -136,16 +134,12 @@ extern "C" int sift3d_jacobian_map(int device, int64_t ox, int64_t oy, int64_t o
     float *d_dst;
     float4 *d_nodes = nullptr;
     DEVCHK(dc, dc.open(device));
-    if (dc.alloc(&d_dst, n_out) != hipSuccess || (field && dc.alloc(&d_nodes, NF) != hipSuccess)) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu bytes on device %d", sizeof(float) * n_out,
-                         sizeof(float4) * NF, device);
-    }
+    if (dc.alloc(&d_dst, n_out) != hipSuccess || (field && dc.alloc(&d_nodes, NF) != hipSuccess)) return dc.no_memory();
     if (field) DEVCHK(dc, send_nodes(dc, *field, nodes, d_nodes));
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_jacobian_map(dc.s, d_dst, ox, oy, oz, map, c, k, field ? field->origin : nullptr, field ? field->spacing : 0.0f,
                                           field ? field->n : nullptr, d_nodes, factor, form < 0 ? JACOBIAN_DEFAULT_FORM : form));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download(out, d_dst, n_out));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));

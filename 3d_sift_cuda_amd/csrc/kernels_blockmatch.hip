@@ -19,9 +19,9 @@
  */
 #include "sift3d_internal.h"
 #include "patch_cost.h"
+#include "quantize.h"
 
 #define BM_THREADS 256
-#define BM_QMAX 1023
 #define BM_LDS_MAX 65536
 #define BM_NONE 0xffffffffu
 
@@ -37,13 +37,7 @@ __global__ __launch_bounds__(256) void bm_quantize_kernel(const float *__restric
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float v = src[i];
-    short q = -1;
-    if (isfinite(v)) {
-        const double t = (((double)v - lo) / (hi - lo)) * (double)BM_QMAX;
-        q = t <= 0.0 ? (short)0 : (t >= (double)BM_QMAX ? (short)BM_QMAX : (short)(int)rint(t));
-    }
-    dst[i] = q;
+    dst[i] = (short)quantize(src[i], lo, hi);
 }
 
 /* A workgroup's brick: the search's sizes, the F and W tiles' extents and strides, the brick's first node and its voxel, and the

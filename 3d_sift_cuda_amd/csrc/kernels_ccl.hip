@@ -3,8 +3,7 @@
  * tests/ccl_oracle.c restates them as a serial flood fill).  Everything is integers, minima and counts, so nothing depends on the
  * tiling, the launch order or the order the atomics arrive in.
  *
- * ccl_label_kernel      float labels to a uint16 plane and one validity bit per voxel (kernels_edt.hip's edt_label_kernel restated
- *                       with a grid loop; that file's kernels stay as they are).
+ * The label plane (uint16 labels and one validity bit per voxel) is kernels_label.hip's label_plane_kernel.
  * ccl_brick_kernel      one workgroup per brick of 32 x 8 x 4 voxels: a union-find in LDS over the brick's voxels.  Every voxel is
  *                       united with its backward neighbours of equal label inside the brick (3 under connectivity 6, 13 under 26)
  *                       by atomicMin on the LDS parent words; the tree is flattened and every voxel writes the global linear index
@@ -30,6 +29,7 @@
 #include <algorithm>
 
 #include "sift3d_internal.h"
+#include "label_plane.h"
 
 #define CCL_THREADS 256
 #define CCL_BX 32
@@ -38,21 +38,6 @@
 #define CCL_BRICK (CCL_BX * CCL_BY * CCL_BZ)
 #define CCL_MAX_BLOCKS 2048 /* of every launch here: the kernels go round a grid loop beyond it */
 #define CCL_NONE 0xffffffffu
-
-__global__ __launch_bounds__(CCL_THREADS) void ccl_label_kernel(const float *__restrict__ labels, long long n, unsigned short *__restrict__ lab,
-                                                                unsigned long long *__restrict__ valid)
-{
-    for (long long base = (long long)blockIdx.x * CCL_THREADS; base < n; base += (long long)gridDim.x * CCL_THREADS) {
-        const long long i = base + threadIdx.x;
-        const float v = i < n ? labels[i] : 0.0f;
-        const bool ok = i < n && isfinite(v);
-        const unsigned long long m = __ballot(ok); /* every lane of the wave is here: the loop's bound is the workgroup's */
-        if (i < n) lab[i] = ok ? (unsigned short)(int)v : (unsigned short)0;
-        if ((threadIdx.x & 63) == 0 && i < n) valid[i >> 6] = m;
-    }
-}
-
-__device__ __forceinline__ bool ccl_valid(const unsigned long long *valid, long long i) { return ((valid[i >> 6] >> (i & 63)) & 1ull) != 0; }
 
 /* the c-th of the 13 backward neighbours (those of a smaller linear index); under connectivity 6 only c = 4, 10 and 12 count */
 template <int CONN> __device__ __forceinline__ bool ccl_backward(int c, int &dx, int &dy, int &dz)
@@ -118,7 +103,7 @@ __global__ __launch_bounds__(CCL_THREADS) void ccl_brick_kernel(const unsigned s
             int v = -1; /* outside the volume or unlabelled: joined with nothing */
             if (x < nx && y < ny && z < nz) {
                 const long long i = ((long long)z * ny + y) * nx + x;
-                if (ccl_valid(valid, i)) v = lab[i];
+                if (label_valid(valid, i)) v = lab[i];
             }
             lb[l] = v;
             par[l] = (unsigned)l;
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(CCL_THREADS) void ccl_merge_kernel(const unsigned s
         const int fx = x % CCL_BX, fy = y % CCL_BY, fz = z % CCL_BZ;
         /* a backward neighbour lies in another brick only from a low face, or, under 26, diagonally across a high x or y face */
         if (!(fx == 0 || fy == 0 || fz == 0 || (CONN == 26 && (fx == CCL_BX - 1 || fy == CCL_BY - 1)))) continue;
-        if (!ccl_valid(valid, i)) continue;
+        if (!label_valid(valid, i)) continue;
         const unsigned short v = lab[i];
         for (int c = 0; c < 13; c++) {
             int dx, dy, dz;
@@ -204,7 +189,7 @@ __global__ __launch_bounds__(CCL_THREADS) void ccl_merge_kernel(const unsigned s
             if (ax < 0 || ax >= nx || ay < 0 || az < 0 || ay >= ny) continue;
             if (ax / CCL_BX == x / CCL_BX && ay / CCL_BY == y / CCL_BY && az / CCL_BZ == z / CCL_BZ) continue; /* the brick pass has done it */
             const long long j = ((long long)az * ny + ay) * nx + ax;
-            if (ccl_valid(valid, j) && lab[j] == v) ccl_unite(parent, (unsigned)i, (unsigned)j);
+            if (label_valid(valid, j) && lab[j] == v) ccl_unite(parent, (unsigned)i, (unsigned)j);
         }
     }
 }
@@ -412,12 +397,6 @@ __global__ __launch_bounds__(CCL_THREADS) void ccl_apply_kernel(const unsigned *
 static unsigned ccl_blocks(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + CCL_THREADS - 1) / CCL_THREADS, CCL_MAX_BLOCKS)); }
 
 /* the callers have checked the extents (1 .. 4096 each, at most 2^30 voxels) and the connectivity (6 or 26) */
-hipError_t sift3d_launch_ccl_labels(hipStream_t s, const float *labels, int64_t n, unsigned short *lab, unsigned long long *valid)
-{
-    hipLaunchKernelGGL(ccl_label_kernel, dim3(ccl_blocks(n)), dim3(CCL_THREADS), 0, s, labels, (long long)n, lab, valid);
-    return hipGetLastError();
-}
-
 hipError_t sift3d_launch_ccl_bricks(hipStream_t s, int conn, const unsigned short *lab, const unsigned long long *valid, int64_t nx, int64_t ny, int64_t nz,
                                     unsigned *parent)
 {

@@ -3,9 +3,8 @@
  * tests/edt_oracle.c restates them as a serial brute force).  Everything is integer arithmetic and every result a minimum, a
  * count or a flag, so nothing depends on the tiling, the pass order or the wave layout.
  *
- * edt_label_kernel      float labels to a uint16 plane and one validity bit per voxel (a wave's ballot is the 64-bit word of its
- *                       64 voxels); once per volume.
- * edt_surface_kernel    one launch per label: the surface flags of the label in both volumes and their two counts.
+ * edt_surface_kernel    one launch per label: the surface flags of the label in both volumes and their two counts, from the two
+ *                       label planes (kernels_label.hip's label_plane_kernel, once per volume).
  * edt_x_kernel          a wave per row: the row's site flags become a bit mask in LDS (one ballot per 64 voxels), every word
  *                       learns the nearest site in the words before and after it, and a voxel finds its nearest site to either
  *                       side with one count-leading-zeros and one find-first-set.  uint16 |dx|, EDT_DX_NONE for a row without a
@@ -22,6 +21,7 @@
 #include <algorithm>
 
 #include "sift3d_internal.h"
+#include "label_plane.h"
 
 #define EDT_THREADS 256
 #define EDT_TX 64    /* lanes along x of a line tile: one wave */
@@ -34,20 +34,9 @@
 #define EDT_DX_NONE 0xffffu
 #define EDT_MAX_WORDS 64 /* 4096 voxels of a row / 64 */
 
-__global__ __launch_bounds__(EDT_THREADS) void edt_label_kernel(const float *__restrict__ labels, long long n, unsigned short *__restrict__ lab,
-                                                                unsigned long long *__restrict__ valid)
-{
-    const long long i = (long long)blockIdx.x * EDT_THREADS + threadIdx.x;
-    const float v = i < n ? labels[i] : 0.0f;
-    const bool ok = i < n && isfinite(v);
-    const unsigned long long m = __ballot(ok); /* every lane of the wave is here: no return above */
-    if (i < n) lab[i] = ok ? (unsigned short)(int)v : (unsigned short)0;
-    if ((threadIdx.x & 63) == 0 && i < n) valid[i >> 6] = m;
-}
-
 __device__ __forceinline__ bool edt_carries(const unsigned short *lab, const unsigned long long *valid, long long i, unsigned l)
 {
-    return lab[i] == l && ((valid[i >> 6] >> (i & 63)) & 1ull) != 0;
+    return lab[i] == l && label_valid(valid, i);
 }
 
 /* counts[0], counts[1]: the surface voxels of l in A and in B (the caller has zeroed them) */
@@ -187,12 +176,6 @@ __global__ __launch_bounds__(EDT_THREADS) void edt_gather_kernel(const unsigned 
 static unsigned edt_blocks(long long n) { return (unsigned)((n + EDT_THREADS - 1) / EDT_THREADS); }
 
 /* the callers have checked the extents (1 .. 4096 each, at most 2^30 voxels) and the spacings (1 .. 65535) */
-hipError_t sift3d_launch_edt_labels(hipStream_t s, const float *labels, int64_t n, unsigned short *lab, unsigned long long *valid)
-{
-    hipLaunchKernelGGL(edt_label_kernel, dim3(edt_blocks(n)), dim3(EDT_THREADS), 0, s, labels, (long long)n, lab, valid);
-    return hipGetLastError();
-}
-
 hipError_t sift3d_launch_edt_surface(hipStream_t s, const unsigned short *lab_a, const unsigned long long *valid_a, const unsigned short *lab_b,
                                      const unsigned long long *valid_b, int64_t nx, int64_t ny, int64_t nz, unsigned l, unsigned char *sites_a,
                                      unsigned char *sites_b, unsigned *counts)

@@ -23,6 +23,7 @@
  * be an array under a run-time index (scratch), and re-reading global memory costs K^2 / 2 loads per voxel.
  */
 #include "sift3d_internal.h"
+#include "label_plane.h"
 #include "patch_sums.h"
 
 #define FUSE_THREADS 256
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_label_kernel(const float *_
     if (i >= n) return;
     const float v = labels[i];
     if (isfinite(v)) {
-        lab[i] = (unsigned short)(int)v;
+        lab[i] = (unsigned short)label_bits(v);
         if (clear_u) u[i] = 0;
     } else {
         lab[i] = 0;

@@ -4,8 +4,8 @@
  * the launch order or the order the atomics arrive in.
  *
  * joint_hist_kernel<LABELS>  reads the two float volumes once (8 bytes per voxel; with LABELS the label volume too, 12), quantises
- *                       in registers (kernels_blockmatch.hip's bm_quantize_kernel restated; that file stays as it is; no int16
- *                       plane is kept) and counts.  The index is flat.  A thread takes SIM_VPT consecutive voxels, as one float4 per
+ *                       in registers (quantize.h's map, which bm_quantize_kernel stores as an int16 plane; none is kept here)
+ *                       and counts.  The index is flat.  A thread takes SIM_VPT consecutive voxels, as one float4 per
  *                       volume where the stretch is whole and the pointers are 16-byte aligned; a workgroup of SIM_THREADS a stretch
  *                       of SIM_THREADS x SIM_VPT voxels; a launch has at most SIM_MAX_BLOCKS workgroups, which go round a grid loop.
  *                       Histogram: bins^2 uint32 in LDS (16 KiB at 64 bins), zeroed by the workgroup, filled with LDS atomic adds;
@@ -24,27 +24,18 @@
  * Result words (uint64): bins^2 cells, the six sums, then with LABELS SIM_MAX_LABELS x 6 label sums.
  */
 #include "sift3d_internal.h"
+#include "label_plane.h"
+#include "quantize.h"
 
 #define SIM_THREADS 256
 #define SIM_VPT 4            /* consecutive voxels per thread */
 #define SIM_MAX_BLOCKS 2048  /* of a launch: the kernel goes round a grid loop beyond it */
-#define SIM_QMAX 1023
 #define SIM_MAX_BINS 64
 #define SIM_MAX_LABELS 64
 #define SIM_SUMS 6
 #define SIM_FLUSH_SLICES 0
 #define SIM_FLUSH_ATOMICS 1
 #define SIM_SLICE_PARTS 16   /* sum_slices_kernel: the slices are summed in this many parts */
-
-__device__ __forceinline__ int sim_quantize(float v, double lo, double hi)
-{
-    int q = -1;
-    if (isfinite(v)) {
-        const double t = (((double)v - lo) / (hi - lo)) * (double)SIM_QMAX;
-        q = t <= 0.0 ? 0 : (t >= (double)SIM_QMAX ? SIM_QMAX : (int)rint(t));
-    }
-    return q;
-}
 
 __device__ __forceinline__ unsigned sim_wave_sum(unsigned v)
 {
@@ -103,7 +94,7 @@ __global__ __launch_bounds__(SIM_THREADS) void joint_hist_kernel(const float *__
         unsigned l[SIM_SUMS] = {0u, 0u, 0u, 0u, 0u, 0u};
 #pragma unroll
         for (int k = 0; k < SIM_VPT; k++) {
-            const int qa = sim_quantize(va[k], alo, ahi), qb = sim_quantize(vb[k], blo, bhi);
+            const int qa = quantize(va[k], alo, ahi), qb = quantize(vb[k], blo, bhi);
             if (k >= cnt || qa < 0 || qb < 0) continue;
             const unsigned ua = (unsigned)qa, ub = (unsigned)qb;
             s[0] += 1ull;
@@ -120,7 +111,7 @@ __global__ __launch_bounds__(SIM_THREADS) void joint_hist_kernel(const float *__
             }
             run++;
             if (LABELS && isfinite(vl[k])) {
-                const int sl = (int)(slot_of[(unsigned)(int)vl[k] & 0xffffu] & (SIM_MAX_LABELS - 1));
+                const int sl = (int)(slot_of[label_bits(vl[k])] & (SIM_MAX_LABELS - 1));
                 if (sl != slot) {
                     if (slot >= 0)
                         for (int j = 0; j < SIM_SUMS; j++)

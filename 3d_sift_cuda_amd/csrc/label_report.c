@@ -11,7 +11,7 @@ void label_report_dice(FILE *o, const int64_t *ca, const int64_t *cb, const int6
     double sum = 0;
     int64_t present = 0;
     fprintf(o, "# label fused truth both dice\n");
-    for (int l = 0; l < 65536; l++)
+    for (int l = 0; l < SIFT3D_LABEL_COUNT; l++)
         if (ca[l] > 0 || cb[l] > 0) {
             const double dice = (double)(2 * cboth[l]) / (double)(ca[l] + cb[l]);
             fprintf(o, "%d\t%lld\t%lld\t%lld\t%.6f\n", l, (long long)ca[l], (long long)cb[l], (long long)cboth[l], dice);

@@ -40,7 +40,7 @@ extern "C" int sift3d_knn64(int device, const int8_t *db, int64_t n_db, const in
     for (int it = 0; it < repeats; it++) { /* repeats > 1: timing (the first run is a warm-up; the last run's results are returned) */
         /* timing starts behind the warm-up run; with repeats == 1 there is none, and the one run's verdict on the bytes (a
          * device-to-host copy the host waits for) sits inside the interval: kernel_ms is then end to end, not kernel time */
-        if (it == 0 || (it == 1 && repeats > 1)) DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+        if (it == 0 || (it == 1 && repeats > 1)) DEVCHK(dc, dc.mark(0));
         stats[0] = stats[1] = stats[3] = stats[4] = ~0ull;
         stats[2] = stats[5] = 0;
         DEVCHK(dc, dc.to_device(d_stats, stats, 6));
@@ -56,7 +56,7 @@ extern "C" int sift3d_knn64(int device, const int8_t *db, int64_t n_db, const in
         }
         DEVCHK(dc, sift3d_launch_knn(dc.s, d_db, d_dbn, n_db, d_q, d_qn, n_q, k, const_norm, groups, segments, d_pd, d_pi, d_oi, d_od));
     }
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download(idx, d_oi, (size_t)n_q * k));
     DEVCHK(dc, dc.download(dist2, d_od, (size_t)n_q * k));
     DEVCHK(dc, dc.sync());

@@ -208,11 +208,11 @@ struct GuidedIndex {
         const long long gn[3] = {g.n[0], g.n[1], g.n[2]};
         const float lo = sift3d_scale_ivs().lo[0], hi = sift3d_scale_ivs().hi[0];
         DEVCHK(dc, hipSetDevice(dc.device));
-        DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+        DEVCHK(dc, dc.mark(0));
         DEVCHK(dc, sift3d_launch_guided(dc.s, d_frows, d_fnorm, d_fpos, d_finfo, d_fidx, n_f, d_cell, d_keys, g.o, g.edge, gn, dense, d_mrows, d_mpos,
                                         d_minfo, d_order, n_m, t->center0, t->center1, t->rot, t->scale, radius, lo, hi, o, o + nq, o + 2 * nq,
                                         o + 3 * nq, visited ? o + 4 * nq : nullptr));
-        DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+        DEVCHK(dc, dc.mark(1));
         DEVCHK(dc, dc.download(i1, o, nq));
         DEVCHK(dc, dc.download(d1, o + nq, nq));
         DEVCHK(dc, dc.download(i2, o + 2 * nq, nq));

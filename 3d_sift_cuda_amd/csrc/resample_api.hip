@@ -28,15 +28,11 @@ extern "C" int sift3d_resample_affine(int device, const float *src, int64_t nx, 
     device_call dc(err, err_len);
     float *d_src, *d_dst;
     DEVCHK(dc, dc.open(device));
-    if (dc.alloc(&d_src, n_in) != hipSuccess || dc.alloc(&d_dst, n_out) != hipSuccess) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu + %zu bytes on device %d", sizeof(float) * n_in, sizeof(float) * n_out,
-                         device);
-    }
+    if (dc.alloc(&d_src, n_in) != hipSuccess || dc.alloc(&d_dst, n_out) != hipSuccess) return dc.no_memory();
     DEVCHK(dc, dc.to_device(d_src, src, n_in));
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_resample(dc.s, d_src, nx, ny, nz, d_dst, ox, oy, oz, map, interp, fill));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download(dst, d_dst, n_out));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));

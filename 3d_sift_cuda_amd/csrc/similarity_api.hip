@@ -21,7 +21,7 @@ hipError_t sift3d_launch_joint_hist(hipStream_t s, const float *a, const float *
 static bool bins_ok(int32_t bins) { return bins == 8 || bins == 16 || bins == 32 || bins == 64; }
 
 /* The volumes to the device, one launch, the result's words back: res holds sift3d_similarity_words(bins, labels != NULL) words.
- * slot_of: 65536 bytes, the slot of every label present (labels given).  The arguments have been checked. */
+ * slot_of: SIFT3D_LABEL_COUNT bytes, the slot of every label present (labels given).  The arguments have been checked. */
 static int run_joint_hist(int device, const float *a, const float *b, const float *labels, const unsigned char *slot_of, int64_t n, const float ar[2],
                           const float br[2], int bins, int flush, unsigned long long *res, double *kernel_ms, char *err, int64_t err_len)
 {
@@ -34,22 +34,19 @@ static int run_joint_hist(int device, const float *a, const float *b, const floa
     unsigned *d_sh = nullptr;
     DEVCHK(dc, dc.open(device));
     bool ok = dc.alloc(&d_a, nv) == hipSuccess && dc.alloc(&d_b, nv) == hipSuccess && dc.alloc(&d_res, (size_t)words) == hipSuccess;
-    if (ok && labels) ok = dc.alloc(&d_l, nv) == hipSuccess && dc.alloc(&d_slot, 65536) == hipSuccess;
+    if (ok && labels) ok = dc.alloc(&d_l, nv) == hipSuccess && dc.alloc(&d_slot, SIFT3D_LABEL_COUNT) == hipSuccess;
     if (ok && flush == 0) ok = dc.alloc(&d_sh, (size_t)blocks * cells) == hipSuccess && dc.alloc(&d_ss, (size_t)blocks * (words - cells)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        return call_fail(err, err_len, SIFT3D_ERR_MEMORY, "cannot allocate %zu bytes on device %d", (labels ? 12 : 8) * nv + (size_t)blocks * words * 8, device);
-    }
+    if (!ok) return dc.no_memory();
     DEVCHK(dc, dc.to_device(d_a, a, nv));
     DEVCHK(dc, dc.to_device(d_b, b, nv));
     if (labels) {
         DEVCHK(dc, dc.to_device(d_l, labels, nv));
-        DEVCHK(dc, dc.to_device(d_slot, slot_of, 65536));
+        DEVCHK(dc, dc.to_device(d_slot, slot_of, SIFT3D_LABEL_COUNT));
     }
-    DEVCHK(dc, hipEventRecord(dc.e0, dc.s));
+    DEVCHK(dc, dc.mark(0));
     DEVCHK(dc, sift3d_launch_joint_hist(dc.s, d_a, d_b, d_l, d_slot, n, (double)ar[0], (double)ar[1], (double)br[0], (double)br[1], bins, flush, d_res, d_sh,
                                         d_ss));
-    DEVCHK(dc, hipEventRecord(dc.e1, dc.s));
+    DEVCHK(dc, dc.mark(1));
     DEVCHK(dc, dc.download(res, d_res, (size_t)words));
     DEVCHK(dc, dc.sync());
     DEVCHK(dc, dc.elapsed_ms(kernel_ms));
@@ -100,12 +97,7 @@ extern "C" int sift3d_image_similarity(const float *a, const float *b, const flo
     if (sift3d_ccl_check_extents(nx, ny, nz, err, err_len) != 0) return SIFT3D_ERR_ARG;
     if (sift3d_similarity_check(&p, err, err_len) != 0) return SIFT3D_ERR_ARG;
     const int64_t n = nx * ny * nz;
-    if (labels) {
-        const int64_t at = sift3d_fuse_check_labels(labels, n);
-        if (at >= 0)
-            return call_fail(err, err_len, SIFT3D_ERR_ARG, "the label %g at voxel %lld is neither non-finite nor an integer 0 .. 65535", (double)labels[at],
-                             (long long)at);
-    }
+    if (labels && check_labels("", labels, n, err, err_len) != SIFT3D_OK) return SIFT3D_ERR_ARG;
     float ar[2] = {0, 0}, br[2] = {0, 0};
     int empty = sift3d_blockmatch_range(a, n, &ar[0], &ar[1]) ? 0 : 1;
     if (p.same_scale) {
@@ -129,15 +121,15 @@ extern "C" int sift3d_image_similarity(const float *a, const float *b, const flo
     std::vector<unsigned char> slot_of;
     std::vector<int> present;
     if (labels) {
-        std::vector<unsigned char> seen(65536, 0);
+        std::vector<unsigned char> seen(SIFT3D_LABEL_COUNT, 0);
         for (int64_t i = 0; i < n; i++)
             if (std::isfinite(labels[i]) && std::isfinite(a[i]) && std::isfinite(b[i])) seen[(int)labels[i]] = 1;
-        for (int l = 0; l < 65536; l++)
+        for (int l = 0; l < SIFT3D_LABEL_COUNT; l++)
             if (seen[l]) present.push_back(l);
         if ((int64_t)present.size() > p.max_labels)
             return call_fail(err, err_len, SIFT3D_ERR_ARG, "%lld labels on counted voxels: more than max_labels = %d (nothing is dropped)",
                              (long long)present.size(), (int)p.max_labels);
-        slot_of.assign(65536, SIM_NO_SLOT);
+        slot_of.assign(SIFT3D_LABEL_COUNT, SIM_NO_SLOT);
         for (size_t k = 0; k < present.size(); k++) slot_of[(size_t)present[k]] = (unsigned char)k;
     }
     std::vector<unsigned long long> res((size_t)sift3d_similarity_words(p.bins, labels != nullptr));

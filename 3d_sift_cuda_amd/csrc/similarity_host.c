@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "sift3d.h"
+#include "quantize.h"
 
 void sift3d_similarity_defaults(sift3d_similarity_params *p)
 {
@@ -54,7 +55,7 @@ static void rho_rms(const int64_t *s, float lo, float hi, int32_t same_scale, do
     if (n <= 0) return;
     if (same_scale) {
         const int64_t d = s[3] - 2 * s[5] + s[4];
-        *rms = sqrt((double)d / (double)n) * (((double)hi - (double)lo) / 1023.0);
+        *rms = sqrt((double)d / (double)n) * (((double)hi - (double)lo) / (double)QMAX);
     }
     const __int128 c = (__int128)n * s[5] - (__int128)s[1] * s[2];
     const __int128 va = (__int128)n * s[3] - (__int128)s[1] * s[1];

@@ -1140,10 +1140,12 @@ int sift3d_fuse_labels(int device, const float *target, int64_t nx, int64_t ny, 
 /* Host helpers (also in libsift3d_host.so).
  * u from the six sums under a metric, as stated above; 0 for n <= 0 or an unknown metric. */
 uint32_t sift3d_fuse_similarity(int32_t metric, int64_t n, int64_t sf, int64_t sff, int64_t sw, int64_t sww, int64_t sfw);
+/* The label domain: a finite voxel of a label volume is an integer 0 .. SIFT3D_LABEL_COUNT - 1 */
+#define SIFT3D_LABEL_COUNT 65536
 /* The first voxel of a label volume that is neither non-finite nor an integer 0 .. 65535, or -1 for none */
 int64_t sift3d_fuse_check_labels(const float *labels, int64_t n);
 /* The overlap of two label volumes in exact counts: per label l, count_a[l] and count_b[l] voxels of that label (non-finite voxels
- * have none) and count_both[l] where both have it; each array holds 65536 counts.  Dice(l) = 2 count_both / (count_a + count_b).
+ * have none) and count_both[l] where both have it; each array holds SIFT3D_LABEL_COUNT counts.  Dice(l) = 2 count_both / (count_a + count_b).
  * Returns the number of labels that occur in either volume, or -1 where sift3d_fuse_check_labels refuses one of them. */
 int64_t sift3d_label_overlap(const float *a, const float *b, int64_t n, int64_t *count_a, int64_t *count_b, int64_t *count_both);
 

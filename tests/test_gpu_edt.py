@@ -132,6 +132,33 @@ def test_surface_distances_of_a_label_in_one_volume_only(built, ed):
     assert by[1]["n_a"] > 0 and by[1]["n_b"] > 0 and by[1]["hausdorff_mm"] > 0
 
 
+def test_surface_distances_past_one_grid_of_the_label_kernel(built, ed):
+    """kernels_label.hip: label_plane_kernel has at most 2048 workgroups of 256 threads and goes round a grid loop beyond them.  578000
+    voxels are more than one round and no multiple of 64, so the last validity word holds 16 voxels.  Label 1 is a box around voxel
+    524288, where the second round starts; label 2 lies wholly in the first round; NaN voxels are scattered in both volumes, in both
+    boxes and among the last 16 voxels."""
+    shape = (5, 340, 340)
+    n, grid = shape[0] * shape[1] * shape[2], 2048 * 256
+    assert n > grid and n % 64 == 16
+    a, b = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+    a[3:5, 176:192, 0:40] = 1
+    b[3:5, 178:194, 3:43] = 1
+    a[0:3, 10:20, 10:30] = 2
+    b[0:3, 12:22, 9:29] = 2
+    fa, fb = a.reshape(-1), b.reshape(-1)
+    assert fa[grid - 1] == 1 and fa[grid] == 1 and fb[grid + 3] == 1 and fa[:grid].max() == 2 and (fa[grid:] != 2).all() and (fb[grid:] != 2).all()
+    rng = np.random.default_rng(11)
+    for flat, last in ((fa, (n - 16, n - 7, n - 1)), (fb, (n - 16, n - 2))):
+        flat[rng.random(n) < 0.001] = np.nan
+        flat[list(last)] = np.nan
+    a[3, 176, 5] = a[0, 10, 15] = b[3, 178, 8] = b[0, 12, 14] = np.nan     # one inside every box
+    spacing = (700, 1300, 3000)
+    got = built.surface_distances(a, b, spacing, first_label=1)
+    want = oracle_records(built, ed, a, b, spacing, first_label=1)
+    same_records(got, want)
+    assert [r["label"] for r in got] == [1, 2] and all(0 < r["n_a"] < 2000 and 0 < r["n_b"] < 2000 and r["max_ab"] > 0 for r in got)
+
+
 def test_surface_distances_refusals(built):
     a, b = blocky_pair()
     with pytest.raises(built.Sift3DError, match=r"5 labels from 0 on .* max_labels = 4"):
