@@ -14,9 +14,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "cli_common.h"
 #include "label_report.h"
-#include "nifti_min.h"
-#include "sift3d.h"
 
 static void print_options(void)
 {
@@ -31,13 +30,6 @@ static void print_options(void)
     printf("  -t <truth>     : label image on the input's grid: also the Dice overlap per label of the input and of the output with it.\n");
     printf("  -m             : with -t: also the surface distances per label of both to the truth, in mm by the voxel size.\n");
     printf("  -d[0-9]        : set device id to be used.\n");
-}
-
-static int bad_option(const char *what, const char *arg)
-{
-    printf("Error: %s: %s\n", what, arg);
-    print_options();
-    return -1;
 }
 
 /* per_label[l]: the components of the label l; returns their total, or -1 with the reason in err */
@@ -85,43 +77,34 @@ int main(int argc, char **argv)
     sift3d_clean_defaults(&p);
     int arg = 1;
     while (arg < argc && argv[arg][0] == '-' && argv[arg][1] != 0) {
-        char *end = NULL;
         switch (argv[arg][1]) {
-        case 'v': {
-            const long v = strtol(argv[arg] + 2, &end, 10);
-            if (end == argv[arg] + 2 || *end != 0 || v < 1 || v > SIFT3D_CLEAN_MAX_MIN_VOXELS) return bad_option("bad minimum of voxels", argv[arg]);
-            p.min_voxels = (int32_t)v;
+        case 'v':
+            if (cli_int(argv[arg] + 2, 1, SIFT3D_CLEAN_MAX_MIN_VOXELS, &p.min_voxels) != 0) return cli_refuse(print_options, "bad minimum of voxels: %s", argv[arg]);
             break;
-        }
         case 'c':
-            if (strcmp(argv[arg], "-c6") != 0 && strcmp(argv[arg], "-c26") != 0) return bad_option("bad connectivity", argv[arg]);
+            if (strcmp(argv[arg], "-c6") != 0 && strcmp(argv[arg], "-c26") != 0) return cli_refuse(print_options, "bad connectivity: %s", argv[arg]);
             p.connectivity = argv[arg][2] == '6' ? 6 : 26;
             break;
-        case 'r': {
-            const long v = strtol(argv[arg] + 2, &end, 10);
-            if (end == argv[arg] + 2 || *end != 0 || v < 1 || v > SIFT3D_CLEAN_MAX_ROUNDS) return bad_option("bad number of rounds", argv[arg]);
-            p.rounds = (int32_t)v;
+        case 'r':
+            if (cli_int(argv[arg] + 2, 1, SIFT3D_CLEAN_MAX_ROUNDS, &p.rounds) != 0) return cli_refuse(print_options, "bad number of rounds: %s", argv[arg]);
             break;
-        }
         case 't':
-            if (argv[arg][2] != 0 || arg + 1 >= argc) return bad_option("-t needs a label image", argv[arg]);
+            if (!cli_bare(argv[arg]) || arg + 1 >= argc) return cli_refuse(print_options, "-t needs a label image: %s", argv[arg]);
             truth_path = argv[++arg];
             break;
         case 'm':
-            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             measure = 1;
             break;
         case 'd':
-            if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count())
-                return bad_option("unknown device", argv[arg] + 2);
-            p.device = argv[arg][2] - '0';
+            if ((p.device = cli_device(argv[arg])) < 0) return cli_refuse(print_options, "unknown device: %s", argv[arg] + 2);
             break;
         default:
-            return bad_option("unknown command line argument", argv[arg]);
+            return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
         }
         arg++;
     }
-    if (measure && !truth_path) return bad_option("the surface distances are taken to a truth", "-m without -t");
+    if (measure && !truth_path) return cli_refuse(print_options, "the surface distances are taken to a truth: -m without -t");
     if (argc - arg != 2) {
         print_options();
         return -1;
@@ -130,39 +113,20 @@ int main(int argc, char **argv)
     nifti_min_image in, truth;
     float *out = NULL;
     int64_t *counts = NULL;
+    char *path = NULL;
     FILE *o = NULL;
     int rc = -1;
     memset(&in, 0, sizeof in);
     memset(&truth, 0, sizeof truth);
-    if (nifti_min_read(in_path, &in) != 0) {
-        printf("Error: could not read input file: %s\n", in_path);
-        goto done;
-    }
-    if (truth_path && nifti_min_read(truth_path, &truth) != 0) {
-        printf("Error: could not read input file: %s\n", truth_path);
-        goto done;
-    }
+    if (cli_read_image(in_path, &in) != 0) goto done;
+    if (truth_path && cli_read_image(truth_path, &truth) != 0) goto done;
     if (truth_path && (in.nx != truth.nx || in.ny != truth.ny || in.nz != truth.nz)) {
         printf("Error: the images are not on one grid: %d x %d x %d voxels against %d x %d x %d\n", in.nx, in.ny, in.nz, truth.nx, truth.ny, truth.nz);
         goto done;
     }
     char err[512] = "";
-    uint32_t spacing_um[3] = {0, 0, 0}, other_um[3] = {0, 0, 0};
-    if (measure) {
-        if (label_report_spacing(in.dx, in.dy, in.dz, spacing_um, err, sizeof err) != 0) {
-            printf("Error: %s: %s\n", err, in_path);
-            goto done;
-        }
-        if (label_report_spacing(truth.dx, truth.dy, truth.dz, other_um, err, sizeof err) != 0) {
-            printf("Error: %s: %s\n", err, truth_path);
-            goto done;
-        }
-        if (memcmp(spacing_um, other_um, sizeof spacing_um) != 0) {
-            printf("Error: the images are not on one grid: voxels of %u x %u x %u um against %u x %u x %u um\n", (unsigned)spacing_um[0], (unsigned)spacing_um[1],
-                   (unsigned)spacing_um[2], (unsigned)other_um[0], (unsigned)other_um[1], (unsigned)other_um[2]);
-            goto done;
-        }
-    }
+    uint32_t spacing_um[3] = {0, 0, 0};
+    if (measure && label_report_common_spacing(&in, &truth, in_path, truth_path, spacing_um) != 0) goto done;
     const int64_t n = (int64_t)in.nx * in.ny * in.nz;
     out = (float *)malloc(sizeof(float) * (size_t)n);
     counts = (int64_t *)malloc(sizeof(int64_t) * 5 * SIFT3D_LABEL_COUNT); /* three of the overlap, the components per label before and after */
@@ -186,8 +150,9 @@ int main(int argc, char **argv)
         printf("Error: could not write output file: %s\n", out_path);
         goto done;
     }
-    char path[4096], text[4096];
-    if (snprintf(path, sizeof path, "%s.clean.txt", out_path) >= (int)sizeof path || !(o = fopen(path, "w"))) {
+    char text[4096];
+    path = cli_path(out_path, ".clean.txt");
+    if (!path || !(o = fopen(path, "w"))) {
         printf("Error: could not write output file: %s.clean.txt\n", out_path);
         goto done;
     }
@@ -217,6 +182,7 @@ int main(int argc, char **argv)
     rc = 0;
 done:
     if (o) fclose(o);
+    free(path);
     free(out);
     free(counts);
     nifti_min_free(&in);

@@ -12,8 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "nifti_min.h"
-#include "sift3d.h"
+#include "cli_common.h"
 
 static void print_options(void)
 {
@@ -31,13 +30,6 @@ static void print_options(void)
     printf("  -d[0-9]    : set device id to be used.\n");
 }
 
-static int bad_option(const char *what, const char *arg)
-{
-    printf("Error: %s: %s\n", what, arg);
-    print_options();
-    return -1;
-}
-
 int main(int argc, char **argv)
 {
     sift3d_similarity_params p;
@@ -46,28 +38,23 @@ int main(int argc, char **argv)
     int arg = 1;
     while (arg < argc && argv[arg][0] == '-' && argv[arg][1] != 0) {
         switch (argv[arg][1]) {
-        case 'b': {
-            char *end = NULL;
-            const long v = strtol(argv[arg] + 2, &end, 10);
-            if (argv[arg][2] == 0 || *end != 0 || (v != 8 && v != 16 && v != 32 && v != 64)) return bad_option("bad number of bins", argv[arg]);
-            p.bins = (int32_t)v;
+        case 'b':
+            if (cli_int(argv[arg] + 2, 8, 64, &p.bins) != 0 || (p.bins != 8 && p.bins != 16 && p.bins != 32 && p.bins != 64))
+                return cli_refuse(print_options, "bad number of bins: %s", argv[arg]);
             break;
-        }
         case 's':
-            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             p.same_scale = 1;
             break;
         case 'l':
-            if (argv[arg][2] != 0 || arg + 1 >= argc) return bad_option("unknown command line argument", argv[arg]);
+            if (!cli_bare(argv[arg]) || arg + 1 >= argc) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             l_path = argv[++arg];
             break;
         case 'd':
-            if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count())
-                return bad_option("unknown device", argv[arg] + 2);
-            p.device = argv[arg][2] - '0';
+            if ((p.device = cli_device(argv[arg])) < 0) return cli_refuse(print_options, "unknown device: %s", argv[arg] + 2);
             break;
         default:
-            return bad_option("unknown command line argument", argv[arg]);
+            return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
         }
         arg++;
     }
@@ -85,18 +72,9 @@ int main(int argc, char **argv)
     memset(&a, 0, sizeof a);
     memset(&b, 0, sizeof b);
     memset(&l, 0, sizeof l);
-    if (nifti_min_read(a_path, &a) != 0) {
-        printf("Error: could not read input file: %s\n", a_path);
-        goto done;
-    }
-    if (nifti_min_read(b_path, &b) != 0) {
-        printf("Error: could not read input file: %s\n", b_path);
-        goto done;
-    }
-    if (l_path && nifti_min_read(l_path, &l) != 0) {
-        printf("Error: could not read input file: %s\n", l_path);
-        goto done;
-    }
+    if (cli_read_image(a_path, &a) != 0) goto done;
+    if (cli_read_image(b_path, &b) != 0) goto done;
+    if (l_path && cli_read_image(l_path, &l) != 0) goto done;
     if (a.nx != b.nx || a.ny != b.ny || a.nz != b.nz) {
         printf("Error: the images are not on one grid: %d x %d x %d voxels against %d x %d x %d\n", a.nx, a.ny, a.nz, b.nx, b.ny, b.nz);
         goto done;
@@ -123,19 +101,10 @@ int main(int argc, char **argv)
         printf("Error: insufficient memory.\n");
         goto done;
     }
-    o = out_path ? fopen(out_path, "w") : stdout;
-    if (!o) {
-        printf("Error: could not write output file: %s\n", out_path);
-        goto done;
-    }
+    if (!(o = cli_open_out(out_path))) goto done;
     fprintf(o, "# featCompare v1.0 bins %d\n%s", (int)rec->bins, text);
-    const int closed = out_path ? fclose(o) : fflush(o);
+    rc = cli_close_out(o, out_path);
     o = NULL;
-    if (closed != 0) {
-        printf("Error: could not write output file: %s\n", out_path ? out_path : "(standard output)");
-        goto done;
-    }
-    rc = 0;
 done:
     if (o && out_path) fclose(o);
     free(text);

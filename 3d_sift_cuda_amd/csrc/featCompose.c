@@ -15,8 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "nifti_min.h"
-#include "sift3d.h"
+#include "cli_common.h"
 
 static void print_options(void)
 {
@@ -35,53 +34,12 @@ static void print_options(void)
     printf("  -d[0-9]     : set device id to be used.\n");
 }
 
-/* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
-static void world_matrix(nifti_min_image *img, int world_mode, float m[16])
-{
-    float(*w)[4] = img->qto_xyz;
-    if (world_mode == 2) {
-        if (img->sform_code > 0) w = img->sto_xyz;
-        else printf("Error: sform_code <= 0, using qto_xyz instead of sto_xyz\n");
-    }
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) m[4 * r + c] = w[r][c];
-    m[12] = m[13] = m[14] = 0.0f;
-    m[15] = 1.0f;
-}
-
-/* 0, or -1 with a message: the field file at path into f (its disp allocated here) */
-static int read_field(const char *path, sift3d_field *f)
-{
-    memset(f, 0, sizeof *f);
-    int rc = sift3d_read_field(path, f);
-    if (rc == SIFT3D_ERR_CAPACITY) {
-        f->capacity = 3 * f->n[0] * f->n[1] * f->n[2];
-        f->disp = (float *)malloc(sizeof(float) * (size_t)f->capacity);
-        rc = f->disp ? sift3d_read_field(path, f) : SIFT3D_ERR_MEMORY;
-    }
-    if (rc != SIFT3D_OK) {
-        printf("Error: could not read displacement field file: %s\n", path);
-        return -1;
-    }
-    return 0;
-}
-
 /* the composite field to <out>.field.nii, its grid, the parameters and the report to <out>.field.txt */
 static int write_composite(const char *out_path, const sift3d_field *f, const sift3d_compose_params *p, const sift3d_compose_report *rep)
 {
-    char *path = (char *)malloc(strlen(out_path) + 16);
-    if (!path) return -1;
-    sprintf(path, "%s.field.nii", out_path);
-    if (sift3d_write_field(path, f) != 0) {
-        free(path);
-        return -1;
-    }
-    sprintf(path, "%s.field.txt", out_path);
-    FILE *o = fopen(path, "w");
-    free(path);
+    FILE *o = cli_write_field(out_path, ".field", f);
     if (!o) return -1;
-    fprintf(o, "# nodes %lld %lld %lld spacing %f origin %f %f %f radius %f margin %d\n", (long long)f->n[0], (long long)f->n[1], (long long)f->n[2],
-            f->spacing, f->origin[0], f->origin[1], f->origin[2], p->radius, p->margin);
+    fprintf(o, " radius %f margin %d\n", p->radius, p->margin);
     fprintf(o, "# nodes outside1 outside2 zeroed max_disp folds residual_cells rms_residual max_residual\n");
     fprintf(o, "%lld\t%lld\t%lld\t%lld\t%f\t%lld\t%lld\t%g\t%g\n", (long long)rep->nodes, (long long)rep->outside1, (long long)rep->outside2,
             (long long)rep->zeroed, rep->max_disp, (long long)rep->folds, (long long)rep->residual_cells, rep->rms_residual, rep->max_residual);
@@ -98,40 +56,22 @@ int main(int argc, char **argv)
         switch (argv[arg][1]) {
         case 'w':
         case 'W':
-            world_mode = 1;
-            if (argv[arg][2] == 's' || argv[arg][2] == 'S') world_mode = 2;
+            world_mode = cli_world_mode(argv[arg]);
             break;
         case 'd':
-            if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count()) {
-                printf("Error: unknown device: %s\n", argv[arg] + 2);
-                print_options();
-                return -1;
-            }
-            device = argv[arg][2] - '0';
+            if ((device = cli_device(argv[arg])) < 0) return cli_refuse(print_options, "unknown device: %s", argv[arg] + 2);
             break;
-        case 'h': {
-            char *end = NULL;
-            spacing = strtof(argv[arg] + 2, &end);
-            if (end == argv[arg] + 2 || *end != 0 || !(spacing > 0.0f)) {
-                printf("Error: bad spacing: %s\n", argv[arg]);
-                print_options();
-                return -1;
-            }
+        case 'h':
+            if (cli_float(argv[arg] + 2, &spacing) != 0 || !(spacing > 0.0f)) return cli_refuse(print_options, "bad spacing: %s", argv[arg]);
             break;
-        }
         case 'u':
-            if ((argv[arg][2] != '1' && argv[arg][2] != '2') || argv[arg][3] != 0 || arg + 1 >= argc) {
-                printf("Error: -u1 and -u2 need a field file\n");
-                print_options();
-                return -1;
-            }
+            if ((argv[arg][2] != '1' && argv[arg][2] != '2') || argv[arg][3] != 0 || arg + 1 >= argc)
+                return cli_refuse(print_options, "-u1 and -u2 need a field file");
             field_path[argv[arg][2] - '1'] = argv[arg + 1];
             arg++;
             break;
         default:
-            printf("Error: unknown command line argument: %s\n", argv[arg]);
-            print_options();
-            return -1;
+            return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
         }
         arg++;
     }
@@ -148,23 +88,20 @@ int main(int argc, char **argv)
         return -1;
     }
     nifti_min_close(as);
-    float m[2][16], mc[16], mr[16], aw[16], av[16];
+    float m[2][16], mc[16], mr[16], av[16];
     for (int k = 0; k < 2; k++)
         if (sift3d_read_similarity(trans_path[k], m[k]) != 0) {
             printf("Error: could not read transform file: %s\n", trans_path[k]);
             return -1;
         }
-    const float avox[3] = {a.dx, a.dy, a.dz};
-    if (world_mode) world_matrix(&a, world_mode, aw);
-    sift3d_key_vox2key(avox, world_mode ? aw : NULL, av);
+    cli_image_vox2key(&a, world_mode, av);
     sift3d_field field[2];
     for (int k = 0; k < 2; k++)
-        if (field_path[k] && read_field(field_path[k], &field[k]) != 0) return -1;
+        if (field_path[k] && cli_read_field(field_path[k], &field[k]) != 0) return -1;
     const sift3d_field *f1 = field_path[0] ? &field[0] : NULL, *f2 = field_path[1] ? &field[1] : NULL;
 
-    char *path = (char *)malloc(strlen(out_path) + 16);
+    char *path = cli_path(out_path, ".trans.txt");
     if (!path) return -1;
-    sprintf(path, "%s.trans.txt", out_path);
     /* the composite matrix as a reader of the file gets it: the field below is solved against these digits */
     if (sift3d_compose_matrix(m[0], m[1], mc) != 0 || sift3d_write_matrix(path, mc) != 0 || sift3d_read_similarity(path, mr) != 0) {
         printf("Error: could not compose the transforms or write: %s\n", path);
@@ -185,11 +122,9 @@ int main(int argc, char **argv)
     }
     printf("Composing: %s . %s on %s (i=%d j=%d k=%d): %lld x %lld x %lld nodes, spacing %g\n", trans_path[0], trans_path[1], a_path, a.nx, a.ny, a.nz,
            (long long)out.n[0], (long long)out.n[1], (long long)out.n[2], out.spacing);
-    out.capacity = 3 * out.n[0] * out.n[1] * out.n[2];
-    out.disp = (float *)malloc(sizeof(float) * (size_t)out.capacity);
     char err[512] = "";
     sift3d_compose_report rep;
-    if (!out.disp || sift3d_compose_field(device, m[0], m[1], mr, f1, f2, &p, &out, &rep, err, sizeof err) != SIFT3D_OK) {
+    if (cli_alloc_field(&out) != 0 || sift3d_compose_field(device, m[0], m[1], mr, f1, f2, &p, &out, &rep, err, sizeof err) != SIFT3D_OK) {
         printf("Error: could not compose the fields: %s\n", out.disp ? err : "insufficient memory");
         return -1;
     }

@@ -22,9 +22,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "cli_common.h"
 #include "label_report.h"
-#include "nifti_min.h"
-#include "sift3d.h"
 
 static void print_options(void)
 {
@@ -54,35 +53,6 @@ static void print_options(void)
     printf("  -d[0-9]    : set device id to be used.\n");
 }
 
-/* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
-static void world_matrix(nifti_min_image *img, int world_mode, float m[16])
-{
-    float(*w)[4] = img->qto_xyz;
-    if (world_mode == 2) {
-        if (img->sform_code > 0) w = img->sto_xyz;
-        else printf("Error: sform_code <= 0, using qto_xyz instead of sto_xyz\n");
-    }
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) m[4 * r + c] = w[r][c];
-    m[12] = m[13] = m[14] = 0.0f;
-    m[15] = 1.0f;
-}
-
-static void image_vox2key(nifti_min_image *img, int world_mode, float v[16])
-{
-    const float vox[3] = {img->dx, img->dy, img->dz};
-    float w[16];
-    if (world_mode) world_matrix(img, world_mode, w);
-    sift3d_key_vox2key(vox, world_mode ? w : NULL, v);
-}
-
-static int bad_option(const char *what, const char *arg)
-{
-    printf("Error: %s: %s\n", what, arg);
-    print_options();
-    return -1;
-}
-
 /* <out>.fuse.txt */
 /* spacing_um: NULL, or the target's voxel size for the distance block of -m; -3 with the reason in err where that block fails */
 static int write_report(const char *out_path, int K, const sift3d_fuse_params *p, const sift3d_fuse_report *rep, const sift3d_fuse_search_report *srep,
@@ -91,10 +61,9 @@ static int write_report(const char *out_path, int K, const sift3d_fuse_params *p
 {
     const int64_t n = (int64_t)target->nx * target->ny * target->nz;
     int64_t *ca = (int64_t *)malloc(sizeof(int64_t) * 3 * SIFT3D_LABEL_COUNT);
-    char *path = (char *)malloc(strlen(out_path) + 16);
+    char *path = cli_path(out_path, ".fuse.txt");
     if (!ca || !path) return -1;
     int64_t *cb = ca + SIFT3D_LABEL_COUNT, *cboth = cb + SIFT3D_LABEL_COUNT;
-    sprintf(path, "%s.fuse.txt", out_path);
     FILE *o = fopen(path, "w");
     free(path);
     if (!o) return -1;
@@ -140,64 +109,50 @@ int main(int argc, char **argv)
     sift3d_fuse_defaults(&p);
     int arg = 1;
     while (arg < argc && argv[arg][0] == '-' && argv[arg][1] != 0) {
-        char *end = NULL;
         switch (argv[arg][1]) {
         case 'w':
         case 'W':
-            world_mode = 1;
-            if (argv[arg][2] == 's' || argv[arg][2] == 'S') world_mode = 2;
+            world_mode = cli_world_mode(argv[arg]);
             break;
         case 'c':
-            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             p.metric = SIFT3D_BLOCKMATCH_NCC;
             break;
-        case 'b': {
-            const long v = strtol(argv[arg] + 2, &end, 10);
-            if (end == argv[arg] + 2 || *end != 0 || v < 1 || v > SIFT3D_BLOCKMATCH_MAX_B) return bad_option("bad patch half-width", argv[arg]);
-            p.block = (int32_t)v;
+        case 'b':
+            if (cli_int(argv[arg] + 2, 1, SIFT3D_BLOCKMATCH_MAX_B, &p.block) != 0) return cli_refuse(print_options, "bad patch half-width: %s", argv[arg]);
             break;
-        }
-        case 'p': {
-            const long v = strtol(argv[arg] + 2, &end, 10);
-            if (end == argv[arg] + 2 || *end != 0 || v < 0 || v > 2) return bad_option("bad power", argv[arg]);
-            p.power = (int32_t)v;
+        case 'p':
+            if (cli_int(argv[arg] + 2, 0, 2, &p.power) != 0) return cli_refuse(print_options, "bad power: %s", argv[arg]);
             break;
-        }
-        case 's': {
-            const long v = strtol(argv[arg] + 2, &end, 10);
-            if (end == argv[arg] + 2 || *end != 0 || v < 1 || v > SIFT3D_FUSE_MAX_SEARCH) return bad_option("bad search radius", argv[arg]);
-            search = (int32_t)v;
+        case 's':
+            if (cli_int(argv[arg] + 2, 1, SIFT3D_FUSE_MAX_SEARCH, &search) != 0) return cli_refuse(print_options, "bad search radius: %s", argv[arg]);
             break;
-        }
         case 'l':
-            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             p.label_interp = SIFT3D_INTERP_LABEL;
             break;
         case 'f':
-            p.fill = strtof(argv[arg] + 2, &end);
-            if (end == argv[arg] + 2 || *end != 0) return bad_option("bad fill value", argv[arg]);
+            if (cli_float(argv[arg] + 2, &p.fill) != 0) return cli_refuse(print_options, "bad fill value: %s", argv[arg]);
             break;
         case 't':
-            if (argv[arg][2] != 0 || arg + 1 >= argc) return bad_option("-t needs a label image", argv[arg]);
+            if (!cli_bare(argv[arg]) || arg + 1 >= argc) return cli_refuse(print_options, "-t needs a label image: %s", argv[arg]);
             truth_path = argv[++arg];
             break;
         case 'm':
-            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             measure = 1;
             break;
         case 'd':
-            if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count())
-                return bad_option("unknown device", argv[arg] + 2);
-            device = argv[arg][2] - '0';
+            if ((device = cli_device(argv[arg])) < 0) return cli_refuse(print_options, "unknown device: %s", argv[arg] + 2);
             break;
         default:
-            return bad_option("unknown command line argument", argv[arg]);
+            return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
         }
         arg++;
     }
-    if (search > 0 && p.power == 0) return bad_option("a search needs weights to search by", "-s with -p0");
-    if (search > 0 && p.block + search > SIFT3D_BLOCKMATCH_MAX_B) return bad_option("the patch half-width plus the search radius must not exceed 6", "-b with -s");
-    if (measure && !truth_path) return bad_option("the surface distances are taken to a truth", "-m without -t");
+    if (search > 0 && p.power == 0) return cli_refuse(print_options, "a search needs weights to search by: -s with -p0");
+    if (search > 0 && p.block + search > SIFT3D_BLOCKMATCH_MAX_B) return cli_refuse(print_options, "the patch half-width plus the search radius must not exceed 6: -b with -s");
+    if (measure && !truth_path) return cli_refuse(print_options, "the surface distances are taken to a truth: -m without -t");
     const int rest = argc - arg - 2;
     if (rest < 4 || rest % 4 != 0 || rest / 4 > SIFT3D_FUSE_MAX_ATLASES) {
         if (rest > 0 && rest % 4 != 0) printf("Error: every atlas takes four arguments: <atlas image> <atlas labels> <atlas.trans.txt> <atlas.field.nii|->\n");
@@ -211,10 +166,7 @@ int main(int argc, char **argv)
 
     nifti_min_image target, truth;
     memset(&truth, 0, sizeof truth);
-    if (nifti_min_read(target_path, &target) != 0) {
-        printf("Error: could not read input file: %s\n", target_path);
-        return -1;
-    }
+    if (cli_read_image(target_path, &target) != 0) return -1;
     if (truth_path && (nifti_min_read(truth_path, &truth) != 0 || truth.nx != target.nx || truth.ny != target.ny || truth.nz != target.nz)) {
         printf("Error: could not read input file, or it is not on the target's grid: %s\n", truth_path);
         return -1;
@@ -226,7 +178,7 @@ int main(int argc, char **argv)
         return -1;
     }
     float tv[16];
-    image_vox2key(&target, world_mode, tv);
+    cli_image_vox2key(&target, world_mode, tv);
     const int64_t n = (int64_t)target.nx * target.ny * target.nz;
 
     sift3d_fuse_atlas *atlas = (sift3d_fuse_atlas *)calloc((size_t)K, sizeof *atlas);
@@ -241,10 +193,7 @@ int main(int argc, char **argv)
         const char *image_path = group[4 * k], *labels_path = group[4 * k + 1], *trans_path = group[4 * k + 2], *field_path = group[4 * k + 3];
         nifti_min_image *im = &img[2 * k], *lb = &img[2 * k + 1];
         float *mv = mats + 32 * k, *t = mv + 16;
-        if (nifti_min_read(image_path, im) != 0) {
-            printf("Error: could not read input file: %s\n", image_path);
-            return -1;
-        }
+        if (cli_read_image(image_path, im) != 0) return -1;
         if (nifti_min_read(labels_path, lb) != 0 || lb->nx != im->nx || lb->ny != im->ny || lb->nz != im->nz) {
             printf("Error: could not read input file, or it is not on the atlas image's grid: %s\n", labels_path);
             return -1;
@@ -253,18 +202,9 @@ int main(int argc, char **argv)
             printf("Error: could not read transform file: %s\n", trans_path);
             return -1;
         }
-        image_vox2key(im, world_mode, mv);
+        cli_image_vox2key(im, world_mode, mv);
         if (strcmp(field_path, "-") != 0) {
-            int frc = sift3d_read_field(field_path, &field[k]);
-            if (frc == SIFT3D_ERR_CAPACITY) {
-                field[k].capacity = 3 * field[k].n[0] * field[k].n[1] * field[k].n[2];
-                field[k].disp = (float *)malloc(sizeof(float) * (size_t)field[k].capacity);
-                frc = field[k].disp ? sift3d_read_field(field_path, &field[k]) : SIFT3D_ERR_MEMORY;
-            }
-            if (frc != SIFT3D_OK) {
-                printf("Error: could not read displacement field file: %s\n", field_path);
-                return -1;
-            }
+            if (cli_read_field(field_path, &field[k]) != 0) return -1;
             atlas[k].field = &field[k];
         }
         atlas[k].image = im->data;
@@ -278,7 +218,7 @@ int main(int argc, char **argv)
     printf("Fusing: %d atlases onto %s (i=%d j=%d k=%d)\n", K, target_path, target.nx, target.ny, target.nz);
     uint32_t *words = (uint32_t *)malloc(sizeof(uint32_t) * 2 * (size_t)n);
     float *labels = (float *)malloc(sizeof(float) * (size_t)n), *conf = (float *)malloc(sizeof(float) * (size_t)n);
-    char *path = (char *)malloc(strlen(out_path) + 16);
+    char *path = cli_path(out_path, ".conf.nii");
     if (!words || !labels || !conf || !path) {
         printf("Error: could not fuse, insufficient memory.\n");
         return -1;
@@ -296,7 +236,6 @@ int main(int argc, char **argv)
         labels[i] = (words[2 * i] & SIFT3D_FUSE_NONE) ? p.fill : (float)(words[2 * i] & 0xffffu);
         conf[i] = (float)words[2 * i + 1] / 65535.0f;
     }
-    sprintf(path, "%s.conf.nii", out_path);
     if (nifti_min_write_f32_geom(out_path, labels, target_path) != 0 || nifti_min_write_f32_geom(path, conf, target_path) != 0) {
         printf("Error: could not write output file: %s\n", out_path);
         return -1;

@@ -28,6 +28,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "cli_common.h"
 #include "keyfile.h"
 #include "match.h"
 #include "sift3d.h"
@@ -119,9 +120,8 @@ static int refine(const char *name, const key_set *fixed, const key_set *moving,
         return -1;
     }
     *t = r;
-    char *path = (char *)malloc(strlen(name) + 16);
+    char *path = cli_path(name, ".refine.txt");
     if (!path) return -1;
-    sprintf(path, "%s.refine.txt", name);
     FILE *f = fopen(path, "wt");
     free(path);
     if (!f) return -1;
@@ -156,29 +156,17 @@ static int fit_field(const char *name, const key_set *fixed, const key_set *movi
         printf("Error: the displacement field of %s needs too many nodes\n", name);
         return -1;
     }
-    f.capacity = 3 * f.n[0] * f.n[1] * f.n[2];
-    f.disp = (float *)malloc(sizeof(float) * (size_t)f.capacity);
-    if (!f.disp) return -1;
+    if (cli_alloc_field(&f) != 0) return -1;
     sift3d_field_report rep;
     if (sift3d_refine_field(device, fixed->f, fixed->n, moving->f, moving->n, t, &p, &f, &rep, err, sizeof err) != SIFT3D_OK) {
         printf("Error: displacement field of %s failed: %s\n", name, err);
         free(f.disp);
         return -1;
     }
-    char *path = (char *)malloc(strlen(name) + 16);
-    if (!path) {
-        free(f.disp);
-        return -1;
-    }
-    sprintf(path, "%s.field.nii", name);
-    rc = sift3d_write_field(path, &f);
+    FILE *o = cli_write_field(name, ".field", &f);
     free(f.disp);
-    sprintf(path, "%s.field.txt", name);
-    FILE *o = rc == 0 ? fopen(path, "wt") : NULL;
-    free(path);
     if (!o) return -1;
-    fprintf(o, "# nodes %lld %lld %lld spacing %f origin %f %f %f radius %f lambda %f\n", (long long)f.n[0], (long long)f.n[1], (long long)f.n[2],
-            f.spacing, f.origin[0], f.origin[1], f.origin[2], p.radius, p.lambda);
+    fprintf(o, " radius %f lambda %f\n", p.radius, p.lambda);
     fprintf(o, "# accepted kept rms_before rms_after max_disp folds\n");
     fprintf(o, "%d\t%d\t%f\t%f\t%f\t%lld\n", rep.accepted, rep.kept, rep.rms_before, rep.rms_after, rep.max_disp, (long long)rep.folds);
     return fclose(o) == 0 ? 0 : -1;

@@ -13,9 +13,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "cli_common.h"
 #include "label_report.h"
-#include "nifti_min.h"
-#include "sift3d.h"
 
 static void print_options(void)
 {
@@ -30,13 +29,6 @@ static void print_options(void)
     printf("  -d[0-9]    : set device id to be used.\n");
 }
 
-static int bad_option(const char *what, const char *arg)
-{
-    printf("Error: %s: %s\n", what, arg);
-    print_options();
-    return -1;
-}
-
 int main(int argc, char **argv)
 {
     int device = 0, measure = 0, zero = 0;
@@ -44,20 +36,18 @@ int main(int argc, char **argv)
     while (arg < argc && argv[arg][0] == '-' && argv[arg][1] != 0) {
         switch (argv[arg][1]) {
         case 'm':
-            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             measure = 1;
             break;
         case 'z':
-            if (argv[arg][2] != 0) return bad_option("unknown command line argument", argv[arg]);
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             zero = 1;
             break;
         case 'd':
-            if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count())
-                return bad_option("unknown device", argv[arg] + 2);
-            device = argv[arg][2] - '0';
+            if ((device = cli_device(argv[arg])) < 0) return cli_refuse(print_options, "unknown device: %s", argv[arg] + 2);
             break;
         default:
-            return bad_option("unknown command line argument", argv[arg]);
+            return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
         }
         arg++;
     }
@@ -72,35 +62,15 @@ int main(int argc, char **argv)
     int rc = -1;
     memset(&a, 0, sizeof a);
     memset(&b, 0, sizeof b);
-    if (nifti_min_read(a_path, &a) != 0) {
-        printf("Error: could not read input file: %s\n", a_path);
-        goto done;
-    }
-    if (nifti_min_read(b_path, &b) != 0) {
-        printf("Error: could not read input file: %s\n", b_path);
-        goto done;
-    }
+    if (cli_read_image(a_path, &a) != 0) goto done;
+    if (cli_read_image(b_path, &b) != 0) goto done;
     if (a.nx != b.nx || a.ny != b.ny || a.nz != b.nz) {
         printf("Error: the images are not on one grid: %d x %d x %d voxels against %d x %d x %d\n", a.nx, a.ny, a.nz, b.nx, b.ny, b.nz);
         goto done;
     }
     char err[512] = "";
-    uint32_t spacing_um[3] = {0, 0, 0}, other_um[3] = {0, 0, 0};
-    if (measure) {
-        if (label_report_spacing(a.dx, a.dy, a.dz, spacing_um, err, sizeof err) != 0) {
-            printf("Error: %s: %s\n", err, a_path);
-            goto done;
-        }
-        if (label_report_spacing(b.dx, b.dy, b.dz, other_um, err, sizeof err) != 0) {
-            printf("Error: %s: %s\n", err, b_path);
-            goto done;
-        }
-        if (memcmp(spacing_um, other_um, sizeof spacing_um) != 0) {
-            printf("Error: the images are not on one grid: voxels of %u x %u x %u um against %u x %u x %u um\n", (unsigned)spacing_um[0], (unsigned)spacing_um[1],
-                   (unsigned)spacing_um[2], (unsigned)other_um[0], (unsigned)other_um[1], (unsigned)other_um[2]);
-            goto done;
-        }
-    }
+    uint32_t spacing_um[3] = {0, 0, 0};
+    if (measure && label_report_common_spacing(&a, &b, a_path, b_path, spacing_um) != 0) goto done;
     const int64_t n = (int64_t)a.nx * a.ny * a.nz;
     ca = (int64_t *)malloc(sizeof(int64_t) * 3 * SIFT3D_LABEL_COUNT);
     if (!ca) {
@@ -112,23 +82,14 @@ int main(int argc, char **argv)
                sift3d_fuse_check_labels(a.data, n) >= 0 ? a_path : b_path);
         goto done;
     }
-    o = out_path ? fopen(out_path, "w") : stdout;
-    if (!o) {
-        printf("Error: could not write output file: %s\n", out_path);
-        goto done;
-    }
+    if (!(o = cli_open_out(out_path))) goto done;
     label_report_dice(o, ca, ca + SIFT3D_LABEL_COUNT, ca + 2 * SIFT3D_LABEL_COUNT);
     if (measure && label_report_distances(o, device, a.data, b.data, a.nx, a.ny, a.nz, spacing_um, zero ? 0 : 1, err, sizeof err) != 0) {
         printf("Error: could not take the surface distances: %s\n", err);
         goto done;
     }
-    const int closed = out_path ? fclose(o) : fflush(o);
+    rc = cli_close_out(o, out_path);
     o = NULL;
-    if (closed != 0) {
-        printf("Error: could not write output file: %s\n", out_path ? out_path : "(standard output)");
-        goto done;
-    }
-    rc = 0;
 done:
     if (o && out_path) fclose(o);
     free(ca);

@@ -28,8 +28,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "nifti_min.h"
-#include "sift3d.h"
+#include "cli_common.h"
 
 static void print_options(void)
 {
@@ -55,37 +54,13 @@ static void print_options(void)
     printf("  -j         : also write <output image>.jac.nii, the Jacobian determinant of the applied map (<= 0: a fold).\n");
 }
 
-/* the qto_xyz / sto_xyz featExtract -w / -ws used (featExtract.c: the same choice and fallback) */
-static void world_matrix(nifti_min_image *img, int world_mode, float m[16])
-{
-    float(*w)[4] = img->qto_xyz;
-    if (world_mode == 2) {
-        if (img->sform_code > 0) w = img->sto_xyz;
-        else printf("Error: sform_code <= 0, using qto_xyz instead of sto_xyz\n");
-    }
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) m[4 * r + c] = w[r][c];
-    m[12] = m[13] = m[14] = 0.0f;
-    m[15] = 1.0f;
-}
-
 /* -i: the refined field to <out>.field.nii, its grid and the report of every round to <out>.field.txt */
 static int write_refined(const char *out_path, const sift3d_field *f, const sift3d_blockmatch_params *p, const sift3d_blockmatch_report *rep,
                          int metric, const float moving_range[2])
 {
-    char *path = (char *)malloc(strlen(out_path) + 16);
-    if (!path) return -1;
-    sprintf(path, "%s.field.nii", out_path);
-    if (sift3d_write_field(path, f) != 0) {
-        free(path);
-        return -1;
-    }
-    sprintf(path, "%s.field.txt", out_path);
-    FILE *o = fopen(path, "w");
-    free(path);
+    FILE *o = cli_write_field(out_path, ".field", f);
     if (!o) return -1;
-    fprintf(o, "# nodes %lld %lld %lld spacing %f origin %f %f %f radius %f lambda %f\n", (long long)f->n[0], (long long)f->n[1], (long long)f->n[2],
-            f->spacing, f->origin[0], f->origin[1], f->origin[2], p->radius, p->lambda);
+    fprintf(o, " radius %f lambda %f\n", p->radius, p->lambda);
     fprintf(o, "# stride %d block %d search %d rounds %d variance_quantile %f cost_fraction %f quantised over %g .. %g%s\n", p->stride, p->block,
             p->search, p->rounds, p->variance_quantile, p->cost_fraction, rep->lo, rep->hi,
             rep->empty_range ? " (empty: nothing matched)" : "");
@@ -105,19 +80,9 @@ static int write_refined(const char *out_path, const sift3d_field *f, const sift
 /* -r: the inverse field to <out>.inv.field.nii, its grid, the parameters and the report to <out>.inv.field.txt */
 static int write_inverse(const char *out_path, const sift3d_field *f, const sift3d_invert_params *p, const sift3d_invert_report *rep)
 {
-    char *path = (char *)malloc(strlen(out_path) + 24);
-    if (!path) return -1;
-    sprintf(path, "%s.inv.field.nii", out_path);
-    if (sift3d_write_field(path, f) != 0) {
-        free(path);
-        return -1;
-    }
-    sprintf(path, "%s.inv.field.txt", out_path);
-    FILE *o = fopen(path, "w");
-    free(path);
+    FILE *o = cli_write_field(out_path, ".inv.field", f);
     if (!o) return -1;
-    fprintf(o, "# nodes %lld %lld %lld spacing %f origin %f %f %f radius %f\n", (long long)f->n[0], (long long)f->n[1], (long long)f->n[2], f->spacing,
-            f->origin[0], f->origin[1], f->origin[2], p->radius);
+    fprintf(o, " radius %f\n", p->radius);
     fprintf(o, "# max_iter %d tol %g\n", p->max_iter, p->tol);
     fprintf(o, "# nodes converged not_converged diverged max_steps rms_residual max_residual max_disp folds\n");
     fprintf(o, "%lld\t%lld\t%lld\t%lld\t%d\t%g\t%g\t%f\t%lld\n", (long long)rep->nodes, (long long)rep->converged, (long long)rep->not_converged,
@@ -130,11 +95,10 @@ static int write_jacobian(int device, const char *out_path, const char *geom_pat
                           const float out_vox2key[16], const float src_vox2key[16], const sift3d_field *field)
 {
     char err[512] = "";
-    char *path = (char *)malloc(strlen(out_path) + 16);
+    char *path = cli_path(out_path, ".jac.nii");
     float *jac = (float *)malloc(sizeof(float) * (size_t)nx * ny * nz);
     int rc = -1;
     if (path && jac) {
-        sprintf(path, "%s.jac.nii", out_path);
         if (sift3d_jacobian_map(device, nx, ny, nz, map, out_vox2key, src_vox2key, field, jac, -1, NULL, err, sizeof err) != SIFT3D_OK)
             printf("Error: could not compute the Jacobian map: %s\n", err);
         else if (nifti_min_write_f32_geom(path, jac, geom_path) != 0) printf("Error: could not write output file: %s\n", path);
@@ -152,9 +116,8 @@ static int reverse(int device, const char *fixed_path, const char *moving_path, 
 {
     char err[512] = "";
     float ti[16], tr[16], rmap[12];
-    char *path = (char *)malloc(strlen(out_path) + 24);
+    char *path = cli_path(out_path, ".inv.trans.txt");
     if (!path) return -1;
-    sprintf(path, "%s.inv.trans.txt", out_path);
     /* the inverse as a reader of the file gets it: the field below is solved against these digits */
     if (sift3d_affine_invert(t, ti) != 0 || sift3d_write_matrix(path, ti) != 0 || sift3d_read_similarity(path, tr) != 0 ||
         sift3d_resample_map(tr, mv, fv, rmap) != 0) {
@@ -182,9 +145,7 @@ static int reverse(int device, const char *fixed_path, const char *moving_path, 
             printf("Error: the inverse field's grid has more than %lld nodes\n", (long long)ip.max_nodes);
             return -1;
         }
-        inv.capacity = 3 * inv.n[0] * inv.n[1] * inv.n[2];
-        inv.disp = (float *)malloc(sizeof(float) * (size_t)inv.capacity);
-        if (!inv.disp || sift3d_invert_field(device, t, tr, field, &ip, &inv, &rep, err, sizeof err) != SIFT3D_OK) {
+        if (cli_alloc_field(&inv) != 0 || sift3d_invert_field(device, t, tr, field, &ip, &inv, &rep, err, sizeof err) != SIFT3D_OK) {
             printf("Error: could not invert the field: %s\n", inv.disp ? err : "insufficient memory");
             return -1;
         }
@@ -227,81 +188,42 @@ int main(int argc, char **argv)
         switch (argv[arg][1]) {
         case 'w':
         case 'W':
-            world_mode = 1;
-            if (argv[arg][2] == 's' || argv[arg][2] == 'S') world_mode = 2;
+            world_mode = cli_world_mode(argv[arg]);
             break;
         case 'n':
             nearest = 1;
             break;
         case 'l':
-            if (argv[arg][2] != 0) {
-                printf("Error: unknown command line argument: %s\n", argv[arg]);
-                print_options();
-                return -1;
-            }
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             label = 1;
             break;
-        case 'f': {
-            char *end = NULL;
-            fill = strtof(argv[arg] + 2, &end);
-            if (end == argv[arg] + 2 || *end != 0) {
-                printf("Error: bad fill value: %s\n", argv[arg]);
-                print_options();
-                return -1;
-            }
+        case 'f':
+            if (cli_float(argv[arg] + 2, &fill) != 0) return cli_refuse(print_options, "bad fill value: %s", argv[arg]);
             break;
-        }
         case 'd':
-            if (argv[arg][2] < '0' || argv[arg][2] > '9' || argv[arg][3] != 0 || argv[arg][2] - '0' >= sift3d_device_count()) {
-                printf("Error: unknown device: %s\n", argv[arg] + 2);
-                print_options();
-                return -1;
-            }
-            device = argv[arg][2] - '0';
+            if ((device = cli_device(argv[arg])) < 0) return cli_refuse(print_options, "unknown device: %s", argv[arg] + 2);
             break;
         case 'i':
             intensity = 1;
-            if (argv[arg][2] != 0) {
-                char *end = NULL;
-                const long v = strtol(argv[arg] + 2, &end, 10);
-                if (*end != 0 || v < 0 || v > SIFT3D_BLOCKMATCH_MAX_ROUNDS) {
-                    printf("Error: bad number of rounds: %s\n", argv[arg]);
-                    print_options();
-                    return -1;
-                }
-                rounds = (int)v;
-            }
+            if (!cli_bare(argv[arg]) && cli_int(argv[arg] + 2, 0, SIFT3D_BLOCKMATCH_MAX_ROUNDS, &rounds) != 0)
+                return cli_refuse(print_options, "bad number of rounds: %s", argv[arg]);
             break;
         case 'c':
-            if (argv[arg][2] != 0) {
-                printf("Error: unknown command line argument: %s\n", argv[arg]);
-                print_options();
-                return -1;
-            }
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             metric = SIFT3D_BLOCKMATCH_NCC;
             break;
         case 'r':
         case 'j':
-            if (argv[arg][2] != 0) {
-                printf("Error: unknown command line argument: %s\n", argv[arg]);
-                print_options();
-                return -1;
-            }
+            if (!cli_bare(argv[arg])) return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
             if (argv[arg][1] == 'r') backward = 1;
             else jacobian = 1;
             break;
         case 'u':
-            if (argv[arg][2] != 0 || arg + 1 >= argc) {
-                printf("Error: -u needs a field file\n");
-                print_options();
-                return -1;
-            }
+            if (!cli_bare(argv[arg]) || arg + 1 >= argc) return cli_refuse(print_options, "-u needs a field file");
             field_path = argv[++arg];
             break;
         default:
-            printf("Error: unknown command line argument: %s\n", argv[arg]);
-            print_options();
-            return -1;
+            return cli_refuse(print_options, "unknown command line argument: %s", argv[arg]);
         }
         arg++;
     }
@@ -309,17 +231,9 @@ int main(int argc, char **argv)
         print_options();
         return -1;
     }
-    if (nearest && label) {
-        printf("Error: -n and -l are two interpolations: give one\n");
-        print_options();
-        return -1;
-    }
+    if (nearest && label) return cli_refuse(print_options, "-n and -l are two interpolations: give one");
     const int interp = label ? SIFT3D_INTERP_LABEL : (nearest ? SIFT3D_INTERP_NEAREST : SIFT3D_INTERP_LINEAR);
-    if (metric != SIFT3D_BLOCKMATCH_SSD && !intensity) {
-        printf("Error: -c needs -i\n");
-        print_options();
-        return -1;
-    }
+    if (metric != SIFT3D_BLOCKMATCH_SSD && !intensity) return cli_refuse(print_options, "-c needs -i");
     const char *fixed_path = argv[arg], *moving_path = argv[arg + 1], *trans_path = argv[arg + 2], *out_path = argv[arg + 3];
 
     nifti_min_image fixed, moving;
@@ -329,26 +243,16 @@ int main(int argc, char **argv)
         return -1;
     }
     nifti_min_close(fs);
-    if ((intensity || backward) && nifti_min_read(fixed_path, &fixed) != 0) { /* -i matches against the fixed image's voxels, -r resamples them */
-        printf("Error: could not read input file: %s\n", fixed_path);
-        return -1;
-    }
-    if (nifti_min_read(moving_path, &moving) != 0) {
-        printf("Error: could not read input file: %s\n", moving_path);
-        return -1;
-    }
-    float t[16], fw[16], mw[16], fv[16], mv[16], map[12];
+    /* -i matches against the fixed image's voxels, -r resamples them */
+    if ((intensity || backward) && cli_read_image(fixed_path, &fixed) != 0) return -1;
+    if (cli_read_image(moving_path, &moving) != 0) return -1;
+    float t[16], fv[16], mv[16], map[12];
     if (sift3d_read_similarity(trans_path, t) != 0) {
         printf("Error: could not read transform file: %s\n", trans_path);
         return -1;
     }
-    const float fvox[3] = {fixed.dx, fixed.dy, fixed.dz}, mvox[3] = {moving.dx, moving.dy, moving.dz};
-    if (world_mode) {
-        world_matrix(&fixed, world_mode, fw);
-        world_matrix(&moving, world_mode, mw);
-    }
-    sift3d_key_vox2key(fvox, world_mode ? fw : NULL, fv);
-    sift3d_key_vox2key(mvox, world_mode ? mw : NULL, mv);
+    cli_image_vox2key(&fixed, world_mode, fv);
+    cli_image_vox2key(&moving, world_mode, mv);
     if (sift3d_resample_map(t, fv, mv, map) != 0) {
         printf("Error: singular transform: %s\n", trans_path);
         return -1;
@@ -366,18 +270,7 @@ int main(int argc, char **argv)
     double ms = 0;
     sift3d_field field;
     memset(&field, 0, sizeof field);
-    if (field_path) {
-        int frc = sift3d_read_field(field_path, &field);
-        if (frc == SIFT3D_ERR_CAPACITY) {
-            field.capacity = 3 * field.n[0] * field.n[1] * field.n[2];
-            field.disp = (float *)malloc(sizeof(float) * (size_t)field.capacity);
-            frc = field.disp ? sift3d_read_field(field_path, &field) : SIFT3D_ERR_MEMORY;
-        }
-        if (frc != SIFT3D_OK) {
-            printf("Error: could not read displacement field file: %s\n", field_path);
-            return -1;
-        }
-    }
+    if (field_path && cli_read_field(field_path, &field) != 0) return -1;
     if (intensity) {
         sift3d_blockmatch_params bp;
         sift3d_blockmatch_defaults(&bp);

@@ -2,6 +2,7 @@
  * label_report.c -- see label_report.h.
  */
 #include <stdlib.h>
+#include <string.h>
 
 #include "label_report.h"
 #include "sift3d.h"
@@ -29,6 +30,26 @@ int label_report_spacing(float dx, float dy, float dz, uint32_t spacing_um[3], c
             snprintf(err, err_len, "the voxel size %g mm along %c is not 0.001 .. 65.535 mm: no distances in micrometres", (double)mm[c], "xyz"[c]);
             return -1;
         }
+    return 0;
+}
+
+int label_report_common_spacing(const nifti_min_image *a, const nifti_min_image *b, const char *a_path, const char *b_path, uint32_t spacing_um[3])
+{
+    char err[512] = "";
+    uint32_t other_um[3];
+    if (label_report_spacing(a->dx, a->dy, a->dz, spacing_um, err, sizeof err) != 0) {
+        printf("Error: %s: %s\n", err, a_path);
+        return -1;
+    }
+    if (label_report_spacing(b->dx, b->dy, b->dz, other_um, err, sizeof err) != 0) {
+        printf("Error: %s: %s\n", err, b_path);
+        return -1;
+    }
+    if (memcmp(spacing_um, other_um, sizeof other_um) != 0) {
+        printf("Error: the images are not on one grid: voxels of %u x %u x %u um against %u x %u x %u um\n", (unsigned)spacing_um[0], (unsigned)spacing_um[1],
+               (unsigned)spacing_um[2], (unsigned)other_um[0], (unsigned)other_um[1], (unsigned)other_um[2]);
+        return -1;
+    }
     return 0;
 }
 
