@@ -1,6 +1,6 @@
 /*
  * desc_bins.h -- the 64 bin sums of the SIFT-rank descriptor (msResampleFeaturesGradientOrientationHistogram,
- * R/src_common/MultiScale.cpp:583-710) as descriptor_kernel<true> (kernels_keypoint.hip) forms them: which lane holds which
+ * R/src_common/MultiScale.cpp:583-710) as descriptor_kernel<true> (kernels_descriptor.hip) forms them: which lane holds which
  * bin, which voxels a bin's chain visits and with which weights.  Plain C++ for host and device, without a HIP include:
  * tests/desc_bins_check.cpp runs the same walk on the CPU against the oracle's o3_desc_sift (tests/test_desc_bins_cpu.py), as
  * tests/blur_plan_check.cpp does for blur_plan.h.

@@ -170,13 +170,43 @@ hipError_t sift3d_launch_extrema_octave_small(hipStream_t s, const float *const 
 #define SIFT3D_SURV_COUNTERS (EX_SEGS * EX_SEG_STRIDE)
 #define SIFT3D_LIST2_COUNTERS EX_SEGS
 
-/* ---- per-keypoint stage (kernels_keypoint.hip) ---- */
+/* ---- per-keypoint stage (phase A: kernels_keypoint.hip; phase B and the record bookkeeping: kernels_descriptor.hip; what
+ * both share: keypoint_device.h, keypoint_math.h, sample_order.h) ---- */
+/* The development stops: what sift3d_dev_set_stop (include/sift3d_dev.h) takes and debug_stop carries.  -DSIFT3D_DEV builds
+ * only; a kernel returns after the stage named, so that the stages can be timed by difference. */
+enum sift3d_dev_stop {
+    SIFT3D_STOP_NONE = 0, /* run everything */
+    /* keypoint_kernel (tools/kp_ablate.py); every extremum is reported as rejected */
+    SIFT3D_STOP_A_SAMPLED = 1,     /* after the identity-frame patch is sampled */
+    SIFT3D_STOP_A_NORMALIZED = 2,  /* after the patch is normalised */
+    SIFT3D_STOP_A_TENSOR = 3,      /* after the gradients and the nine structure-tensor chains */
+    SIFT3D_STOP_A_SPLAT = 4,       /* after the SVD + eigen test and the first orientation splat */
+    SIFT3D_STOP_A_SPLAT_5 = 5, SIFT3D_STOP_A_SPLAT_6 = 6, /* the same place as 4 */
+    SIFT3D_STOP_A_BLURRED = 7,     /* after the blur of the primary histogram */
+    SIFT3D_STOP_A_PEAKS = 8,       /* after the peak search of the primary histogram */
+    SIFT3D_STOP_A2_PREPASS = 31,   /* first primary peak: after the pre-pass of the secondary splat */
+    SIFT3D_STOP_A2_SPLAT = 32,     /* first primary peak: after the secondary splat */
+    SIFT3D_STOP_A2_BLURRED = 33,   /* first primary peak: after the blur of the secondary histogram */
+    SIFT3D_STOP_A2_PEAKS = 34,     /* first primary peak: after the peak search of the secondary histogram */
+    SIFT3D_STOP_A_SVD_FIRST = 40,  /* no stop: the SVD + eigen test before the first splat, not beside it (tools/kp_svd_first.py) */
+    /* descriptor_kernel (tools/desc_ablate.py) */
+    SIFT3D_STOP_B_SAMPLED = 11,    /* after the record's patch is loaded or sampled */
+    SIFT3D_STOP_B_NORMALIZED = 12, /* after the patch is normalised */
+    SIFT3D_STOP_B_GRADIENTS = 13,  /* SIFT-rank: after the gradient pre-pass */
+    /* 21 .. 26: every record samples one cache-resident region of its level instead of its own patch, then */
+    SIFT3D_STOP_B_CACHED_SAMPLED = 21,    /* stops after that sampling */
+    SIFT3D_STOP_B_CACHED_ALL = 22,        /* runs to the end */
+    SIFT3D_STOP_B_CACHED_NORMALIZED = 23, /* stops where 12 does */
+    SIFT3D_STOP_B_CACHED_GRADIENTS = 24,  /* stops where 13 does */
+    SIFT3D_STOP_B_CACHED_25 = 25,         /* no stage of its own: runs to the end as 22 does */
+    SIFT3D_STOP_B_CACHED_BINS = 26,       /* SIFT-rank: stops after the bin chains */
+};
 struct sift3d_kp_params {
     const sift3d_level *levels; /* device table indexed by level id */
     float eig_thres;
     float size_factor;
     int desc_mode;
-    int debug_stop; /* -DSIFT3D_DEV builds only (timing ablation, tools/kp_ablate.py): the kernels return after stage N; 0 = run everything */
+    int debug_stop; /* a sift3d_dev_stop; -DSIFT3D_DEV builds only (timing ablation, tools/kp_ablate.py); 0 = run everything */
     float *patch0;  /* per extremum: the identity-frame patch (1331 floats, normalised once) that phase A sampled anyway;
                      * phase B reads it for the un-reoriented record instead of sampling it again */
     int *sampler_tokens; /* phase B: per-CU count of workgroups in their sampling phase (SIFT3D_CU_SLOTS ints, zero between runs) */

@@ -35,7 +35,8 @@ int sift3d_selftest_alloc_fill(int byte, uint64_t stats[2]);
 
 #ifdef SIFT3D_DEV
 /* Development builds only (make DEV=1; tools/kp_ablate.py, tools/desc_ablate.py): the per-keypoint kernels return after
- * stage n (0 = run everything).  Not compiled into the product library. */
+ * stage n (0 = run everything; the codes and their stages: enum sift3d_dev_stop, csrc/sift3d_internal.h).  Not compiled into
+ * the product library. */
 int sift3d_dev_set_stop(sift3d_ctx *ctx, int n);
 /* Development builds only (tools/bench_match.py with KNN_PLAN=groups,segments): overrides how sift3d_knn64 cuts a search
  * (0 = the library's own choice). */

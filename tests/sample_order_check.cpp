@@ -3,15 +3,15 @@
  * Stand-alone (tests/test_sample_order_cpu.py builds it once plain and once under AddressSanitizer +
  * UndefinedBehaviorSanitizer).  Per record (a frame, a scale, a centre, a volume):
  *   - every sample's key lies inside the record's bins, and the bins fit the counters;
- *   - where the sample's position is finite, the key is the one that follows from the cells trilinear (kernels_keypoint.hip)
+ *   - where the sample's position is finite, the key is the one that follows from the cells trilinear (keypoint_device.h)
  *     takes for it: interp_coord per axis, before the slab's z offset is subtracted;
  *   - the counting sort, emulated the way the kernel runs it (packed 16-bit counters, the old value of an add as the rank,
  *     SAMPLE_ORDER_LANES chunks for the prefix), yields a permutation of 0 .. 1330 -- with the samples arriving in index order
  *     and in a shuffled order, as the LDS atomics of two wavefronts may.
  * Then the line model: over finite orthonormal frames in the interior of a 512^3 volume, the 128-byte lines the four lanes of a
  * quad touch in one gather instruction, summed over the quads, the four gathers of a sample and the instructions of a record
- * (64-lane instructions, 128 lanes, three samples per lane per trip) -- for the patch order of wave_sample_patch, restated here,
- * and for the new order.
+ * (64-lane instructions, 128 lanes, three samples per lane per trip) -- for the patch order wave_sample_patch takes from the
+ * header, and for the new order.
  * Prints "<family> <records> <bad>" per family and "lines <step> <patch order> <image order>" per step; exits 1 if any record
  * was bad.
  */
@@ -21,6 +21,7 @@
 #include <cstring>
 #include <limits>
 
+#include "keypoint_math.h" /* invert3 */
 #include "sample_order.h"
 
 #define PD SAMPLE_ORDER_PD
@@ -35,25 +36,6 @@ static uint32_t rnd32()
 }
 static float rndu() { return (float)(rnd32() >> 8) * (1.0f / 16777216.0f); } /* [0, 1) */
 static float rnds() { return 2.0f * rndu() - 1.0f; }
-
-/* invert_3x3 as the kernel has it */
-static void invert3(const float *in, float *out)
-{
-    float a11 = in[0], a21 = in[3], a31 = in[6];
-    float a12 = in[1], a22 = in[4], a32 = in[7];
-    float a13 = in[2], a23 = in[5], a33 = in[8];
-    float det = a11 * (a33 * a22 - a32 * a23) - a21 * (a33 * a12 - a32 * a13) + a31 * (a23 * a12 - a22 * a13);
-    double div = 1 / (double)det;
-    out[0] = (float)((a33 * a22 - a32 * a23) * div);
-    out[3] = (float)(-(a33 * a21 - a31 * a23) * div);
-    out[6] = (float)((a32 * a21 - a31 * a22) * div);
-    out[1] = (float)(-(a33 * a12 - a32 * a13) * div);
-    out[4] = (float)((a33 * a11 - a31 * a13) * div);
-    out[7] = (float)(-(a32 * a11 - a31 * a12) * div);
-    out[2] = (float)((a23 * a12 - a22 * a13) * div);
-    out[5] = (float)(-(a23 * a11 - a21 * a13) * div);
-    out[8] = (float)((a22 * a11 - a21 * a12) * div);
-}
 
 static void frame_random(float *f) /* a rotation from a random unit quaternion */
 {
@@ -163,16 +145,8 @@ static bool sort_record(const record &r, const int *arrival, unsigned short *ord
 /* wave_sample_patch's patch order: the t-th sample taken is patch voxel order[t] */
 static void patch_order(const float *inv, unsigned short *order)
 {
-    int ax_fast = 0, ax_mid = 1, ax_slow = 2;
-    const float f0 = fabsf(inv[0]), f1 = fabsf(inv[1]), f2 = fabsf(inv[2]);
-    ax_fast = f0 >= f1 && f0 >= f2 ? 0 : (f1 >= f2 ? 1 : 2);
-    const int r0 = ax_fast == 0 ? 1 : 0, r1 = ax_fast == 2 ? 1 : 2;
-    const bool firstb = fabsf(inv[3 + r0]) >= fabsf(inv[3 + r1]);
-    ax_mid = firstb ? r0 : r1;
-    ax_slow = firstb ? r1 : r0;
-    const int st_fast = ax_fast == 0 ? 1 : (ax_fast == 1 ? PD : PD * PD), st_mid = ax_mid == 0 ? 1 : (ax_mid == 1 ? PD : PD * PD),
-              st_slow = ax_slow == 0 ? 1 : (ax_slow == 1 ? PD : PD * PD);
-    for (int t = 0; t < PV; t++) order[t] = (unsigned short)((t % PD) * st_fast + ((t / PD) % PD) * st_mid + (t / (PD * PD)) * st_slow);
+    const sample_order_strides st = sample_order_patch_strides(inv);
+    for (int t = 0; t < PV; t++) order[t] = (unsigned short)sample_order_patch_voxel(t, st);
 }
 
 /* 128-byte lines per quad and gather instruction, summed over a record */

@@ -61,7 +61,7 @@ def test_product_reads_no_environment_variable(built):
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".h")):
             assert "getenv" not in open(os.path.join(csrc, f)).read(), f
-    for obj in ("api_context.o", "api_timing.o", "api_ops.o", "api_pipeline.o", "api_slab.o", "kernels_volume.o", "kernels_extrema.o", "kernels_blur_fused.o", "kernels_keypoint.o", "gauss_taps.o"):
+    for obj in ("api_context.o", "api_timing.o", "api_ops.o", "api_pipeline.o", "api_slab.o", "kernels_volume.o", "kernels_extrema.o", "kernels_blur_fused.o", "kernels_keypoint.o", "kernels_descriptor.o", "gauss_taps.o"):
         nm = subprocess.run(["nm", "--undefined-only", os.path.join(csrc, "_build", obj)], capture_output=True, text=True)
         assert nm.returncode == 0 and "getenv" not in nm.stdout, obj
 
