@@ -38,6 +38,7 @@ FEATFUSE = os.path.join(CSRC, "_build", "featFuse")
 FEATOVERLAP = os.path.join(CSRC, "_build", "featOverlap")
 FEATCLEAN = os.path.join(CSRC, "_build", "featClean")
 FEATCOMPARE = os.path.join(CSRC, "_build", "featCompare")
+FEATREGISTER = os.path.join(CSRC, "_build", "featRegister")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 7   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -201,6 +202,8 @@ def hip_lib():
     _sig(L.sift3d_clean_labels, I, P, I64, I64, I64, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_joint_histogram, I, I, P, P, I64, I64, I64, P, P, C.c_int32, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_image_similarity, I, P, P, P, I64, I64, I64, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_warp_histogram, I, I, P, I64, I64, I64, P, I64, I64, I64, P, C.c_int32, C.c_int32, P, P, C.c_int32, C.c_int32, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_register_affine, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -285,6 +288,13 @@ def host_lib():
     _sig(L.sift3d_similarity_measures, I, P, C.c_int32, P, F, F, C.c_int32, P)
     _sig(L.sift3d_similarity_label_measures, None, C.c_int32, P, F, F, C.c_int32, P)
     _sig(L.sift3d_similarity_report_text, I64, P, P, C.c_int32, C.c_char_p, I64)
+    _sig(L.sift3d_register_defaults, None, P)
+    _sig(L.sift3d_register_check, I, P, C.c_char_p, I64)
+    _sig(L.sift3d_register_map, I, P, I64, I64, I64, P, P, P, P)
+    _sig(L.sift3d_register_result, I, P, I64, I64, I64, P, P, P)
+    _sig(L.sift3d_register_candidates, I, P, C.c_int32, C.c_double, C.c_double, P)
+    _sig(L.sift3d_register_lattice, I64, I64, I64, I64, C.c_int32, P, P, P, P)
+    _sig(L.sift3d_register_report_text, I64, P, C.c_char_p, I64)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -1764,6 +1774,167 @@ def image_similarity(a, b, labels=None, **params):
     n = C.c_int32(0)
     _call("sift3d_image_similarity", a.ctypes.data, b.ctypes.data, _ptr(lb), nx, ny, nz, C.byref(p), C.byref(rec), lrec, C.byref(n))
     return _image_similarity_dict(rec, None if lb is None else (SimilarityLabelRecord * n.value)(*lrec[:n.value]))
+
+
+# ---- affine registration by mutual information (featRegister), DESIGN.md section 7q -------------------------------------------------
+REGISTER_MAX_MAPS, REGISTER_MAX_LEVELS, REGISTER_THETA = 32, 4, 12
+REGISTER_METRICS = {"mi": 0, "nmi": 1}
+REGISTER_FORMS = {"default": -1, "by_brick": 0, "by_map": 1, "by_brick_plane": 2, "by_map_plane": 3}
+
+
+class RegisterParams(C.Structure):
+    """sift3d_register_params"""
+    _fields_ = [("dof", C.c_int32), ("metric", C.c_int32), ("bins", C.c_int32), ("n_levels", C.c_int32), ("stride", C.c_int32 * REGISTER_MAX_LEVELS),
+                ("max_iterations", C.c_int32), ("device", C.c_int32), ("form", C.c_int32), ("reserved", C.c_int32),
+                ("first_step", C.c_double * REGISTER_MAX_LEVELS), ("last_step", C.c_double * REGISTER_MAX_LEVELS), ("min_overlap", C.c_double)]
+
+
+class RegisterLevel(C.Structure):
+    """sift3d_register_level"""
+    _fields_ = [("stride", C.c_int32), ("iterations", C.c_int32), ("evaluations", C.c_int32), ("stop", C.c_int32), ("n_lattice", C.c_int64),
+                ("score_in", C.c_double), ("score_out", C.c_double), ("last_step", C.c_double), ("device_ms", C.c_double)]
+
+
+class RegisterReport(C.Structure):
+    """sift3d_register_report"""
+    _fields_ = [("dof", C.c_int32), ("metric", C.c_int32), ("bins", C.c_int32), ("n_levels", C.c_int32), ("stop", C.c_int32), ("reserved", C.c_int32),
+                ("h", C.c_double), ("rho", C.c_double), ("theta", C.c_double * REGISTER_THETA), ("result", C.c_float * 16), ("map", C.c_float * 12),
+                ("reserved2", C.c_float * 4), ("level", RegisterLevel * REGISTER_MAX_LEVELS), ("outside_before", C.c_int64), ("outside_after", C.c_int64),
+                ("before", SimilarityRecord), ("after", SimilarityRecord)]
+
+
+def register_params(**kw):
+    """sift3d_register_defaults, then the given fields: dof, metric (0 / "mi", 1 / "nmi"), bins, max_iterations, device, min_overlap, form
+    (a key of REGISTER_FORMS or its number), and levels = [(stride, first_step, last_step), ...] with the steps in multiples of h"""
+    p = RegisterParams()
+    host_lib().sift3d_register_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k == "levels":
+            p.n_levels = len(v)
+            for l, (s, a, b) in enumerate(v[:REGISTER_MAX_LEVELS]):
+                p.stride[l], p.first_step[l], p.last_step[l] = int(s), float(a), float(b)
+        elif k == "min_overlap":
+            p.min_overlap = float(v)
+        elif k in ("dof", "bins", "max_iterations", "device", "n_levels"):
+            setattr(p, k, int(v))
+        elif k == "metric":
+            p.metric = int(REGISTER_METRICS.get(v, v))
+        elif k == "form":
+            p.form = int(REGISTER_FORMS.get(v, v))
+        else:
+            raise ValueError("no registration parameter %s" % k)
+    return p
+
+
+def register_check(p):
+    """sift3d_register_check: None, or the text with which the parameters are refused"""
+    err = C.create_string_buffer(512)
+    return None if host_lib().sift3d_register_check(C.byref(p), err, len(err)) == 0 else err.value.decode()
+
+
+def _theta(theta):
+    t = np.ascontiguousarray(theta, np.float64)
+    if t.size != REGISTER_THETA:
+        raise ValueError("theta is 12 numbers: t, r, s, g")
+    return t.reshape(REGISTER_THETA)
+
+
+def register_map(theta, shape, fixed_vox2key=None, moving_vox2key=None, initial=None):
+    """sift3d_register_map: the 3 x 4 float32 map fixed voxel -> moving voxel of theta for a fixed image of shape (nz, ny, nx)"""
+    t, (nz, ny, nx) = _theta(theta), (int(d) for d in shape)
+    fv, mv, m0 = _m16(fixed_vox2key), _m16(moving_vox2key), _m16(initial)
+    out = np.zeros(12, np.float32)
+    if host_lib().sift3d_register_map(t.ctypes.data, nx, ny, nz, _ptr(fv), _ptr(mv), _ptr(m0), out.ctypes.data) != 0:
+        raise Sift3DError("sift3d_register_map: a matrix is singular, not finite or its last row is not 0 0 0 1")
+    return out.reshape(3, 4)
+
+
+def register_result(theta, shape, fixed_vox2key=None, initial=None):
+    """sift3d_register_result: the 4 x 4 float32 moving -> fixed matrix M1 = inv(D(theta)) . M0"""
+    t, (nz, ny, nx) = _theta(theta), (int(d) for d in shape)
+    fv, m0 = _m16(fixed_vox2key), _m16(initial)
+    out = np.zeros(16, np.float32)
+    if host_lib().sift3d_register_result(t.ctypes.data, nx, ny, nz, _ptr(fv), _ptr(m0), out.ctypes.data) != 0:
+        raise Sift3DError("sift3d_register_result: a matrix is singular, not finite or its last row is not 0 0 0 1")
+    return out.reshape(4, 4)
+
+
+def register_candidates(theta, dof, u, rho):
+    """sift3d_register_candidates: (2 active parameters) x 12 float64, + before -"""
+    t, out = _theta(theta), np.zeros((2 * REGISTER_THETA, REGISTER_THETA), np.float64)
+    n = host_lib().sift3d_register_candidates(t.ctypes.data, int(dof), float(u), float(rho), out.ctypes.data)
+    if n < 0:
+        raise Sift3DError("sift3d_register_candidates: dof = %d is not 3, 6, 7, 9 or 12" % int(dof))
+    return out[:n].copy()
+
+
+def register_lattice(shape, stride, fixed_vox2key=None):
+    """sift3d_register_lattice of a fixed image of shape (nz, ny, nx): (N, points per axis (x, y, z), h, rho)"""
+    nz, ny, nx = (int(d) for d in shape)
+    fv, n, h, rho = _m16(fixed_vox2key), (C.c_int64 * 3)(), C.c_double(0), C.c_double(0)
+    N = host_lib().sift3d_register_lattice(nx, ny, nz, int(stride), _ptr(fv), n, C.byref(h), C.byref(rho))
+    if N < 0:
+        raise Sift3DError("sift3d_register_lattice: an extent below 1, a stride other than 1, 2, 4, 8 or a degenerate vox2key")
+    return int(N), tuple(int(v) for v in n), h.value, rho.value
+
+
+def warp_histogram(fixed, moving, maps, fixed_range, moving_range, stride=1, bins=64, form="default", device=0, return_ms=False):
+    """sift3d_warp_histogram: the joint histograms of fixed (nz, ny, nx) and moving (mz, my, mx) under K maps (K x 3 x 4, fixed voxel ->
+    moving voxel) on the lattice of the stride: (hist int64 K x bins x bins, sums K lists of six Python integers, excluded K, outside K).
+    return_ms=True appends kernel_ms."""
+    f, m = _f32(fixed), _f32(moving)
+    if f.ndim != 3 or m.ndim != 3:
+        raise ValueError("the images are (nz, ny, nx)")
+    a = np.ascontiguousarray(maps, np.float32)
+    if a.size % 12:
+        raise ValueError("a map is 3 x 4 floats")
+    a = a.reshape(-1, 12)
+    K, bins = len(a), int(bins)
+    (nz, ny, nx), (mz, my, mx) = f.shape, m.shape
+    hist, sums = np.zeros((K, max(bins, 0), max(bins, 0)), np.int64), np.zeros((K, len(SIMILARITY_SUMS)), np.int64)
+    excluded, outside, ms = np.zeros(K, np.int64), np.zeros(K, np.int64), C.c_double(0.0)
+    fr, mr = (C.c_float * 2)(*[float(v) for v in fixed_range]), (C.c_float * 2)(*[float(v) for v in moving_range])
+    _call("sift3d_warp_histogram", int(device), f.ctypes.data, nx, ny, nz, m.ctypes.data, mx, my, mz, a.ctypes.data, K, int(stride), fr, mr, bins,
+          int(REGISTER_FORMS.get(form, form)), hist.ctypes.data, sums.ctypes.data, excluded.ctypes.data, outside.ctypes.data, C.byref(ms))
+    out = (hist, [[int(v) for v in row] for row in sums], [int(v) for v in excluded], [int(v) for v in outside])
+    return out + (ms.value,) if return_ms else out
+
+
+def _register_report_dict(r):
+    d = {"dof": int(r.dof), "metric": int(r.metric), "bins": int(r.bins), "stop": int(r.stop), "h": float(r.h), "rho": float(r.rho),
+         "theta": np.array(r.theta[:], np.float64), "result": np.array(r.result[:], np.float32).reshape(4, 4), "map": np.array(r.map[:], np.float32).reshape(3, 4),
+         "levels": [{k: (float if k in ("score_in", "score_out", "last_step", "device_ms") else int)(getattr(v, k)) for k, _ in RegisterLevel._fields_}
+                    for v in r.level[:r.n_levels]],
+         "outside_before": int(r.outside_before), "outside_after": int(r.outside_after), "before": _image_similarity_dict(r.before, None),
+         "after": _image_similarity_dict(r.after, None), "struct": r}
+    return d
+
+
+def register_affine(fixed, moving, fixed_vox2key=None, moving_vox2key=None, initial=None, **params):
+    """sift3d_register_affine: the affine alignment of moving (mz, my, mx) to fixed (nz, ny, nx) by mutual information.  A dict: theta
+    (12 float64), result (M1, 4 x 4 float32, moving keys -> fixed keys: write_matrix's input), map, levels (one dict per level), stop,
+    before and after (image_similarity's dicts on the whole lattice under theta = 0 and theta*), outside_before, outside_after.
+    params: fields of register_params."""
+    f, m = _f32(fixed), _f32(moving)
+    if f.ndim != 3 or m.ndim != 3:
+        raise ValueError("the images are (nz, ny, nx)")
+    (nz, ny, nx), (mz, my, mx) = f.shape, m.shape
+    fv, mv, m0 = _m16(fixed_vox2key), _m16(moving_vox2key), _m16(initial)
+    p, rep = register_params(**params), RegisterReport()
+    _call("sift3d_register_affine", f.ctypes.data, nx, ny, nz, m.ctypes.data, mx, my, mz, _ptr(fv), _ptr(mv), _ptr(m0), C.byref(p), C.byref(rep))
+    return _register_report_dict(rep)
+
+
+def register_report_text(report):
+    """sift3d_register_report_text of what register_affine returned (or of a RegisterReport)"""
+    r = report["struct"] if isinstance(report, dict) else report
+    need = host_lib().sift3d_register_report_text(C.byref(r), None, 0)
+    if need < 0:
+        raise Sift3DError("sift3d_register_report_text -> %d" % need)
+    buf = C.create_string_buffer(need + 1)
+    if host_lib().sift3d_register_report_text(C.byref(r), buf, len(buf)) != need:
+        raise Sift3DError("sift3d_register_report_text: the length changed")
+    return buf.value.decode()
 
 
 def _map12(m):

@@ -1448,6 +1448,120 @@ void sift3d_similarity_label_measures(int32_t label, const int64_t *sums, float 
 int64_t sift3d_similarity_report_text(const sift3d_similarity_record *record, const sift3d_similarity_label_record *label_records,
                                       int32_t n_labels, char *buf, int64_t len);
 
+/* ---- affine registration by mutual information (featRegister; beyond the reference) ---------------------------------------------
+ * DESIGN.md section 7q states the contract; tests/register_oracle.c restates it serially.  The GPU makes counts and integer sums
+ * only; every score and every matrix is host arithmetic in double (register_host.c, similarity_host.c).
+ *
+ * The kernel's contract (sift3d_warp_histogram).  F: nx ny nz floats, M: mx my mz floats, x fastest; every extent 1 .. 4096, at
+ * most 2^30 voxels each; bins 8, 16, 32 or 64; stride s 1, 2, 4 or 8; K = 1 .. SIFT3D_REGISTER_MAX_MAPS maps of 12 floats each,
+ * fixed voxel -> moving voxel, exactly the map of sift3d_resample_affine; two ranges (lo, hi), finite with hi > lo.
+ * Lattice: the fixed voxels (a s, b s, c s) with a s < nx, b s < ny, c s < nz; N is their number.
+ * Per lattice voxel p and map k: q = map p in section 7c's order; v = the linear sample of M at q with fill = NaN (all eight
+ * corners read and weighed, so a non-finite corner of weight 0 reaches v); qA = q(F[p]) with F's range, qB = q(v) with M's range
+ * (section 7f's q).  The voxel counts when qA >= 0 and qB >= 0.
+ * Per map: hist[i bins + j] (int64) and the six sums of the section above over the counted voxels; excluded = N - n; outside = the
+ * lattice voxels whose q fails the sampler's inside test 0 <= q <= extent - 1 (a NaN q included), so outside <= excluded.
+ *
+ * The transform family.  theta = (t[3], r[3], s[3], g[3]), 12 doubles, acts in fixed key space about c = fixed_vox2key .
+ * ((nx - 1) / 2, (ny - 1) / 2, (nz - 1) / 2):  D(y) = c + L (y - c) + t,  L = (R(r) . G(g)) . diag(exp s), R Rodrigues' formula on
+ * the rotation vector r (the identity at |r| = 0: a = sqrt((r0 r0 + r1 r1) + r2 r2), R = I + (sin a / a) K + ((1 - cos a) / (a a))
+ * (K K), K the cross-product matrix of r), G unit upper triangular with g = (g_xy, g_xz, g_yz).  The map of theta is A =
+ * inv(moving_vox2key) . (inv(M0) . (D . fixed_vox2key)), with the inverses as sift3d_resample_map takes them, rounded to float
+ * once; M0 is the initial moving -> fixed matrix (NULL: identity).  The result is M1 = inv(D) . M0, rounded to float once, a
+ * moving -> fixed matrix like M0: sift3d_write_matrix writes it and featResample, featFuse and featCompose read it.
+ * dof: 3 = t; 6 = t, r; 7 = t, r and one scale shared by s0 = s1 = s2; 9 = t, r, s; 12 = all.
+ * Units: h = the fixed image's smallest voxel edge in key units (the least column norm of fixed_vox2key's 3 x 3 part); rho = half
+ * the largest key-space edge (n - 1) |column| of the fixed volume (h / 2 for a single voxel).  A step u moves t by u and r, s, g
+ * by u / rho.
+ * Search: up to SIFT3D_REGISTER_MAX_LEVELS levels of (stride, first step, last step), steps in multiples of h.  One iteration
+ * scores, in ONE launch, theta + step and then theta - step for every active parameter in the order t, r, s, g (2 dof maps).  The
+ * score is mi or nmi of sift3d_similarity_measures from the map's integers.  A candidate is admissible when its score is not NaN
+ * and (double)n >= min_overlap (double)N.  The best admissible candidate (greatest score, ties to the lowest index) is moved to
+ * when its score is strictly greater than the current one; otherwise the step is halved.  A level ends when the step falls below
+ * its last step, or after max_iterations iterations (recorded in stop).  The next level re-scores theta on its own lattice first.
+ * No smoothing and no pyramid: a level is a lattice stride and nothing else. */
+#define SIFT3D_REGISTER_MAX_MAPS 32
+#define SIFT3D_REGISTER_MAX_LEVELS 4
+#define SIFT3D_REGISTER_THETA 12
+#define SIFT3D_REGISTER_METRIC_MI 0
+#define SIFT3D_REGISTER_METRIC_NMI 1
+/* sift3d_warp_histogram's form: SIFT3D_REGISTER_FORM_DEFAULT, or a sum of the bits below.  Every form gives the same integers */
+#define SIFT3D_REGISTER_FORM_DEFAULT (-1)
+#define SIFT3D_REGISTER_FORM_BY_MAP 1 /* workgroups ordered by map; without it the maps of one brick run side by side on one XCD */
+#define SIFT3D_REGISTER_FORM_PLANE 2  /* F quantised once into an int16 lattice plane; without it F is read and quantised per map */
+
+typedef struct {
+    int32_t dof;            /* 12; or 3, 6, 7, 9 */
+    int32_t metric;         /* SIFT3D_REGISTER_METRIC_NMI; or _MI */
+    int32_t bins;           /* 32; or 8, 16, 64 */
+    int32_t n_levels;       /* 3; 1 .. SIFT3D_REGISTER_MAX_LEVELS */
+    int32_t stride[SIFT3D_REGISTER_MAX_LEVELS];    /* 4, 2, 1; each 1, 2, 4 or 8 */
+    int32_t max_iterations; /* 200, per level; at least 1 */
+    int32_t device;         /* 0 */
+    int32_t form;           /* SIFT3D_REGISTER_FORM_DEFAULT */
+    int32_t reserved;
+    double first_step[SIFT3D_REGISTER_MAX_LEVELS]; /* 4, 1, 1/4: multiples of h; finite, > 0 */
+    double last_step[SIFT3D_REGISTER_MAX_LEVELS];  /* 1, 1/4, 1/16: > 0 and <= first_step */
+    double min_overlap;     /* 0.25; 0 .. 1 */
+} sift3d_register_params;
+
+typedef struct {
+    int32_t stride, iterations, evaluations;
+    int32_t stop;           /* 0: the step fell below the last step; 1: max_iterations */
+    int64_t n_lattice;      /* N */
+    double score_in, score_out, last_step /* key units */, device_ms;
+} sift3d_register_level;
+
+typedef struct {
+    int32_t dof, metric, bins, n_levels;
+    int32_t stop;           /* 0, or 1 where a level stopped at max_iterations */
+    int32_t reserved;
+    double h, rho;
+    double theta[SIFT3D_REGISTER_THETA]; /* theta* */
+    float result[16];       /* M1 */
+    float map[12];          /* A(theta*) */
+    float reserved2[4];
+    sift3d_register_level level[SIFT3D_REGISTER_MAX_LEVELS];
+    int64_t outside_before, outside_after;
+    sift3d_similarity_record before, after; /* the whole lattice (stride 1) under theta = 0 and under theta*, one K = 2 launch */
+} sift3d_register_report;
+
+/* K joint histograms under K maps, host arrays in and out: hist n_maps bins^2 int64, sums n_maps SIFT3D_SIMILARITY_SUMS int64,
+ * excluded and outside n_maps int64 each; kernel_ms may be NULL.  SIFT3D_ERR_ARG with text naming the argument, before anything is
+ * allocated: a null pointer, an extent outside 1 .. 4096 or more than 2^30 voxels (either image), bins, stride, n_maps, a range,
+ * a form that is neither the default nor a sum of its bits. */
+int sift3d_warp_histogram(int device, const float *fixed, int64_t nx, int64_t ny, int64_t nz, const float *moving, int64_t mx, int64_t my,
+                          int64_t mz, const float *maps, int32_t n_maps, int32_t stride, const float fixed_range[2], const float moving_range[2],
+                          int32_t bins, int32_t form, int64_t *hist, int64_t *sums, int64_t *excluded, int64_t *outside, double *kernel_ms, char *err,
+                          int64_t err_len);
+/* The search.  vox2key, initial: 4 x 4 row-major, NULL: identity; p NULL: defaults.  Each image's range is its own
+ * (sift3d_blockmatch_range).  SIFT3D_ERR_ARG with text, before anything is allocated: a null pointer, extents, what
+ * sift3d_register_check refuses, a matrix sift3d_register_map refuses at theta = 0, an image without two distinct finite values;
+ * and, before anything further is allocated, a start that is inadmissible at the first level (n and N in the text). */
+int sift3d_register_affine(const float *fixed, int64_t nx, int64_t ny, int64_t nz, const float *moving, int64_t mx, int64_t my, int64_t mz,
+                           const float fixed_vox2key[16], const float moving_vox2key[16], const float initial[16], const sift3d_register_params *p,
+                           sift3d_register_report *report, char *err, int64_t err_len);
+/* Host helpers (also in libsift3d_host.so). */
+void sift3d_register_defaults(sift3d_register_params *p);
+/* 0, or -1 and into err which field is refused, with its value */
+int sift3d_register_check(const sift3d_register_params *p, char *err, int64_t err_len);
+/* A(theta) into map; 0, or -1 where a matrix's last row is not 0 0 0 1, a matrix is singular or an entry of the map is not finite */
+int sift3d_register_map(const double theta[SIFT3D_REGISTER_THETA], int64_t nx, int64_t ny, int64_t nz, const float fixed_vox2key[16],
+                        const float moving_vox2key[16], const float initial[16], float map[12]);
+/* M1(theta) into result; 0 or -1 likewise */
+int sift3d_register_result(const double theta[SIFT3D_REGISTER_THETA], int64_t nx, int64_t ny, int64_t nz, const float fixed_vox2key[16],
+                           const float initial[16], float result[16]);
+/* The candidates of one iteration around theta at step u (key units): 2 active parameters x SIFT3D_REGISTER_THETA doubles into
+ * cand, + before -.  Returns their number, or -1 for a dof other than 3, 6, 7, 9, 12. */
+int sift3d_register_candidates(const double theta[SIFT3D_REGISTER_THETA], int32_t dof, double u, double rho, double *cand);
+/* The lattice of a stride: the points per axis into n, h and rho of the fixed image (each may be NULL); returns N, or -1 for an
+ * extent below 1, a stride other than 1, 2, 4, 8 or a vox2key whose 3 x 3 part has a column that is zero or not finite */
+int64_t sift3d_register_lattice(int64_t nx, int64_t ny, int64_t nz, int32_t stride, const float fixed_vox2key[16], int64_t n[3], double *h,
+                                double *rho);
+/* The report as text: a header, one line per level, theta*, M1 and the two records' "n excluded outside mi nmi rho".  Returns the
+ * length the whole text needs, as snprintf does; buf holds at most len - 1 characters of it.  4096 bytes hold every report. */
+int64_t sift3d_register_report_text(const sift3d_register_report *report, char *buf, int64_t len);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
