@@ -39,6 +39,7 @@ FEATOVERLAP = os.path.join(CSRC, "_build", "featOverlap")
 FEATCLEAN = os.path.join(CSRC, "_build", "featClean")
 FEATCOMPARE = os.path.join(CSRC, "_build", "featCompare")
 FEATREGISTER = os.path.join(CSRC, "_build", "featRegister")
+FEATAVERAGE = os.path.join(CSRC, "_build", "featAverage")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 7   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -204,6 +205,7 @@ def hip_lib():
     _sig(L.sift3d_image_similarity, I, P, P, P, I64, I64, I64, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_warp_histogram, I, I, P, I64, I64, I64, P, I64, I64, I64, P, C.c_int32, C.c_int32, P, P, C.c_int32, C.c_int32, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_register_affine, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_average_warped, I, I64, I64, I64, P, C.c_int32, P, P, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -295,6 +297,11 @@ def host_lib():
     _sig(L.sift3d_register_candidates, I, P, C.c_int32, C.c_double, C.c_double, P)
     _sig(L.sift3d_register_lattice, I64, I64, I64, I64, C.c_int32, P, P, P, P)
     _sig(L.sift3d_register_report_text, I64, P, C.c_char_p, I64)
+    _sig(L.sift3d_average_defaults, None, P)
+    _sig(L.sift3d_average_check, I, P, C.c_int32, C.c_char_p, I64)
+    _sig(L.sift3d_average_counts, I, P, I64, C.c_int32, C.c_int32, C.c_int32, P)
+    _sig(L.sift3d_average_report_text, I64, P, C.c_char_p, I64)
+    _sig(L.sift3d_mean_field, I, C.c_int32, P, P, C.c_char_p, I64)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -1935,6 +1942,134 @@ def register_report_text(report):
     if host_lib().sift3d_register_report_text(C.byref(r), buf, len(buf)) != need:
         raise Sift3DError("sift3d_register_report_text: the length changed")
     return buf.value.decode()
+
+
+# ---- a template from up to 32 warped images (featAverage), DESIGN.md section 7r -----------------------------------------------------
+AVERAGE_MAX_IMAGES, AVERAGE_MAX_TRIM = 32, 15
+AVERAGE_FORMS = {"default": -1, "column": 0}
+AVERAGE_MODES = {"mean": 0, "median": AVERAGE_MAX_TRIM}
+
+
+class AverageParams(C.Structure):
+    """sift3d_average_params"""
+    _fields_ = [("trim", C.c_int32), ("min_count", C.c_int32), ("fill", C.c_float), ("device", C.c_int32), ("max_voxels", C.c_int64), ("form", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class AverageImage(C.Structure):
+    """sift3d_average_image"""
+    _fields_ = [("image", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("vox2key", C.c_void_p), ("moving_to_fixed", C.c_void_p),
+                ("field", C.c_void_p)]
+
+
+class AverageImageReport(C.Structure):
+    """sift3d_average_image_report"""
+    _fields_ = [("contributing", C.c_int64), ("upload_ms", C.c_double)]
+
+
+class AverageReport(C.Structure):
+    """sift3d_average_report"""
+    _fields_ = [("images", C.c_int32), ("trim", C.c_int32), ("min_count", C.c_int32), ("reserved", C.c_int32), ("voxels", C.c_int64), ("none", C.c_int64),
+                ("below", C.c_int64), ("count", C.c_int64 * (AVERAGE_MAX_IMAGES + 1)), ("kernel_ms", C.c_double), ("wall_ms", C.c_double),
+                ("image", AverageImageReport * AVERAGE_MAX_IMAGES)]
+
+
+def average_params(**kw):
+    """sift3d_average_defaults, then the given fields: trim (0 .. 15, or "mean" / "median"), min_count, fill, device, max_voxels, form (a
+    key of AVERAGE_FORMS or its number)"""
+    p = AverageParams()
+    host_lib().sift3d_average_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k == "trim":
+            p.trim = int(AVERAGE_MODES.get(v, v))
+        elif k == "form":
+            p.form = int(AVERAGE_FORMS.get(v, v))
+        elif k == "fill":
+            p.fill = float(v)
+        elif k in ("min_count", "device", "max_voxels"):
+            setattr(p, k, int(v))
+        else:
+            raise ValueError("no averaging parameter %s" % k)
+    return p
+
+
+def average_check(p, K):
+    """sift3d_average_check: None, or the text with which the parameters are refused for K images"""
+    err = C.create_string_buffer(512)
+    return None if host_lib().sift3d_average_check(C.byref(p), int(K), err, len(err)) == 0 else err.value.decode()
+
+
+def _average_report_dict(r):
+    K = int(r.images)
+    return {"images": K, "trim": int(r.trim), "min_count": int(r.min_count), "voxels": int(r.voxels), "none": int(r.none), "below": int(r.below),
+            "count": [int(v) for v in r.count[:K + 1]], "kernel_ms": float(r.kernel_ms), "wall_ms": float(r.wall_ms),
+            "image": [{"contributing": int(r.image[k].contributing), "upload_ms": float(r.image[k].upload_ms)} for k in range(K)], "struct": r}
+
+
+def average_counts(mask, K, trim=0, min_count=1):
+    """sift3d_average_counts: the report's counts (a dict as average_warped's report, the times 0) from a mask plane"""
+    m = np.ascontiguousarray(mask, np.uint32)
+    rep = AverageReport()
+    if host_lib().sift3d_average_counts(m.ctypes.data, m.size, int(K), int(trim), int(min_count), C.byref(rep)) != 0:
+        raise Sift3DError("sift3d_average_counts: K outside 1 .. 32, or the mask holds a bit at or above K")
+    return _average_report_dict(rep)
+
+
+def average_report_text(report):
+    """sift3d_average_report_text of what average_warped returned as its report (or of an AverageReport)"""
+    r = report["struct"] if isinstance(report, dict) else report
+    need = host_lib().sift3d_average_report_text(C.byref(r), None, 0)
+    if need < 0:
+        raise Sift3DError("sift3d_average_report_text -> %d" % need)
+    buf = C.create_string_buffer(need + 1)
+    if host_lib().sift3d_average_report_text(C.byref(r), buf, len(buf)) != need:
+        raise Sift3DError("sift3d_average_report_text: the length changed")
+    return buf.value.decode()
+
+
+def mean_field(fields):
+    """sift3d_mean_field: the node-wise mean of field dicts on one node grid, a field dict.  Raises where a grid differs."""
+    K = len(fields)
+    arr, keep = (Field * max(K, 1))(), []
+    for k, d in enumerate(fields):
+        f, disp = _field_struct(d)
+        keep.append(disp)
+        arr[k] = f
+    out, err = Field(), C.create_string_buffer(512)
+    rc = host_lib().sift3d_mean_field(K, arr, C.byref(out), err, len(err))
+    if rc == -4:
+        disp = np.zeros(3 * int(out.n[0]) * int(out.n[1]) * int(out.n[2]), np.float32)
+        out.capacity, out.disp = disp.size, disp.ctypes.data
+        rc = host_lib().sift3d_mean_field(K, arr, C.byref(out), err, len(err))
+    if rc != 0:
+        e = Sift3DError("sift3d_mean_field -> %d: %s" % (rc, err.value.decode(errors="replace")))
+        e.code = rc
+        raise e
+    return _field_dict(out, disp)
+
+
+def average_warped(shape, images, grid_vox2key=None, **params):
+    """sift3d_average_warped: the template of K images on the grid of shape (nz, ny, nx).  images: dicts with image ((nz, ny, nx) float32)
+    and optionally t (the image's moving -> fixed key transform against the grid, 4 x 4; None: identity), vox2key (4 x 4) and field (a
+    field dict); params: fields of average_params.  Returns (avg float32, var float32, mask uint32, report dict), the planes (nz, ny, nx)."""
+    nz, ny, nx = (int(d) for d in shape)
+    K = len(images)
+    arr, keep = (AverageImage * max(K, 1))(), []
+    for k, a in enumerate(images):
+        im = _f32(a["image"])
+        if im.ndim != 3:
+            raise ValueError("image %d is not (nz, ny, nx)" % k)
+        mv, tm = _m16(a.get("vox2key")), _m16(a.get("t"))
+        fs, disp = _field_struct(a["field"]) if a.get("field") is not None else (None, None)
+        keep.append((im, mv, tm, fs, disp))
+        arr[k].image = im.ctypes.data
+        arr[k].nz, arr[k].ny, arr[k].nx = im.shape
+        arr[k].vox2key, arr[k].moving_to_fixed = _ptr(mv), _ptr(tm)
+        arr[k].field = C.addressof(fs) if fs is not None else None
+    avg, var, mask = (np.zeros((max(nz, 0), max(ny, 0), max(nx, 0)), t) for t in (np.float32, np.float32, np.uint32))
+    p, rep = average_params(**params), AverageReport()
+    _call("sift3d_average_warped", nx, ny, nz, _ptr(_m16(grid_vox2key)), K, arr, C.byref(p), avg.ctypes.data, var.ctypes.data, mask.ctypes.data, C.byref(rep))
+    return avg, var, mask, _average_report_dict(rep)
 
 
 def _map12(m):

@@ -1562,6 +1562,87 @@ int64_t sift3d_register_lattice(int64_t nx, int64_t ny, int64_t nz, int32_t stri
  * length the whole text needs, as snprintf does; buf holds at most len - 1 characters of it.  4096 bytes hold every report. */
 int64_t sift3d_register_report_text(const sift3d_register_report *report, char *buf, int64_t len);
 
+/* ---- a template from up to 32 warped images (featAverage; beyond the reference) ---------------------------------------------------
+ * DESIGN.md section 7r states the contract; tests/average_oracle.c restates it serially.  One launch samples all K images at every
+ * voxel of the output grid and writes three planes; no warped volume is written.
+ *
+ * The output grid: nx ny nz voxels (each extent 1 .. 2^24, at most 2^40 voxels, x fastest) with grid_vox2key (NULL: identity).  Image
+ * k is a moving image in featResample's roles: its map is sift3d_resample_map(moving_to_fixed, grid_vox2key, vox2key), its field
+ * terms sift3d_field_warp_terms(grid_vox2key, vox2key).
+ * Per grid voxel x and image k, v_k is the image sampled linearly with fill NaN: with a field sift3d_resample_field's arithmetic,
+ * without one sift3d_resample_affine's, bit for bit.  Image k contributes iff v_k is finite; n is the number of contributors and
+ * mask has bit k set iff image k contributes.
+ * Mean and variance, in double: S = sum of (double)v_k over the contributors in image order; m = S / (double)n; V = sum of
+ * ((double)v_k - m)^2 in image order; var = (float)(V / (double)(n - 1)), 0 for n = 1.  No square root is taken.  Every sum starts
+ * from +0.
+ * Average: trim = 0: avg = (float)m.  trim = t > 0: the contributors are ranked by value, equal values (-0 == 0) by image index:
+ * rank_k = #{j : v_j < v_k, or v_j == v_k and j < k}; t_eff = min(t, (n - 1) / 2) (integer division); avg = (float)(the sum of
+ * (double)v over the ranks t_eff .. n - 1 - t_eff, added in rank order, / (double)(n - 2 t_eff)).  t = 15 is the median for every
+ * n <= 32: the middle value for odd n, the mean of the middle two for even n.
+ * Short voxels: where n < min_count, avg and var are fill; mask is kept. */
+#define SIFT3D_AVERAGE_MAX_IMAGES 32
+#define SIFT3D_AVERAGE_MAX_TRIM 15
+#define SIFT3D_AVERAGE_FORM_DEFAULT (-1)
+#define SIFT3D_AVERAGE_FORM_COLUMN 0 /* the one form built: a lane keeps its K samples in its own LDS column */
+
+typedef struct {
+    int32_t trim;       /* 0; 0 .. SIFT3D_AVERAGE_MAX_TRIM */
+    int32_t min_count;  /* 1; 1 .. K */
+    float fill;         /* NaN */
+    int32_t device;     /* 0 */
+    int64_t max_voxels; /* 2^32: the sum of all source voxels; a call above it is refused */
+    int32_t form;       /* SIFT3D_AVERAGE_FORM_DEFAULT */
+    int32_t reserved;
+} sift3d_average_params;
+
+typedef struct {
+    const float *image;           /* nx ny nz floats, x fastest */
+    int64_t nx, ny, nz;           /* 1 .. 2^24 */
+    const float *vox2key;         /* 16 floats; NULL: identity */
+    const float *moving_to_fixed; /* 16 floats: the image's .trans.txt against the grid; NULL: identity */
+    const sift3d_field *field;    /* NULL: none */
+} sift3d_average_image;
+
+typedef struct {
+    int64_t contributing; /* grid voxels where the image contributes (from mask, exact) */
+    double upload_ms;     /* device time of the image's copy (and its field's) to the device */
+} sift3d_average_image_report;
+
+typedef struct {
+    int32_t images, trim, min_count, reserved;
+    int64_t voxels;                                  /* nx ny nz */
+    int64_t none;                                    /* voxels with n = 0 */
+    int64_t below;                                   /* voxels with n < min_count (those with n = 0 included) */
+    int64_t count[SIFT3D_AVERAGE_MAX_IMAGES + 1];    /* count[n]: voxels with n contributors */
+    double kernel_ms, wall_ms;                       /* device time of the launch; host time of the whole call */
+    sift3d_average_image_report image[SIFT3D_AVERAGE_MAX_IMAGES];
+} sift3d_average_report;
+
+/* The stage.  Every image goes to the device once and stays for the one launch.  avg, var: nx ny nz floats; mask: nx ny nz uint32;
+ * p NULL: defaults; report may be NULL.  SIFT3D_ERR_ARG with text naming the argument and the image, before anything is allocated: a
+ * null pointer, K outside 1 .. 32, a grid extent outside 1 .. 2^24 or more than 2^40 grid voxels, what sift3d_average_check refuses,
+ * an image extent outside 1 .. 2^24, a field that sift3d_resample_field refuses, a matrix that sift3d_resample_map refuses, source
+ * voxels above max_voxels. */
+int sift3d_average_warped(int64_t nx, int64_t ny, int64_t nz, const float grid_vox2key[16], int32_t K, const sift3d_average_image *images,
+                          const sift3d_average_params *p, float *avg, float *var, uint32_t *mask, sift3d_average_report *report, char *err,
+                          int64_t err_len);
+/* Host helpers (also in libsift3d_host.so). */
+void sift3d_average_defaults(sift3d_average_params *p);
+/* 0, or -1 and into err which field is refused, with its value: trim, min_count (against K), max_voxels, form */
+int sift3d_average_check(const sift3d_average_params *p, int32_t K, char *err, int64_t err_len);
+/* The report's counts from the mask plane (n words): images, trim, min_count, voxels, none, below, count[] and every image's
+ * contributing; the times are left as they are.  0, or -1 for a null pointer, K outside 1 .. 32 or a mask with a bit at or above K */
+int sift3d_average_counts(const uint32_t *mask, int64_t n, int32_t K, int32_t trim, int32_t min_count, sift3d_average_report *report);
+/* The report as text: "# images K trim t min_count c", "# voxels N none a below b", "# image contributing upload_ms" and one line per
+ * image, "# n voxels" and one line per n = 0 .. K, "# kernel_ms wall_ms" and their line.  Returns the length the whole text needs, as
+ * snprintf does, or -1 for a null report or images outside 1 .. 32; buf holds at most len - 1 characters of it.  4096 bytes hold every report. */
+int64_t sift3d_average_report_text(const sift3d_average_report *report, char *buf, int64_t len);
+/* The node-wise mean of K fields on one grid: out->disp[i] = (float)((sum of (double)fields[k].disp[i] in image order) / (double)K).
+ * Fills out->n, origin and spacing from fields[0].  SIFT3D_ERR_ARG with text: K outside 1 .. 32, a null pointer, a field whose disp holds
+ * fewer than 3 n0 n1 n2 floats, a field whose n, origin bits or spacing bits differ from those of the first (the text names it);
+ * SIFT3D_ERR_CAPACITY with the grid filled in where out->capacity < 3 n0 n1 n2. */
+int sift3d_mean_field(int32_t K, const sift3d_field *fields, sift3d_field *out, char *err, int64_t err_len);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
