@@ -40,6 +40,7 @@ FEATCLEAN = os.path.join(CSRC, "_build", "featClean")
 FEATCOMPARE = os.path.join(CSRC, "_build", "featCompare")
 FEATREGISTER = os.path.join(CSRC, "_build", "featRegister")
 FEATAVERAGE = os.path.join(CSRC, "_build", "featAverage")
+FEATNORMALIZE = os.path.join(CSRC, "_build", "featNormalize")
 
 DESC_SIFT, DESC_BRIEF, DESC_RRIEF, DESC_NRRIEF = 0, 1, 2, 3
 ABI_VERSION = 7   # SIFT3D_ABI_VERSION of include/sift3d.h: the structure layouts this file mirrors
@@ -206,6 +207,9 @@ def hip_lib():
     _sig(L.sift3d_warp_histogram, I, I, P, I64, I64, I64, P, I64, I64, I64, P, C.c_int32, C.c_int32, P, P, C.c_int32, C.c_int32, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_register_affine, I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P, C.c_char_p, I64)
     _sig(L.sift3d_average_warped, I, I64, I64, I64, P, C.c_int32, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_overlap_histograms, I, I, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_apply_transfer, I, I, P, I64, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_normalize_intensity, I, P, I64, I64, I64, P, P, P, P, P, P, C.c_char_p, I64)
     _hip = L
     return L
 
@@ -302,6 +306,11 @@ def host_lib():
     _sig(L.sift3d_average_counts, I, P, I64, C.c_int32, C.c_int32, C.c_int32, P)
     _sig(L.sift3d_average_report_text, I64, P, C.c_char_p, I64)
     _sig(L.sift3d_mean_field, I, C.c_int32, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_normalize_defaults, None, P)
+    _sig(L.sift3d_normalize_check, I, P, C.c_char_p, I64)
+    _sig(L.sift3d_normalize_transfer, I, C.c_int32, C.c_int32, P, P, P, P, P, P, C.c_char_p, I64)
+    _sig(L.sift3d_transfer_check, I, P, C.c_char_p, I64)
+    _sig(L.sift3d_normalize_report_text, I64, P, C.c_char_p, I64)
     L.free_ptr = C.CDLL(None).free
     L.free_ptr.argtypes = [C.c_void_p]
     _host = L
@@ -2070,6 +2079,177 @@ def average_warped(shape, images, grid_vox2key=None, **params):
     p, rep = average_params(**params), AverageReport()
     _call("sift3d_average_warped", nx, ny, nz, _ptr(_m16(grid_vox2key)), K, arr, C.byref(p), avg.ctypes.data, var.ctypes.data, mask.ctypes.data, C.byref(rep))
     return avg, var, mask, _average_report_dict(rep)
+
+
+# ---- intensity matching of a registered image (featNormalize), DESIGN.md section 7s -------------------------------------------------
+NORMALIZE_BINS, NORMALIZE_MAX_KNOTS = 1024, 257
+NORMALIZE_MODES = {"linear": 0, "hist": 1}
+NORMALIZE_COUNTS = ("masked", "outside", "excluded")
+
+
+class NormalizeParams(C.Structure):
+    """sift3d_normalize_params"""
+    _fields_ = [("mode", C.c_int32), ("knots", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Transfer(C.Structure):
+    """sift3d_transfer"""
+    _fields_ = [("mode", C.c_int32), ("m", C.c_int32), ("a_lo", C.c_float), ("a_hi", C.c_float), ("b_lo", C.c_float), ("b_hi", C.c_float), ("wa", C.c_double),
+                ("tail", C.c_double), ("xb", C.c_double * NORMALIZE_MAX_KNOTS), ("xa", C.c_double * NORMALIZE_MAX_KNOTS), ("slope", C.c_double * NORMALIZE_MAX_KNOTS)]
+
+
+class NormalizeReport(C.Structure):
+    """sift3d_normalize_report"""
+    _fields_ = [("mode", C.c_int32), ("knots", C.c_int32), ("reference_voxels", C.c_int64), ("image_voxels", C.c_int64), ("counts", C.c_int64 * 3),
+                ("sums", C.c_int64 * 6), ("hist_ms", C.c_double), ("apply_ms", C.c_double), ("wall_ms", C.c_double), ("table", Transfer)]
+
+
+def normalize_params(**kw):
+    """sift3d_normalize_defaults, then the given fields: mode ("linear", "hist" or its number), knots, device"""
+    p = NormalizeParams()
+    host_lib().sift3d_normalize_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k == "mode":
+            p.mode = int(NORMALIZE_MODES.get(v, v))
+        elif k in ("knots", "device"):
+            setattr(p, k, int(v))
+        else:
+            raise ValueError("no normalisation parameter %s" % k)
+    return p
+
+
+def normalize_check(p):
+    """sift3d_normalize_check: None, or the text with which the parameters are refused"""
+    err = C.create_string_buffer(512)
+    return None if host_lib().sift3d_normalize_check(C.byref(p), err, len(err)) == 0 else err.value.decode()
+
+
+def _transfer_dict(t):
+    m = int(t.m)
+    return {"mode": int(t.mode), "m": m, "a_range": (np.float32(t.a_lo), np.float32(t.a_hi)), "b_range": (np.float32(t.b_lo), np.float32(t.b_hi)), "wa": float(t.wa),
+            "tail": float(t.tail), "xb": np.array(t.xb[:m], np.float64), "xa": np.array(t.xa[:m], np.float64), "slope": np.array(t.slope[:max(m - 1, 0)], np.float64),
+            "struct": t}
+
+
+def transfer_struct(d):
+    """a Transfer from a table dict (its struct, or its fields: mode, a_range, b_range, wa, tail, xb, xa, slope)"""
+    if isinstance(d, Transfer):
+        return d
+    if d.get("struct") is not None:
+        return d["struct"]
+    t = Transfer()
+    t.mode, t.m = int(d.get("mode", 0)), len(d["xb"])
+    (t.a_lo, t.a_hi), (t.b_lo, t.b_hi) = d["a_range"], d["b_range"]
+    t.wa, t.tail = float(d["wa"]), float(d["tail"])
+    for k in range(min(t.m, NORMALIZE_MAX_KNOTS)):
+        t.xb[k], t.xa[k] = float(d["xb"][k]), float(d["xa"][k])
+        if k < len(d["slope"]):
+            t.slope[k] = float(d["slope"][k])
+    return t
+
+
+def normalize_transfer(mode, hist_a, hist_b, sums, a_range, b_range, knots=64):
+    """sift3d_normalize_transfer: the table dict (mode, m, a_range, b_range, wa, tail, xb, xa, slope) of two histograms (1024 int64 each)
+    and the six sums; raises Sift3DError with the refusal's text"""
+    ha, hb, s = (np.ascontiguousarray(v, np.int64) for v in (hist_a, hist_b, sums))
+    if ha.size != NORMALIZE_BINS or hb.size != NORMALIZE_BINS or s.size != 6:
+        raise ValueError("two histograms of 1024 words and six sums")
+    ar, br = (C.c_float * 2)(*[float(v) for v in a_range]), (C.c_float * 2)(*[float(v) for v in b_range])
+    t, err = Transfer(), C.create_string_buffer(512)
+    rc = host_lib().sift3d_normalize_transfer(int(NORMALIZE_MODES.get(mode, mode)), int(knots), ha.ctypes.data, hb.ctypes.data, s.ctypes.data, ar, br, C.byref(t), err, len(err))
+    if rc != 0:
+        e = Sift3DError("sift3d_normalize_transfer -> %d: %s" % (rc, err.value.decode(errors="replace")))
+        e.code = rc
+        raise e
+    return _transfer_dict(t)
+
+
+def transfer_check(table):
+    """sift3d_transfer_check: None, or the text with which the table is refused"""
+    err = C.create_string_buffer(512)
+    return None if host_lib().sift3d_transfer_check(C.byref(transfer_struct(table)), err, len(err)) == 0 else err.value.decode()
+
+
+def _normalize_image(a):
+    """(AverageImage, what it points to) of an image dict: image and optionally t, vox2key, field, as average_warped takes them"""
+    im = _f32(a["image"])
+    if im.ndim != 3:
+        raise ValueError("the image is not (nz, ny, nx)")
+    mv, tm = _m16(a.get("vox2key")), _m16(a.get("t"))
+    fs, disp = _field_struct(a["field"]) if a.get("field") is not None else (None, None)
+    s = AverageImage()
+    s.image = im.ctypes.data
+    s.nz, s.ny, s.nx = im.shape
+    s.vox2key, s.moving_to_fixed = _ptr(mv), _ptr(tm)
+    s.field = C.addressof(fs) if fs is not None else None
+    return s, (im, mv, tm, fs, disp)
+
+
+def _reference(reference, mask):
+    r = _f32(reference)
+    if r.ndim != 3:
+        raise ValueError("the reference is not (nz, ny, nx)")
+    k = None if mask is None else _f32(mask)
+    if k is not None and k.shape != r.shape:
+        raise ValueError("the mask is on the reference's grid")
+    return r, k
+
+
+def overlap_histograms(reference, image, ref_range, image_range, ref_vox2key=None, mask=None, device=0, return_ms=False):
+    """sift3d_overlap_histograms: (hist_a int64 1024, hist_b int64 1024, sums: six Python integers, counts: a dict masked, outside,
+    excluded) of the reference (nz, ny, nx) and an image dict (image, t, vox2key, field) with the ranges given.  return_ms=True appends kernel_ms."""
+    r, k = _reference(reference, mask)
+    s, keep = _normalize_image(image)
+    nz, ny, nx = r.shape
+    ha, hb, sums, counts, ms = np.zeros(NORMALIZE_BINS, np.int64), np.zeros(NORMALIZE_BINS, np.int64), np.zeros(6, np.int64), np.zeros(3, np.int64), C.c_double(0.0)
+    rr, ir = (C.c_float * 2)(*[float(v) for v in ref_range]), (C.c_float * 2)(*[float(v) for v in image_range])
+    _call("sift3d_overlap_histograms", int(device), r.ctypes.data, nx, ny, nz, _ptr(_m16(ref_vox2key)), None if k is None else k.ctypes.data, C.addressof(s), rr, ir,
+          ha.ctypes.data, hb.ctypes.data, sums.ctypes.data, counts.ctypes.data, C.byref(ms))
+    out = (ha, hb, [int(v) for v in sums], dict(zip(NORMALIZE_COUNTS, (int(v) for v in counts))))
+    return out + (ms.value,) if return_ms else out
+
+
+def apply_transfer(image, table, device=0, return_ms=False):
+    """sift3d_apply_transfer: the table (normalize_transfer's dict, or a Transfer) applied to every voxel of image; float32 of its shape"""
+    v = _f32(image)
+    out, ms = np.empty(v.shape, np.float32), C.c_double(0.0)
+    _call("sift3d_apply_transfer", int(device), v.ctypes.data, v.size, C.byref(transfer_struct(table)), out.ctypes.data, C.byref(ms))
+    return (out, ms.value) if return_ms else out
+
+
+def _normalize_report_dict(r):
+    return {"mode": int(r.mode), "knots": int(r.knots), "reference_voxels": int(r.reference_voxels), "image_voxels": int(r.image_voxels),
+            "counts": dict(zip(NORMALIZE_COUNTS, (int(v) for v in r.counts))), "sums": [int(v) for v in r.sums], "hist_ms": float(r.hist_ms),
+            "apply_ms": float(r.apply_ms), "wall_ms": float(r.wall_ms), "table": _transfer_dict(r.table) if r.table.m >= 2 else None, "struct": r}
+
+
+def normalize_intensity(reference, image, ref_vox2key=None, mask=None, **params):
+    """sift3d_normalize_intensity: the image dict (image, t, vox2key, field) on its own grid on the reference's intensity scale: (out
+    float32 of the image's shape, report dict).  params: fields of normalize_params.  A refusal raises Sift3DError with .report, the
+    counts as far as they were taken."""
+    r, k = _reference(reference, mask)
+    s, keep = _normalize_image(image)
+    nz, ny, nx = r.shape
+    out, p, rep = np.empty(keep[0].shape, np.float32), normalize_params(**params), NormalizeReport()
+    try:
+        _call("sift3d_normalize_intensity", r.ctypes.data, nx, ny, nz, _ptr(_m16(ref_vox2key)), None if k is None else k.ctypes.data, C.addressof(s), C.byref(p),
+              out.ctypes.data, C.byref(rep))
+    except Sift3DError as e:
+        e.report = _normalize_report_dict(rep)
+        raise
+    return out, _normalize_report_dict(rep)
+
+
+def normalize_report_text(report):
+    """sift3d_normalize_report_text of what normalize_intensity returned as its report (or of a NormalizeReport)"""
+    r = report["struct"] if isinstance(report, dict) else report
+    need = host_lib().sift3d_normalize_report_text(C.byref(r), None, 0)
+    if need < 0:
+        raise Sift3DError("sift3d_normalize_report_text -> %d" % need)
+    buf = C.create_string_buffer(need + 1)
+    if host_lib().sift3d_normalize_report_text(C.byref(r), buf, len(buf)) != need:
+        raise Sift3DError("sift3d_normalize_report_text: the length changed")
+    return buf.value.decode()
 
 
 def _map12(m):

@@ -1643,6 +1643,101 @@ int64_t sift3d_average_report_text(const sift3d_average_report *report, char *bu
  * SIFT3D_ERR_CAPACITY with the grid filled in where out->capacity < 3 n0 n1 n2. */
 int sift3d_mean_field(int32_t K, const sift3d_field *fields, sift3d_field *out, char *err, int64_t err_len);
 
+/* ---- intensity matching of a registered image (featNormalize; beyond the reference) -----------------------------------------------
+ * DESIGN.md section 7s states the contract; tests/normalize_oracle.c restates it serially.  The GPU makes two histograms, integer sums
+ * and counts over the reference grid, then applies a transfer table to every voxel of the image; the table is host arithmetic in
+ * double (normalize_host.c, built without contraction), so every word of every result is held to the oracle by equality of bits.
+ *
+ * Inputs: R, the reference, nx ny nz floats with ref_vox2key; B, the image, a sift3d_average_image (its extents, vox2key,
+ * moving_to_fixed and field; NULL: identity or none) in featResample's moving role against R; an optional mask M of nx ny nz floats.
+ * Every extent 1 .. 4096, at most 2^30 voxels per volume.
+ * Ranges: (alo, ahi) = sift3d_blockmatch_range of R, (blo, bhi) of B, each over its whole volume.
+ * Per reference voxel x: a = R[x]; b = B sampled linearly with fill NaN at x's position, with a field sift3d_resample_field's
+ * arithmetic, without one sift3d_resample_affine's, bit for bit; qa = q(a; alo, ahi), qb = q(b; blo, bhi), section 7f's q.
+ * Classes, exclusive, tested in this order: masked (M given and M[x] not finite or == 0); outside (x's position fails the sampler's
+ * inside test 0 <= q <= extent - 1, a NaN position included); excluded (qa < 0 or qb < 0); counted.
+ * The GPU returns hist_a[1024] and hist_b[1024] (int64: the counted voxels by qa and by qb), the six sums n, Sa, Sb, Saa, Sbb, Sab of
+ * the similarity section over the counted voxels, and counts[3] = masked, outside, excluded.
+ *
+ * The transfer table: m >= 2 knots, xb strictly increasing, xa non-decreasing, slope[k] = (xa[k+1] - xa[k]) / (xb[k+1] - xb[k]) for
+ * k < m - 1, tail = (xa[m-1] - xa[0]) / (xb[m-1] - xb[0]), all doubles in quantiser units; both ranges; wa = ((double)ahi -
+ * (double)alo) / 1023.0.
+ * linear: Va = n Saa - Sa^2, Vb = n Sbb - Sb^2, exact in 128-bit integers, converted to double once; ma = (double)Sa / (double)n,
+ * mb = (double)Sb / (double)n; g = sqrt(Va) / sqrt(Vb); xb = {0, 1023}, xa = {ma + (0 - mb) g, ma + (1023 - mb) g}.  Refused unless
+ * n >= 2, Va > 0 and Vb > 0.
+ * hist (Q knots asked for, 2 .. 256): for j = 0 .. Q, r_j = (j (n - 1)) / Q (integer division); in a histogram h with running sums
+ * cum_i (cum_-1 = 0), i the smallest bin with cum_i > r_j: x_j = ((double)i - 0.5) + ((double)(r_j - cum_(i-1)) + 0.5) / (double)h_i;
+ * xa_j from hist_a, xb_j from hist_b.  Knot 0 is kept, knot j iff xb_j > the xb of the last kept knot.  Refused when n < 2, when fewer
+ * than two knots are kept, or when the first and last kept xa are equal.
+ * Applying it to a voxel v of B: a non-finite v keeps its bits; else u = (((double)v - blo) / (bhi - blo)) 1023, unrounded and
+ * unclamped; u < xb[0]: y = xa[0] + (u - xb[0]) tail; u >= xb[m-1]: y = xa[m-1] + (u - xb[m-1]) tail; else, k the largest index
+ * with xb[k] <= u, y = fmin(xa[k] + (u - xb[k]) slope[k], xa[k+1]); out = (float)((double)alo + y wa). */
+#define SIFT3D_NORMALIZE_BINS 1024
+#define SIFT3D_NORMALIZE_MAX_KNOTS 257 /* Q + 1 at Q = 256 */
+#define SIFT3D_NORMALIZE_COUNTS 3      /* masked, outside, excluded */
+#define SIFT3D_NORMALIZE_LINEAR 0
+#define SIFT3D_NORMALIZE_HIST 1
+
+typedef struct {
+    int32_t mode;   /* SIFT3D_NORMALIZE_LINEAR; or _HIST */
+    int32_t knots;  /* Q: 64; 2 .. 256; read under _HIST only */
+    int32_t device; /* 0 */
+    int32_t reserved;
+} sift3d_normalize_params;
+
+typedef struct {
+    int32_t mode;
+    int32_t m;                    /* the kept knots, 2 .. SIFT3D_NORMALIZE_MAX_KNOTS */
+    float a_lo, a_hi, b_lo, b_hi; /* the reference's range and the image's */
+    double wa, tail;
+    double xb[SIFT3D_NORMALIZE_MAX_KNOTS], xa[SIFT3D_NORMALIZE_MAX_KNOTS];
+    double slope[SIFT3D_NORMALIZE_MAX_KNOTS]; /* slope[m - 1 ..] = 0: not read */
+} sift3d_transfer;
+
+typedef struct {
+    int32_t mode, knots;                     /* as asked for */
+    int64_t reference_voxels, image_voxels;  /* nx ny nz; mx my mz */
+    int64_t counts[SIFT3D_NORMALIZE_COUNTS]; /* masked, outside, excluded */
+    int64_t sums[SIFT3D_SIMILARITY_SUMS];    /* n, Sa, Sb, Saa, Sbb, Sab */
+    double hist_ms, apply_ms, wall_ms;       /* device time of either launch; host time of the whole call */
+    sift3d_transfer table;
+} sift3d_normalize_report;
+
+/* The first kernel alone on host arrays, with the ranges the caller passes (lo, hi each: finite, hi > lo).  mask may be NULL;
+ * hist_a, hist_b: 1024 int64 each; sums: SIFT3D_SIMILARITY_SUMS int64; counts: SIFT3D_NORMALIZE_COUNTS int64; kernel_ms may be NULL.
+ * SIFT3D_ERR_ARG with text naming the argument, before anything is allocated: a null pointer, an extent outside 1 .. 4096 or more than
+ * 2^30 voxels (either volume), a range, a matrix that sift3d_resample_map refuses, a field that sift3d_resample_field refuses. */
+int sift3d_overlap_histograms(int device, const float *reference, int64_t nx, int64_t ny, int64_t nz, const float ref_vox2key[16], const float *mask,
+                              const sift3d_average_image *image, const float ref_range[2], const float image_range[2], int64_t *hist_a, int64_t *hist_b,
+                              int64_t *sums, int64_t *counts, double *kernel_ms, char *err, int64_t err_len);
+/* The second kernel alone: out[i] = the table applied to image[i], n voxels (1 .. 2^30), host arrays.  SIFT3D_ERR_ARG with text: a null
+ * pointer, n, a table that sift3d_transfer_check refuses. */
+int sift3d_apply_transfer(int device, const float *image, int64_t n, const sift3d_transfer *table, float *out, double *kernel_ms, char *err,
+                          int64_t err_len);
+/* The stage: the ranges, one upload per volume, the histogram launch, the table, the apply launch.  out: mx my mz floats, the image on
+ * its own grid on the reference's intensity scale; p NULL: defaults; report may be NULL.  SIFT3D_ERR_ARG with text, before anything is
+ * allocated: what sift3d_overlap_histograms refuses, what sift3d_normalize_check refuses, an image without two distinct finite values;
+ * and after the histogram launch what sift3d_normalize_transfer refuses (the counts are in the report then). */
+int sift3d_normalize_intensity(const float *reference, int64_t nx, int64_t ny, int64_t nz, const float ref_vox2key[16], const float *mask,
+                               const sift3d_average_image *image, const sift3d_normalize_params *p, float *out, sift3d_normalize_report *report,
+                               char *err, int64_t err_len);
+/* Host helpers (also in libsift3d_host.so). */
+void sift3d_normalize_defaults(sift3d_normalize_params *p);
+/* 0, or -1 and into err which field is refused, with its value: mode, knots (under _HIST) */
+int sift3d_normalize_check(const sift3d_normalize_params *p, char *err, int64_t err_len);
+/* The table from the histograms (1024 int64 each), the sums and both ranges (lo, hi).  0, or -1 with the refusal's text in err: a null
+ * pointer, a mode or Q that sift3d_normalize_check refuses, a range that is not finite or has hi <= lo, sums[0] other than the total of
+ * either histogram or a negative word, and the refusals of the two modes above. */
+int sift3d_normalize_transfer(int32_t mode, int32_t knots, const int64_t *hist_a, const int64_t *hist_b, const int64_t *sums, const float a_range[2],
+                              const float b_range[2], sift3d_transfer *table, char *err, int64_t err_len);
+/* 0, or -1 with text: m outside 2 .. 257, xb not strictly increasing, xa decreasing, a value that is not finite, a range */
+int sift3d_transfer_check(const sift3d_transfer *table, char *err, int64_t err_len);
+/* The report as text: "# mode linear|hist knots Q kept m", "# range_reference lo hi", "# range_image lo hi", "# reference_voxels N counted
+ * n masked a outside b excluded c", "# image_voxels N", "# knot xb xa slope" and one line per kept knot (%.17g), "# tail wa" and their
+ * line, "# hist_ms apply_ms wall_ms" and their line.  Returns the length the whole text needs, as snprintf does, or -1 for a null report
+ * or a table with m outside 2 .. 257; buf holds at most len - 1 characters of it.  32768 bytes hold every report. */
+int64_t sift3d_normalize_report_text(const sift3d_normalize_report *report, char *buf, int64_t len);
+
 /* ---- measurement ------------------------------------------------------------
  * Device time per stage of the last sift3d_detect/sift3d_extract call, from
  * HIP events recorded on the stream the kernels ran on. */
